@@ -1,6 +1,6 @@
 """Benchmark: TaxID damage fits/s of the MI355X fit engine (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,7 +20,15 @@ per-GPU share (seed 3): every rank's shard and the one-GPU base (c4_one_gpu)
 fit exactly the same taxa, so value_N / (N * c4_one_gpu) is an exact
 efficiency.
 
-The N = 1 line also carries c3_nuts: BASELINE config C3 (100k TaxIDs, the
+A plain run sets up, warms up, times the K steps and prints the headline line
+with the HBM roofline its own steps give.  --dump-outputs DIR also writes what
+the last timed step returned (out, pred, status; on N > 1 the records rank 0
+gathered) as DIR/<name>.npy, all finite (fields that are NaN by definition are
+written as 0 and marked in <name>_nonfinite): the inputs are seeded, so two builds can be
+compared output for output.  Everything below marked --full takes runs of its
+own and is measured only with that option.
+
+With --full the N = 1 line also carries c3_nuts: BASELINE config C3 (100k TaxIDs, the
 reference's own inference -- NUTS 500 warmup + 1000 draws on all 6 sub-fits,
 fits.py:382-387, 792-799), one warm-up and one timed call, with its rooflines
 and its distributional parity against the CPU oracle's sampler.
@@ -31,12 +39,12 @@ Printed JSON (rank 0): the driver contract fields plus
                     on the launch stream); PMC traffic from profiles/;
                     hbm_intermediate: the 816 B/taxon the kernel actually moves
                     (the K0 -> K1 -> K3 hand-off through the record)
-  compute_roofline  useful point-evaluations/s vs the register-only probe of the
+  compute_roofline  (--full) useful point-evaluations/s vs the register-only probe of the
                     same point evaluation (the kernel's real bound: FP64 VALU)
-  host_to_host      (N = 1) the product call from pinned host buffers: H2D of
+  host_to_host      (--full, N = 1) the product call from pinned host buffers: H2D of
                     y, N (+ the mismatch counts), the fit, D2H of the 32 record
                     columns, predictions and status
-  cpu_baseline      (N = 1) the CPU oracle (C/OpenMP restatement of the same
+  cpu_baseline      (--full, N = 1) the CPU oracle (C/OpenMP restatement of the same
                     fit) on the box's core share, median of 5 over the whole
                     workload, with the reference-dispatch-shape figure beside
                     it (tools/cpu_reference_dispatch.py: scipy per taxon, a Pool
@@ -83,10 +91,16 @@ def parse():
     ap.add_argument("--taxa", type=int, default=0, help="taxa per GPU (default: 10k MAP / 100k NUTS)")
     ap.add_argument("--mode", choices=["map", "nuts"], default="map",
                     help="map: config C2 (the headline); nuts: config C3, the reference's sampler")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: compute_roofline, host_to_host, c4_one_gpu, "
+                    "c3_nuts, cpu_baseline + parity, per_rank (the --no-* options switch single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (out, pred, status; non-finite fields as 0 with a mask "
+                    "beside them) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity")
     ap.add_argument("--no-c4-base", action="store_true",
-                    help="N=1: skip the C4-on-one-GPU strong-scaling base (c4_one_gpu)")
-    ap.add_argument("--no-c3", action="store_true", help="N=1 MAP: skip the C3 NUTS leg (c3_nuts)")
+                    help="--full, N=1: skip the C4-on-one-GPU strong-scaling base (c4_one_gpu)")
+    ap.add_argument("--no-c3", action="store_true", help="--full, N=1 MAP: skip the C3 NUTS leg (c3_nuts)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the process's core share (affinity, OMP_NUM_THREADS)")
     ap.add_argument("--workload", choices=["c2", "c4"], default=None,
                     help="default: c2 at N = 1 (the headline), c4 (1M taxa, strong scaling) at N > 1")
@@ -95,7 +109,42 @@ def parse():
         a.steps = 20 if a.mode == "map" else 1
     if a.warmup is None:
         a.warmup = 3 if a.mode == "map" else 1
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return a
+
+
+DUMP_MAX_BYTES = 60_000_000  # of array data in all: the files stay under 64 MB
+
+
+def dump_outputs(dest, out, pred, status) -> None:
+    """--dump-outputs: the results of the last timed step as a caller of the
+    timed path receives them -- out (float64 [T, columns]: the record), pred
+    (float32 [T, 3, 30]) and status (written as float32 [T]) -- one .npy each.
+    Every file holds finite numbers only, so any two dumps can be subtracted:
+    a record field that is NaN by definition (the reference's 0/0, e.g. the
+    asymmetry of a taxon whose forward and reverse fits coincide) or infinite
+    is written as 0 in out / pred and marked in out_nonfinite / pred_nonfinite
+    (float32, same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf), so a value turning
+    NaN or back shows as a difference there.  Above DUMP_MAX_BYTES in all, the
+    same fixed sample of the taxa (seed 0, in taxon order) is written of each,
+    with its row numbers beside it (sample_rows, float64)."""
+    dest = Path(dest)
+    dest.mkdir(parents=True, exist_ok=True)
+    arrays = {"status": np.asarray(status, np.float32)}
+    for name, a in (("out", np.array(out, np.float64)), ("pred", np.array(pred, np.float32))):
+        code = np.where(np.isnan(a), 1, np.where(a == np.inf, 2, np.where(a == -np.inf, 3, 0))).astype(np.float32)
+        a[code != 0] = 0
+        arrays[name], arrays[name + "_nonfinite"] = a, code
+    T = len(arrays["status"])
+    row_bytes = sum(a.nbytes // max(T, 1) for a in arrays.values())
+    if T * row_bytes > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(T, size=n, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(dest / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def pmc_traffic(kernel: str = "fit_kernel", taxa: int = TAXA_PER_GPU):
@@ -211,7 +260,7 @@ def main():
     if args.cpu_threads > 0:
         cores = args.cpu_threads
     ref_dispatch = None
-    if not args.no_cpu_baseline and world == 1 and not nuts:
+    if args.full and not args.no_cpu_baseline and world == 1 and not nuts:
         ref_dispatch = ref_dispatch_baseline(cores)  # before any GPU call
 
     import torch
@@ -256,7 +305,7 @@ def main():
         engine.fit_batch_device(ty, tN, tm, opts, fb, stream=stream)
         if world > 1:  # the one gather of the packed records to rank 0 (synchronous)
             buf = rec.stage()
-            gather_records(buf, cap, rank, world)
+            return gather_records(buf, cap, rank, world)
 
     for _ in range(args.warmup):
         step()
@@ -268,8 +317,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    parts = None
     for i in range(args.steps):
-        step()
+        parts = step()
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -283,7 +333,7 @@ def main():
     engine.profile_enable(False)
     assert n_calls == min(args.steps, 256), (n_calls, args.steps)  # the library keeps up to 256 calls
     ranks = None
-    if world > 1:
+    if world > 1 and args.full:
         # per-rank split of a step (after the timed region, so its
         # synchronisations stay out of it): the fit call and the gather, by
         # the wall clock over a few extra steps; every rank's pair to rank 0
@@ -308,6 +358,14 @@ def main():
 
     o = fb.out.cpu().numpy()
     st = fb.status.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        if world > 1:  # what rank 0 holds after the gather: every shard's records, in taxon order
+            from metadamage_amd.distributed import unpack_gathered
+
+            dump_outputs(args.dump_outputs, *unpack_gathered(parts, total_per_step, world))
+        else:
+            dump_outputs(args.dump_outputs, o, fb.pred.cpu().numpy(), st)
+    del parts
     evals = o[:, _lib.F_DIAG + 5 :: _lib.DIAG_STRIDE][:, :6]
     useful_pe = float((evals * NPTS).sum())
     # position slots the fit kernel's 32-lane groups spent: an all-position fit
@@ -321,7 +379,7 @@ def main():
         # at byte 128 / 136): wave-trips with a running slot, running slot-trips
         util = fb.workspace[128:144].view(torch.int64).cpu().numpy()
         # compute roofline: register-only probe of the same potential evaluation
-        probe_rate = nuts_probe_rate(engine, dev, stream)
+        probe_rate = nuts_probe_rate(engine, dev, stream) if args.full else None
         print(json.dumps(nuts_line(args, T, world, elapsed, call_ms_sum, fit_ms_sum, n_calls, o, st, b, smp,
                                    util, probe_rate)), flush=True)
     elif rank == 0:
@@ -334,17 +392,6 @@ def main():
         # entry per taxon: the PMD-all mode, the taxon index, the epoch tag)
         inter_bytes = FIT_BYTES_PER_TAXON * T + READY_BYTES_PER_TAXON * T
         traffic = pmc_traffic("fit_kernel", T)
-        # compute roofline: register-only probe of the same point evaluation
-        n_waves, iters = 256 * 16, 64
-        engine.peak_probe(n_waves, iters, stream=stream)  # warm
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(3):
-            engine.peak_probe(n_waves, iters, stream=stream)
-        e1.record(stream)
-        torch.cuda.synchronize(dev)
-        probe_rate = 3 * n_waves * 60 * iters / (e0.elapsed_time(e1) / 1e3)  # 60 points per wave-iteration
-        useful_rate = useful_pe / k_avg_s
         if workload == "c4":
             wl = (f"C4: 1M synthetic TaxIDs x +-15 positions sharded over {world} GPUs ({T} on rank 0), MAP "
                   "beta-binomial damage fit (6 sub-fits per TaxID) + record assembly + predictive HPDI, then one "
@@ -400,7 +447,16 @@ def main():
                 "call_bytes_per_taxon": CALL_BYTES_PER_TAXON,
                 "call_achieved": round(CALL_BYTES_PER_TAXON * T / call_avg_s / 1e9, 3),
             },
-            "compute_roofline": {
+            "status_ok_frac": float((st == 0).mean()),
+            # items the HPDI stream's early waves handed to the late launch in the
+            # last call (their bounded wait, DESIGN.md 4): 0 when undisturbed
+            "hpdi_deferred_items": int(fb.workspace[128:132].view(torch.int32).item() & ~0x40000000),
+        }
+        if args.full:
+            # compute roofline: register-only probe of the same point evaluation
+            probe_rate = map_probe_rate(engine, dev, stream)
+            useful_rate = useful_pe / k_avg_s
+            line["compute_roofline"] = {
                 "bound": "fp64-valu",
                 "achieved": round(useful_rate, 1),
                 "peak": round(probe_rate, 1),
@@ -408,13 +464,8 @@ def main():
                 "frac": useful_rate / probe_rate,
                 "slot_util": useful_pe / slot_pe,
                 "point_evals_per_taxon": useful_pe / T,
-            },
-            "status_ok_frac": float((st == 0).mean()),
-            # items the HPDI stream's early waves handed to the late launch in the
-            # last call (their bounded wait, DESIGN.md 4): 0 when undisturbed
-            "hpdi_deferred_items": int(fb.workspace[128:132].view(torch.int32).item() & ~0x40000000),
-        }
-        if world == 1 and b is not None:
+            }
+        if args.full and world == 1 and b is not None:
             line["host_to_host"] = host_to_host(engine, b, opts, dev, max(5, args.steps // 2), generate)
         if ranks is not None:
             from metadamage_amd.distributed import REC_BYTES
@@ -428,17 +479,17 @@ def main():
             line["gather_model"] = gather_model(REC_BYTES * cap, world, ranks)
             line["per_rank_note"] = ("a step split into the fit call and the one gather by the wall clock, "
                                      "measured after the timed region (synchronised per phase)")
-        if (world == 1 and workload == "c2" or workload == "c4" and world > 1) and not args.no_c4_base:
+        if args.full and (world == 1 and workload == "c2" or workload == "c4" and world > 1) and not args.no_c4_base:
             # the strong-scaling base, measured in the same run on rank 0's GPU
             # (at N > 1 the other ranks wait at the closing barrier):
             # value_N / (N * c4_one_gpu.value) is the C4 scaling efficiency
             line["c4_one_gpu"] = c4_one_gpu(engine, _lib, generate, dev, stream)
-        if world == 1 and workload == "c2" and not args.no_c3:
+        if args.full and world == 1 and workload == "c2" and not args.no_c3:
             # config C3, the reference's own inference, in the driver's default run
             del fb, rec
             torch.cuda.empty_cache()
             line["c3_nuts"] = c3_nuts(engine, _lib, generate, dev, stream, args)
-        if not args.no_cpu_baseline and world == 1 and b is not None:  # the CPU baseline is an N=1 figure
+        if args.full and not args.no_cpu_baseline and world == 1 and b is not None:  # the CPU baseline is an N=1 figure
             line["cpu_baseline"], ref = cpu_baseline(b, cores, visible)
             if ref_dispatch is not None:
                 line["cpu_baseline"]["reference_dispatch"] = ref_dispatch
@@ -464,6 +515,22 @@ def gather_model(bytes_per_peer: int, world: int, ranks) -> dict:
             "note": "one dist.gather of the packed records to rank 0 over RCCL: modelled = bytes per peer / one "
             "xGMI link (the peers send on their own links in parallel); measured = wall clock of the gather call "
             "after the fit, per rank (includes RCCL launch and the rank-0 receive)"}
+
+
+def map_probe_rate(engine, dev, stream) -> float:
+    """Point evaluations/s of the register-only probe of the MAP fit's point
+    evaluation (value + gradient + Hessian), the compute ceiling of fit_kernel."""
+    import torch
+
+    n_waves, iters = 256 * 16, 64
+    engine.peak_probe(n_waves, iters, stream=stream)  # warm
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(3):
+        engine.peak_probe(n_waves, iters, stream=stream)
+    e1.record(stream)
+    torch.cuda.synchronize(dev)
+    return 3 * n_waves * 60 * iters / (e0.elapsed_time(e1) / 1e3)  # 60 points per wave-iteration
 
 
 def nuts_probe_rate(engine, dev, stream) -> float:
@@ -514,7 +581,8 @@ def c3_nuts(engine, _lib, generate, dev, stream, args) -> dict:
     del fb, ty, tN, tm
     torch.cuda.empty_cache()
     probe_rate = nuts_probe_rate(engine, dev, stream)
-    a = types.SimpleNamespace(steps=1, warmup=1, no_cpu_baseline=args.no_cpu_baseline, cpu_threads=args.cpu_threads)
+    a = types.SimpleNamespace(steps=1, warmup=1, full=True, no_cpu_baseline=args.no_cpu_baseline,
+                              cpu_threads=args.cpu_threads)
     line = nuts_line(a, T, 1, elapsed, elapsed * 1e3, fit_ms_sum, n_calls, o, st, b, smp, util, probe_rate)
     for k in ("metric", "higher_is_better", "vs_baseline", "n_gpus"):
         line.pop(k, None)
@@ -645,7 +713,12 @@ def nuts_line(args, T, world, elapsed, call_ms_sum, fit_ms_sum, n_calls, o, st, 
             },
             "call_ms_avg": round(call_ms_sum / n_calls, 3),
         },
-        "compute_roofline": {
+        "leapfrog_point_evals_per_s": round(point_evals / k_avg_s, 1),
+        "mean_leapfrogs_per_iteration": round(float(leap.mean()), 3),
+        "status_ok_frac": float((st == 0).mean()),
+    }
+    if args.full:
+        line["compute_roofline"] = {
             "bound": "fp64-valu",
             "achieved": round(15.0 * float(util[1]) / k_avg_s, 1),
             "peak": round(probe_rate, 1),
@@ -656,12 +729,8 @@ def nuts_line(args, T, world, elapsed, call_ms_sum, fit_ms_sum, n_calls, o, st, 
             "note": "the chain kernel's potential evaluations (15 points per running chain slot per trip: "
             "leapfrogs, initial points, step-size probes; counted by the kernel) / its time, against "
             "nuts_probe_kernel, a register-only loop over the same potential_cd at the chain kernel's occupancy",
-        },
-        "leapfrog_point_evals_per_s": round(point_evals / k_avg_s, 1),
-        "mean_leapfrogs_per_iteration": round(float(leap.mean()), 3),
-        "status_ok_frac": float((st == 0).mean()),
-    }
-    if not args.no_cpu_baseline and world == 1:
+        }
+    if args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"], ref = cpu_baseline_nuts(b, args.cpu_threads or host_cores()[0])
         line["parity"] = nuts_parity(smp, st, ref)
     return line
