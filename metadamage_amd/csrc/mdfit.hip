@@ -612,6 +612,7 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
 
     // ---- 4. Newton logic (oracle: fit_one) ----------------------------------
     if (running) {
+#pragma clang fp contract(off)
       Eval tr;
       finish_eval(pa.pmd, th, acc, tr);
       ++evals;
@@ -671,7 +672,7 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
 #endif
           const bool gok = gprobe && pg_direction(u, tr.g, d);
           curG3 = tr.g[3];
-          curGd = tr.g[0] * d[0] + tr.g[1] * d[1] + tr.g[2] * d[2] + tr.g[3] * d[3];
+          curGd = fma(tr.g[3], d[3], fma(tr.g[2], d[2], fma(tr.g[1], d[1], tr.g[0] * d[0])));
           t = 1.0;
           if (gprobe) {
             if (gok) {
@@ -776,7 +777,7 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
       }
       if (!done) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ut[j] = clampd(u[j] + t * d[j], kULo[j], kUHi[j]);
+        for (int j = 0; j < 4; ++j) ut[j] = clampd(fma(t, d[j], u[j]), kULo[j], kUHi[j]);
       } else {
         // lanes 0..7 of the half write the diag slots (for an all-position fit
         // the forward half only)

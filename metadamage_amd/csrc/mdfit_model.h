@@ -344,20 +344,25 @@ __device__ __forceinline__ int hidx(int j, int m) {  // packed index, j <= m
 
 __device__ __forceinline__ void finish_eval(bool pmd, const Theta& th, const double s[kNAcc],
                                             Eval& e) {
+#pragma clang fp contract(off)
   const double q = th.q, A = th.A, c = th.c, delta = th.delta;
   const double J[4] = {q * th.omq, th.JA, 1.0, delta};
-  const double J2[4] = {J[0] * (1.0 - 2.0 * q), th.JA * (1.0 - 2.0 * A), 0.0, delta};
-  const double gp[4] = {1.0 - 3.0 * q, pmd ? 1.0 - 3.0 * A : 0.0, pmd ? -8.0 * th.iomc : 0.0,
-                        -delta / 1000.0};
+  const double J2[4] = {J[0] * fma(-2.0, q, 1.0), th.JA * fma(-2.0, A, 1.0), 0.0, delta};
+  // (0 - delta/1000, not -delta/1000: the optimiser folds a negation into the
+  // divisor, delta / -1000, a second division beside make_theta's delta / 1000;
+  // delta > 0, so both forms are the same value)
+  const double gp[4] = {fma(-3.0, q, 1.0), pmd ? fma(-3.0, A, 1.0) : 0.0, pmd ? -8.0 * th.iomc : 0.0,
+                        0.0 - delta / 1000.0};
   const double hp[4] = {-3.0 * J[0], pmd ? -3.0 * th.JA : 0.0,
-                        pmd ? -8.0 * th.iomc * th.iomc : 0.0, -delta / 1000.0};
+                        pmd ? -8.0 * th.iomc * th.iomc : 0.0, 0.0 - delta / 1000.0};
   const bool infeasible = pmd && (A + c >= 1.0);
   e.F = infeasible ? INFINITY : -(s[0] + th.lprior);
   e.mag = s[1];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const bool fixed = !pmd && (j == 1 || j == 2);
-    e.g[j] = fixed ? 0.0 : -(J[j] * s[2 + j] + gp[j]);
+    // (j == 2: J = 1 and, where not fixed, gp = -8 iomc)
+    e.g[j] = fixed ? 0.0 : -(j == 2 ? fma(-8.0, th.iomc, s[2 + j]) : fma(J[j], s[2 + j], gp[j]));
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -365,7 +370,10 @@ __device__ __forceinline__ void finish_eval(bool pmd, const Theta& th, const dou
     for (int m = j; m < 4; ++m) {
       const int k = hidx(j, m);
       double h = J[j] * s[6 + k] * J[m];
-      if (j == m) h += J2[j] * s[2 + j] + hp[j];
+      if (j == m) {
+        const double dg = fma(J2[j], s[2 + j], hp[j]);
+        h = j == 2 ? s[6 + k] + dg : fma(J[j] * s[6 + k], J[m], dg);
+      }
       const bool fixed = !pmd && (j == 1 || j == 2 || m == 1 || m == 2);
       e.H[k] = fixed ? 0.0 : -h;
     }
@@ -378,6 +386,7 @@ __device__ __forceinline__ double maxabs4(const double v[4]) {
 
 // projected-gradient size (oracle: pgnorm): 0 for a variable held on its bound
 __device__ __forceinline__ double pgnorm(const double u[4], const double g[4]) {
+#pragma clang fp contract(off)
   double m = 0.0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) m = fmax(m, fabs(u[j] - clampd(u[j] - g[j], kULo[j], kUHi[j])));
@@ -387,6 +396,7 @@ __device__ __forceinline__ double pgnorm(const double u[4], const double g[4]) {
 // the projected-gradient direction P(u - g) - u scaled to max-norm 1 (the
 // gradient fallback of fit_kernel; oracle: pg_direction); false when it vanishes
 __device__ __forceinline__ bool pg_direction(const double u[4], const double g[4], double d[4]) {
+#pragma clang fp contract(off)
   double p[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) p[j] = clampd(u[j] - g[j], kULo[j], kUHi[j]) - u[j];
@@ -411,6 +421,9 @@ __device__ __forceinline__ double rsqrt_nr(double x) {
 // Cholesky of the free block of H + mu*I (fixed / bound rows -> identity);
 // returns the first non-positive pivot's index (-1: positive definite).
 // Packed lower triangle L (same index as H), iL = 1 / diag(L).
+// (No contract(off) here on purpose, unlike its callers: every sum is an
+// explicit fma chain already, and the records of the commit that pinned the
+// callers' arithmetic were taken with this function as the compiler fuses it.)
 __device__ __forceinline__ int chol4(const bool fr[4], const double H[10], double mu, double L[10],
                                      double iL[4]) {
   int jf = -1;
@@ -444,6 +457,7 @@ __device__ __forceinline__ int chol4(const bool fr[4], const double H[10], doubl
 // inside the box, so they add nothing to it).
 __device__ __forceinline__ void free_set(bool pmd, const double u[4], const double g[4], const double H[10],
                                          double w, bool fr[4], double dbind[4]) {
+#pragma clang fp contract(off)
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const bool fixed = !pmd && (j == 1 || j == 2);
@@ -454,10 +468,19 @@ __device__ __forceinline__ void free_set(bool pmd, const double u[4], const doub
     // unless, with positive curvature, its own Newton step g/H stops short of
     // the bound (an interior optimum just inside it)
     const double hjj = H[hidx(j, j)];
-    const bool bind = (atlo && g[j] > -kEpsAct && (hjj <= 0.0 || g[j] + kEpsAct > hjj * dlo)) ||
-                      (athi && g[j] < kEpsAct && (hjj <= 0.0 || -g[j] + kEpsAct > hjj * dhi));
-    dbind[j] = (bind && !fixed) ? (atlo ? kULo[j] : kUHi[j]) - u[j] : 0.0;
-    fr[j] = !(fixed || bind);
+    // (every comparison is taken first, then combined without short-circuit:
+    // no branch and no exec-mask bookkeeping per term; the whole test sits
+    // behind one wave-uniform guard, since no lane is next to this bound on
+    // most trips.  A fixed coordinate's bind is never read.)
+    bool bind = false;
+    if (__any((atlo | athi) & !fixed)) {
+      const bool hnp = hjj <= 0.0;
+      const bool glo = g[j] > -kEpsAct, ghi = g[j] < kEpsAct;
+      const bool slo = g[j] + kEpsAct > hjj * dlo, shi = -g[j] + kEpsAct > hjj * dhi;
+      bind = (atlo & glo & (hnp | slo)) | (athi & ghi & (hnp | shi));
+    }
+    dbind[j] = (bind & !fixed) ? (atlo ? kULo[j] : kUHi[j]) - u[j] : 0.0;
+    fr[j] = !(fixed | bind);
   }
 }
 
@@ -485,6 +508,7 @@ __device__ __forceinline__ bool newton_dir(bool pmd, const double u[4], const do
   const int jf = chol4(fr, H, 0.0, L, iL);  // plain Newton: the common case
   const bool indef = jf >= 0;
   if (want_nc && indef) {
+#pragma clang fp contract(off)
     double z[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) z[j] = j == jf ? 1.0 : 0.0;
@@ -493,12 +517,15 @@ __device__ __forceinline__ bool newton_dir(bool pmd, const double u[4], const do
       if (p < jf) {
         double s = 0.0;
 #pragma unroll
-        for (int k = p + 1; k < 4; ++k) s += k <= jf ? L[hidx(p, k)] * z[k] : 0.0;  // L(k,p)
+        for (int k = p + 1; k < 4; ++k) {  // L(k,p); the first product is fused into the sum's 0
+          if (k == p + 1) s = k <= jf ? fma(L[hidx(p, k)], z[k], 0.0) : 0.0;
+          else s += k <= jf ? L[hidx(p, k)] * z[k] : 0.0;
+        }
         z[p] = -s * iL[p];
       }
     }
     const double mx = maxabs4(z);
-    const double gz = g[0] * z[0] + g[1] * z[1] + g[2] * z[2] + g[3] * z[3];
+    const double gz = fma(g[2], z[2], fma(g[1], z[1], g[0] * z[0])) + g[3] * z[3];
     const double sg = gz > 0.0 ? -1.0 : 1.0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) d[j] = sg * z[j] / mx;
@@ -547,6 +574,7 @@ __device__ __forceinline__ bool newton_dir(bool pmd, const double u[4], const do
 #pragma unroll
     for (int j = 0; j < 4; ++j) d[j] = (fr[j] && isfinite(g[j])) ? -g[j] : 0.0;
   } else {
+#pragma clang fp contract(off)
     double z[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {  // L z = -g (free rows)
