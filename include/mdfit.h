@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MDFIT_ABI_VERSION 2
+#define MDFIT_ABI_VERSION 3
 
 /* Dense count layout: one row of MDFIT_LD uint32 per taxon.
  * Column i < 15 is forward position z = i+1 (y = CT, N = C by default);
@@ -189,6 +189,50 @@ int64_t mdfit_workspace_bytes(int64_t n_taxa, const mdfit_opts* opts);
  */
 int mdfit_noise(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, double* out,
                 void* hip_stream);
+
+/* Laplace record: double lap[T][3][MDFIT_NLAPLACE], one row per PMD sub-fit
+ * (0 all positions, 1 forward, 2 reverse): q_std, A_std, c_std, phi_std,
+ * D_max_std, rho_Ac, significance, flags.  flags (an integer stored as double):
+ * bit j (1, 2, 4, 8) coordinate j of (q, A, c, phi) is free, bit 4 (16) the
+ * row is valid. */
+#define MDFIT_NLAPLACE 8
+
+/*
+ * Laplace standard errors of finished MAP records: per PMD
+ * sub-fit one evaluation of the objective's Hessian at the mode -- the fit
+ * kernel's own code, at u = (logit q, logit A, c, log(phi - 2)) rebuilt from
+ * the record's diagnostic slots -- the inverse of its block over the
+ * coordinates the optimiser's binding rule does not hold on a box bound, and
+ * the delta method to (q, A, c, phi) and D_max = A + c:
+ *   std_j = J_j sqrt(C_jj), J = (q(1-q), A(1-A), 1, phi - 2); 0 for a held j
+ *   D_max_std = sqrt(J_A^2 C_AA + C_cc + 2 J_A C_Ac)
+ *   rho_Ac = C_Ac / sqrt(C_AA C_cc)   (NaN when A or c is held)
+ *   significance = (A + c) / D_max_std (NaN when D_max_std = 0)
+ * The Hessian includes the priors: these are posterior-mode standard errors,
+ * not likelihood-only ones.  A row is valid when status[t] == 0, at least one
+ * coordinate is free, every free H_jj > 0 and every pivot of the Cholesky of
+ * the Jacobi-scaled free block exceeds 1e-8; otherwise its seven statistics
+ * are NaN and bit 4 of flags is clear (status[t] != 0: flags 0).
+ *   y, N, out, status : the inputs and results of a finished MODE_MAP
+ *                       mdfit_fit_batch call (device; read only -- records of a
+ *                       MODE_NUTS call hold posterior means, not modes, and give
+ *                       meaningless numbers)
+ *   lap               : double[n_taxa][3][MDFIT_NLAPLACE]       (device)
+ *   gh                : double[n_taxa][3][20] or NULL (device): the gradient
+ *                       g[4], then the Hessian H[4][4], at the rebuilt u (parity
+ *                       tests)
+ * One launch on hip_stream, one wave per taxon; no workspace, no side stream,
+ * no host synchronisation.  n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_laplace(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                      int64_t n_taxa, double* lap, double* gh, void* hip_stream);
+
+/* The same launch (the same kernel), which also writes the rebuilt modes it
+ * evaluates at: u double[n_taxa][3][4] or NULL (device; NaN where status[t]
+ * != 0).  For parity tests: g and H of `gh` are those of mdfit_objective at
+ * exactly these u. */
+int mdfit_map_laplace_u(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                        int64_t n_taxa, double* lap, double* gh, double* u, void* hip_stream);
 
 /*
  * Pointwise beta-binomial log-pmf (numpyro BetaBinomial.log_prob, used by

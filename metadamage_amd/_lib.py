@@ -15,7 +15,7 @@ PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = PKG_DIR / "libmdfit.so"
 
 # mirrors of include/mdfit.h
-ABI_VERSION = 2
+ABI_VERSION = 3
 NPOS = 30
 NHALF = 15
 LD = 32
@@ -28,6 +28,7 @@ F_DIAG = 32
 NOUT = 80
 NSUBFIT = 6
 DIAG_STRIDE = 8
+NLAPLACE = 8
 
 # output record field order (enum mdfit_field) == fit_results numeric columns
 RESULT_FIELDS = [
@@ -59,6 +60,9 @@ RESULT_FIELDS = [
 ]
 SUBFITS = ["PMD", "null", "PMD_forward", "PMD_reverse", "null_forward", "null_reverse"]
 DIAG_FIELDS = ["q", "A", "c", "phi", "objective", "evals", "status"]
+# Laplace record (mdfit_map_laplace): float64 [T][3][NLAPLACE], rows PMD-all, PMD-forward, PMD-reverse
+LAPLACE_FIELDS = ["q_std", "A_std", "c_std", "phi_std", "D_max_std", "rho_Ac", "significance", "flags"]
+LAPLACE_VALID = 16  # flags: bits 0..3 coordinate (q, A, c, phi) free, bit 4 valid
 
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
@@ -66,6 +70,8 @@ EXPORTED_SYMBOLS = [
     "mdfit_fit_batch",
     "mdfit_workspace_bytes",
     "mdfit_noise",
+    "mdfit_map_laplace",
+    "mdfit_map_laplace_u",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
     "mdfit_hpdi68",
@@ -137,6 +143,10 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_workspace_bytes.restype = i64
     lib.mdfit_noise.argtypes = [vp, vp, vp, i64, vp, vp]
     lib.mdfit_noise.restype = ctypes.c_int
+    lib.mdfit_map_laplace.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
+    lib.mdfit_map_laplace.restype = ctypes.c_int
+    lib.mdfit_map_laplace_u.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.mdfit_map_laplace_u.restype = ctypes.c_int
     lib.mdfit_betabinom_logpmf.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.mdfit_betabinom_logpmf.restype = ctypes.c_int
     lib.mdfit_special.argtypes = [vp, i64, vp, vp]

@@ -52,7 +52,8 @@ def cli_fit(
     substitution_bases_forward: utils.SubstitutionBases = typer.Option(utils.SubstitutionBases.CT),
     substitution_bases_reverse: utils.SubstitutionBases = typer.Option(utils.SubstitutionBases.GA),
     forced: bool = typer.Option(False, "--forced"),
-    inference: str = typer.Option("nuts", help="nuts: NUTS sampling as the reference; map: MAP fit"),
+    inference: str = typer.Option("nuts", help="nuts: NUTS sampling as the reference; map: MAP fit; "
+                                  "map-laplace: MAP fit with Laplace standard errors and significance"),
 ):
     """Fitting Ancient Damage.
 
@@ -74,8 +75,8 @@ def cli_fit(
         "version": "0.0.0",
         "inference": inference,
     }
-    if inference not in ("nuts", "map"):
-        raise typer.BadParameter("--inference must be nuts or map")
+    if inference not in ("nuts", "map", "map-laplace"):
+        raise typer.BadParameter("--inference must be nuts, map or map-laplace")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

@@ -41,6 +41,7 @@
 #include "../../include/mdfit.h"
 #include "mdfit_hpdi.h"
 #include "mdfit_host.h"
+#include "mdfit_laplace.h"
 #include "mdfit_model.h"
 #include "mdfit_special.h"
 
@@ -2026,6 +2027,22 @@ int mdfit_objective(const int32_t* model, const int32_t* subset, const uint32_t*
   hipLaunchKernelGGL(mdfit::objective_kernel, dim3((unsigned)n), dim3(mdfit::kWave), 0,
                      (hipStream_t)hip_stream, model, subset, y, N, u, n, F, g, H, ell);
   return check_launch("objective_kernel");
+}
+
+int mdfit_map_laplace(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                      int64_t n_taxa, double* lap, double* gh, void* hip_stream) {
+  return mdfit_map_laplace_u(y, N, out, status, n_taxa, lap, gh, nullptr, hip_stream);
+}
+
+int mdfit_map_laplace_u(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                        int64_t n_taxa, double* lap, double* gh, double* u, void* hip_stream) {
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !lap) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  hipLaunchKernelGGL(mdfit::laplace_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave), 0,
+                     (hipStream_t)hip_stream, y, N, out, status, n_taxa, lap, gh, u);
+  return check_launch("laplace_kernel");
 }
 
 #ifdef MDFIT_STAMP

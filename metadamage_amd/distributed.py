@@ -35,6 +35,9 @@ REC_PRED = _lib.NPRED * _lib.NPOS * 4
 REC_RES = REC_INT + REC_F32
 REC_BYTES = REC_RES + REC_PRED + 4
 REC_OUT = _lib.NOUT * 8  # the full record the kernel writes (rank-local)
+# with_laplace (a "map-laplace" run): one more f32 block [n, 3, NLAPLACE] after
+# the status, 96 B per taxon, in the same buffer and the same single gather
+REC_LAP = 3 * _lib.NLAPLACE * 4
 
 
 def shard_range(n_taxa: int, rank: int, world: int) -> tuple[int, int]:
@@ -59,15 +62,21 @@ class Records:
     bytes holding ints f64[n, 8] | floats f32[n, 17] | pred f32[n, 3, 30] |
     status i32[n].  The kernel writes pred and status in place; `stage()`
     copies the result columns of out into ints / floats (two strided device
-    copies, the second rounding to f32) before the gather."""
+    copies, the second rounding to f32) before the gather.  with_laplace: the
+    buffer is n * REC_LAP bytes longer, `lap` f32[n, 3, 8] after the status,
+    written in place by the chunked dispatch."""
 
-    def __init__(self, n: int, device):
+    def __init__(self, n: int, device, with_laplace: bool = False):
         import torch
 
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
-        self.buf = torch.empty(n * REC_BYTES, dtype=torch.uint8, device=device)
-        self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
+        self.buf = torch.empty(n * (REC_BYTES + (REC_LAP if with_laplace else 0)), dtype=torch.uint8, device=device)
+        self.lap = None
+        if with_laplace:
+            self.pred, self.status, self.ints, self.floats, self.lap = packed_views(self.buf, n, with_laplace=True)
+        else:
+            self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
         self._fidx = torch.as_tensor(FLOAT_COLS, device=device)
 
     def stage(self):
@@ -76,11 +85,12 @@ class Records:
         return self.buf
 
 
-def packed_views(buf, n: int):
+def packed_views(buf, n: int, with_laplace: bool = False):
     """Views (pred[n, 3, 30] f32, status[n] i32, ints[n, 8] f64, floats[n, 17]
     f32) into one uint8 gather buffer of n * REC_BYTES bytes laid out ints |
     floats | pred | status (torch tensor; the f64 block first keeps it 8-byte
-    aligned for any n)."""
+    aligned for any n).  with_laplace: the buffer holds n * REC_LAP more bytes
+    and a fifth view, lap[n, 3, 8] f32, follows the status."""
     o1 = n * REC_INT
     o2 = o1 + n * REC_F32
     o3 = o2 + n * REC_PRED
@@ -88,6 +98,10 @@ def packed_views(buf, n: int):
     floats = buf[o1:o2].view(dtype=_torch_dtype("float32")).view(n, len(FLOAT_COLS))
     pred = buf[o2:o3].view(dtype=_torch_dtype("float32")).view(n, _lib.NPRED, _lib.NPOS)
     status = buf[o3 : o3 + 4 * n].view(dtype=_torch_dtype("int32"))
+    if with_laplace:
+        o4 = o3 + 4 * n
+        lap = buf[o4 : o4 + n * REC_LAP].view(dtype=_torch_dtype("float32")).view(n, 3, _lib.NLAPLACE)
+        return pred, status, ints, floats, lap
     return pred, status, ints, floats
 
 
@@ -105,8 +119,8 @@ def _torch_dtype(name):
     return getattr(torch, name)
 
 
-def alloc_records(n: int, device) -> Records:
-    return Records(n, device)
+def alloc_records(n: int, device, with_laplace: bool = False) -> Records:
+    return Records(n, device, with_laplace)
 
 
 def gather_records(buf, n_cap: int, rank: int, world: int, group=None, async_op: bool = False):
@@ -211,12 +225,14 @@ def run_distributed(fn, *args, **kwargs):
     return result
 
 
-def unpack_gathered(parts, n_taxa: int, world: int):
+def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False):
     """Concatenate gathered shards back into df_counts order (host numpy);
-    the parts may be device (RCCL) or host (gloo) buffers."""
+    the parts may be device (RCCL) or host (gloo) buffers.  with_laplace: the
+    parts carry the Laplace block and a fourth array lap[T, 3, 8] f32 is returned."""
     import torch
 
-    outs, preds, sts = [], [], []
+    outs, preds, sts, laps = [], [], [], []
+    rec_bytes = REC_BYTES + (REC_LAP if with_laplace else 0)
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)
@@ -232,14 +248,18 @@ def unpack_gathered(parts, n_taxa: int, world: int):
         parts = [host[o : o + p.numel()] for o, p in zip(off, parts)]
     for r, part in enumerate(parts):
         lo, hi = shard_range(n_taxa, r, world)
-        n_cap = part.numel() // REC_BYTES
-        p, s, ints, floats = packed_views(part, n_cap)
+        n_cap = part.numel() // rec_bytes
+        p, s, ints, floats, *rest = packed_views(part, n_cap, with_laplace=with_laplace)
+        if with_laplace:
+            laps.append(rest[0][: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)
         o[:, INT_LO:INT_HI] = ints[: hi - lo].numpy()
         o[:, FLOAT_COLS] = floats[: hi - lo].numpy()
         outs.append(o)
         preds.append(p[: hi - lo].numpy())
         sts.append(s[: hi - lo].numpy())
+    if with_laplace:
+        return np.concatenate(outs), np.concatenate(preds), np.concatenate(sts), np.concatenate(laps)
     return np.concatenate(outs), np.concatenate(preds), np.concatenate(sts)
 
 

@@ -37,6 +37,7 @@ class FitBatch:
     pred: "object"  # torch.float32 [T, 3, 30]
     status: "object"  # torch.int32 [T]
     workspace: "object" = None  # torch.uint8 [mdfit_workspace_bytes(T, opts)] (work queues; NUTS: the draws)
+    lap: "object" = None  # torch.float32 [T, 3, NLAPLACE]: the Laplace records (ChunkedFitter with_laplace)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -122,6 +123,33 @@ def fit_batch_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, res: F
     return res
 
 
+def map_laplace_device(ty, tN, res: FitBatch, lap=None, gh=None, stream=None, u=None):
+    """Launch mdfit_map_laplace on the records of a finished MAP call
+    (asynchronous on `stream`): the Laplace standard errors of the three PMD
+    sub-fits, float64 lap[T, 3, NLAPLACE] (_lib.LAPLACE_FIELDS).  gh
+    (float64[T, 3, 20], optional) receives g[4] then H[4][4] at the rebuilt
+    mode and u (float64[T, 3, 4], optional; mdfit_map_laplace_u) that mode itself
+    (parity tests).  Returns lap."""
+    torch = _torch()
+    lib = _lib.load()
+    T = int(ty.shape[0])
+    if lap is None:
+        lap = torch.empty((T, 3, _lib.NLAPLACE), dtype=torch.float64, device=ty.device)
+    for name, t, n in (("lap", lap, T * 3 * _lib.NLAPLACE), ("gh", gh, T * 3 * 20), ("u", u, T * 3 * 4)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    args = [ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
+            ctypes.c_void_p(res.status.data_ptr()), T, ctypes.c_void_p(lap.data_ptr()),
+            ctypes.c_void_p(gh.data_ptr()) if gh is not None else None]
+    if u is not None:
+        _lib.check(lib.mdfit_map_laplace_u(*args, ctypes.c_void_p(u.data_ptr()), _stream_handle(torch, stream)))
+    else:
+        _lib.check(lib.mdfit_map_laplace(*args, _stream_handle(torch, stream)))
+    return lap
+
+
 def fit_batch(y, N, mm=None, opts: _lib.MdfitOpts | None = None, device="cuda"):
     """Host arrays in, host arrays out: (out[T,80] f64, pred[T,3,30] f32, status[T] i32)."""
     torch = _torch()
@@ -140,23 +168,30 @@ N_SETS = 2  # device buffer sets in flight: chunk k+1's H2D (and fit) beside chu
 _BUDGET_FRAC = 0.6  # default device budget of a staging: this fraction of the free device memory
 
 
+LAP_BYTES = 3 * _lib.NLAPLACE * 4  # one taxon's Laplace records as they leave the device: f32 [3][8]
+
+
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
-                 dest_on_device: bool = False) -> int:
+                 dest_on_device: bool = False, with_laplace: bool = False) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
     call's workspace (mdfit_workspace_bytes: MAP ~48 B below 60k taxa and
-    ~4.9 KB from 60k, NUTS 6 x num_samples x 32 B, the draws)."""
+    ~4.9 KB from 60k, NUTS 6 x num_samples x 32 B, the draws).  with_laplace:
+    the Laplace records, 192 B as computed (f64) and -- unless they go to the
+    caller's device buffer -- 96 B rounded to f32."""
     C = int(C)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
+    if with_laplace:
+        b += C * (2 * LAP_BYTES + (0 if dest_on_device else LAP_BYTES))
     return b + workspace_bytes(C, opts)
 
 
 def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | None = None, *,
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
-                dest_on_device: bool = False) -> list[tuple[int, int]]:
+                dest_on_device: bool = False, with_laplace: bool = False) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk fit in budget_bytes (None: no memory
     bound), no chunk exceeds the per-call limit (2^25 taxa) or chunk_taxa (> 0;
@@ -172,7 +207,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     if chunk_taxa > 0:
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
-        per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device)  # noqa: E731
+        per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, with_laplace)  # noqa: E731
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
         if per(cap) > budget_bytes:  # largest c with per(c) <= budget (per is monotone in c)
@@ -203,7 +238,8 @@ class _Set:
     """One chunk's device buffers (the workspace is the fitter's: the calls
     run one after another on the compute stream)."""
 
-    def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool):
+    def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
+                 with_laplace: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -213,6 +249,11 @@ class _Set:
             self.pred = (torch.empty((C, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=device)
                          if with_pred else None)
             self.status = torch.empty((C,), dtype=torch.int32, device=device)
+        self.lap64 = self.lap = None
+        if with_laplace:  # as mdfit_map_laplace writes them, and rounded to f32 for the way out
+            self.lap64 = torch.empty((C, 3, _lib.NLAPLACE), dtype=torch.float64, device=device)
+            if not dest_on_device:
+                self.lap = torch.empty((C, 3, _lib.NLAPLACE), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -239,21 +280,29 @@ class ChunkedFitter:
     Outputs go to pinned host buffers (run: the 25 result columns, the
     predictions, the status; grown as needed and reused) or, run_into_device,
     straight into the caller's device tensors (the sharded fit's gather
-    records)."""
+    records).
+
+    with_laplace (MAP only): mdfit_map_laplace follows each chunk's fit on the
+    compute stream, its records are rounded to f32 there and leave with the
+    chunk's other results (96 B per taxon; run returns them as a fourth array,
+    run_into_device writes dest.lap) -- no further stream or hardware queue."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
-                 with_mm: bool = True, dest_on_device: bool = False):
+                 with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False):
         torch = _torch()
+        if with_laplace and opts is not None and int(opts.mode) != _lib.MODE_MAP:
+            raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
+        self.with_laplace = bool(with_laplace)
         self.chunk_cap = int(chunk_cap)
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
-        self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device)
+        self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.with_laplace)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
-        self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = None
+        self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = self.h_lap = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -269,6 +318,8 @@ class ChunkedFitter:
             self.h_pred = (torch.empty((cap, _lib.NPRED, _lib.NPOS), dtype=torch.float32).pin_memory()
                            if self.with_pred else None)
             self.h_status = torch.empty((cap,), dtype=torch.int32).pin_memory()
+            if self.with_laplace:
+                self.h_lap = torch.empty((cap, 3, _lib.NLAPLACE), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -294,6 +345,10 @@ class ChunkedFitter:
         torch = _torch()
         lib = _lib.load()
         o0 = opts if opts is not None else _lib.default_opts()
+        if self.with_laplace and int(o0.mode) != _lib.MODE_MAP:
+            raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
+        if self.with_laplace and dest is not None and dest.lap is None:
+            raise ValueError("with_laplace: dest.lap (float32 [T, 3, NLAPLACE]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -336,6 +391,12 @@ class ChunkedFitter:
                 _lib.check(lib.mdfit_noise(ctypes.c_void_p(st.d_y.data_ptr()), ctypes.c_void_p(st.d_N.data_ptr()),
                                            ctypes.c_void_p(st.d_mm.data_ptr()), n, ctypes.c_void_p(res.out.data_ptr()),
                                            h_s))
+            lap32 = None
+            if self.with_laplace:  # the records are final: their standard errors, rounded to f32 in place
+                map_laplace_device(st.d_y[:n], st.d_N[:n], res, lap=st.lap64[:n], stream=comp)
+                lap32 = dest.lap[lo:hi] if dest is not None else st.lap[:n]
+                with torch.cuda.stream(comp):
+                    lap32.copy_(st.lap64[:n])
             ev_done = torch.cuda.Event()
             ev_done.record(comp)
             done.append(ev_done)
@@ -346,6 +407,8 @@ class ChunkedFitter:
                     if res.pred is not None:
                         self.h_pred[lo:hi].copy_(res.pred, non_blocking=True)
                     self.h_status[lo:hi].copy_(res.status, non_blocking=True)
+                    if lap32 is not None:
+                        self.h_lap[lo:hi].copy_(lap32, non_blocking=True)
                 last_d2h = cp
         end = torch.cuda.Event()
         end.record(cp if last_d2h is not None else comp)
@@ -354,7 +417,8 @@ class ChunkedFitter:
 
     def run(self, y, N, mm=None, opts: _lib.MdfitOpts | None = None, sync: bool = True,
             pinned: PinnedPack | None = None, chunks=None):
-        """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status) of the
+        """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status -- and,
+        with_laplace, lap[:, 3, 8] f32) of the
         pinned buffers (valid until the next run).  pinned: y, N, mm are that
         PinnedPack's views.  chunks: the split (default plan_chunks at this
         staging's chunk_cap)."""
@@ -368,12 +432,14 @@ class ChunkedFitter:
         if sync:
             end.synchronize()
         pred = self.h_pred[:T].numpy() if self.h_pred is not None else None
+        if self.with_laplace:
+            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_lap[:T].numpy()
         return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy()
 
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
-        (out[T, NOUT], pred, status: rows written in place), ordered on the
-        caller's current stream."""
+        (out[T, NOUT], pred, status -- with_laplace also lap, f32 [T, 3, 8]: rows
+        written in place), ordered on the caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
             chunks = plan_chunks(T, opts, chunk_taxa=self.chunk_cap)
@@ -439,7 +505,8 @@ _STAGING_LOCK = __import__("threading").Lock()
 
 
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
-            dest_on_device: bool = False, budget_bytes: int | None = None) -> ChunkedFitter:
+            dest_on_device: bool = False, budget_bytes: int | None = None,
+            with_laplace: bool = False) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind and sampler length): the
     multi-file pipeline fits one file after another, and pinned + device
@@ -455,7 +522,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
         dev = torch.device(dev.type, torch.cuda.current_device())
     o = opts if opts is not None else _lib.default_opts()
     env_chunk = int(os.environ.get("MDFIT_CHUNK_TAXA", "0") or 0)
-    key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk)
+    key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
+           bool(with_laplace))
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -471,9 +539,11 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     # per taxon that batches below 60k never touch)
     if T < _lib.STREAM_MAX_TAXA:
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
-    cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device)[0]
+    cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
+                      with_laplace=with_laplace)[0]
     cap = cap[1] - cap[0]
-    st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device)
+    st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
+                       with_laplace=with_laplace)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -481,20 +551,25 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 
 
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
-                   pinned: PinnedPack | None = None):
-    """The product's host-to-host fit: (out[T, 25], pred, status), chunked
+                   pinned: PinnedPack | None = None, laplace: bool = False):
+    """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
+    laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
+    the PMD sub-fits (_lib.LAPLACE_FIELDS) --, chunked
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
     PinnedPack (copied to the device from there)."""
     T = int(y.shape[0])
     with _STAGING_LOCK:
-        st = staging(T, device=device, opts=opts, with_mm=mm is not None)
-        out, pred, status = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
-        out, pred, status = out.copy(), pred.copy(), status.copy()
+        st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace)
+        got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
+        out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
+        lap = got[3].copy() if laplace else None
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
+    if laplace:
+        return out, pred, status, lap
     return out, pred, status
 
 

@@ -38,6 +38,15 @@ FIT_RESULT_COLUMNS = (
     + _lib.RESULT_FIELDS[7:]
     + ["shortname"]
 )
+# "map-laplace": the Laplace columns appended after shortname --
+# (column, row of the Laplace record: 0 PMD-all, 1 forward, 2 reverse, its field)
+LAPLACE_COLUMNS = (
+    [(name, 0, f) for name, f in (("D_max_std", "D_max_std"), ("significance", "significance"), ("q_std", "q_std"),
+                                   ("A_std", "A_std"), ("c_std", "c_std"), ("concentration_std", "phi_std"),
+                                   ("rho_Ac", "rho_Ac"))]
+    + [("D_max_std_forward", 1, "D_max_std"), ("q_std_forward", 1, "q_std"),
+       ("D_max_std_reverse", 2, "D_max_std"), ("q_std_reverse", 2, "q_std")]
+)
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -225,10 +234,12 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
-def fit_packed(p: Packed, opts=None, shard: bool = True):
+def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
-    taxon on this rank's GPU (main() shards whole files across ranks)."""
+    taxon on this rank's GPU (main() shards whole files across ranks).
+    laplace (MAP): mdfit_map_laplace follows the fit and a fourth array, the
+    Laplace records lap[T, 3, 8] f32, is returned."""
     import torch
 
     from . import engine
@@ -251,16 +262,16 @@ def fit_packed(p: Packed, opts=None, shard: bool = True):
     # share of a multi-file pipeline that is host-bound
     if not grouped:
         try:
-            return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned)
+            return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world)
+        return _fit_sharded(p, opts, dev, rank, world, laplace)
     finally:
         p.release_pinned()
 
 
-def _fit_sharded(p: Packed, opts, dev, rank: int, world: int):
+def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False):
     import torch
 
     from . import engine
@@ -271,14 +282,16 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int):
         opts = _lib.MdfitOpts.from_buffer_copy(opts)
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
-    rec = alloc_records(cap, dev)
+    rec = alloc_records(cap, dev, with_laplace=laplace)
     if hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
         # records written in place into the gather buffers
         with engine._STAGING_LOCK:
-            st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True)
+            st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
+                                with_laplace=laplace)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
-                               engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo]))
+                               engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
+                                               lap=rec.lap[: hi - lo] if laplace else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -286,7 +299,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int):
     parts = gather_records(buf, cap, rank, world)
     if rank != 0:
         return None
-    return unpack_gathered(parts, p.n_taxa, world)
+    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace)
 
 
 # --------------------------------------------------------------------------
@@ -342,10 +355,12 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
     return cols
 
 
-def make_df_fit_results(p: Packed, out, keep, cfg) -> pd.DataFrame:
+def make_df_fit_results(p: Packed, out, keep, cfg, lap=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
-    categorical, integer fields uint32, the rest float32."""
+    categorical, integer fields uint32, the rest float32.  lap (the Laplace
+    records [T, 3, 8] of a "map-laplace" run): the LAPLACE_COLUMNS follow as
+    float32, then laplace_valid (uint32: the valid bit of the PMD-all row)."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -359,7 +374,15 @@ def make_df_fit_results(p: Packed, out, keep, cfg) -> pd.DataFrame:
         data[name] = _uint32(np.rint(v).astype(np.int64)) if name in INT_RESULT_FIELDS else v.astype(np.float32)
     data["N_alignments"] = _uint32(p.N_alignments if keep is None else p.N_alignments[keep])
     data["shortname"] = _const_category(cfg.shortname, n)
-    return pd.DataFrame({c: data[c] for c in FIT_RESULT_COLUMNS}, copy=False)
+    columns = list(FIT_RESULT_COLUMNS)
+    if lap is not None:
+        kl = np.asarray(lap) if keep is None else np.asarray(lap)[keep]
+        for name, row, field in LAPLACE_COLUMNS:
+            data[name] = np.ascontiguousarray(kl[:, row, _lib.LAPLACE_FIELDS.index(field)], dtype=np.float32)
+        flags = kl[:, 0, _lib.LAPLACE_FIELDS.index("flags")].astype(np.int64)
+        data["laplace_valid"] = ((flags & _lib.LAPLACE_VALID) != 0).astype(np.uint32)
+        columns += [name for name, _, _ in LAPLACE_COLUMNS] + ["laplace_valid"]
+    return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
 def make_df_fit_predictions(p: Packed, pred, keep, cfg) -> pd.DataFrame:
@@ -382,32 +405,39 @@ def make_df_fit_predictions(p: Packed, pred, keep, cfg) -> pd.DataFrame:
 def make_opts(cfg, mcmc_kwargs=None):
     """Engine options for cfg.inference: "nuts" (the reference's sampler,
     num_warmup / num_samples from mcmc_kwargs as fits.py:792-799 passes them)
-    or "map"."""
+    "map" or "map-laplace" (the MAP fit; wants_laplace adds the standard errors)."""
     inference = getattr(cfg, "inference", "nuts")
-    if inference == "map":
+    if inference in ("map", "map-laplace"):
         return _lib.default_opts(mode=_lib.MODE_MAP)
     if inference != "nuts":
-        raise ValueError(f"inference must be 'nuts' or 'map', got {inference!r}")
+        raise ValueError(f"inference must be 'nuts', 'map' or 'map-laplace', got {inference!r}")
     kw = mcmc_kwargs or {}
     return _lib.default_opts(mode=_lib.MODE_NUTS, num_warmup=int(kw.get("num_warmup", 500)),
                              num_samples=int(kw.get("num_samples", 1000)))
 
 
+def wants_laplace(cfg) -> bool:
+    """cfg.inference "map-laplace": the MAP fit followed by mdfit_map_laplace."""
+    return getattr(cfg, "inference", "nuts") == "map-laplace"
+
+
 def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     """fits.py:709-730: (df_fit_results, df_fit_predictions) for every taxon of
     df_counts, in df_counts order, by the sampler (cfg.inference "nuts", the
-    reference's NUTS with mcmc_kwargs' warmup / samples) or the MAP fit."""
+    reference's NUTS with mcmc_kwargs' warmup / samples) or the MAP fit
+    ("map-laplace": with the Laplace columns in df_fit_results)."""
     if opts is None:
         opts = make_opts(cfg, mcmc_kwargs)
     p = pack_counts(df_counts, cfg)
-    res = fit_packed(p, opts, shard=shard)
+    res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
-    out, pred, status = res
+    out, pred, status, *rest = res
+    lap = rest[0] if rest else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return make_df_fit_results(p, out, keep, cfg), make_df_fit_predictions(p, pred, keep, cfg)
+    return make_df_fit_results(p, out, keep, cfg, lap=lap), make_df_fit_predictions(p, pred, keep, cfg)
 
 
 def extract_top_max_fits(df_counts, max_fits):
@@ -501,10 +531,12 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     p = packed if packed is not None else pack_counts(get_top_max_fits(df_counts, cfg.N_fits), cfg)
     # fits.py:792-799
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
-    res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard)
+    res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
+                     laplace=wants_laplace(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
-    out, pred, status = res
+    out, pred, status, *rest = res
+    lap = rest[0] if rest else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -512,7 +544,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     def finish():
         from .counts import _save
 
-        df_fit_results = make_df_fit_results(p, out, keep, cfg)
+        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
