@@ -234,6 +234,36 @@ int mdfit_map_laplace(const uint32_t* y, const uint32_t* N, const double* out, c
 int mdfit_map_laplace_u(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
                         int64_t n_taxa, double* lap, double* gh, double* u, void* hip_stream);
 
+/* Sampling diagnostics record: double diag[T][6][MDFIT_NNUTSDIAG], one row per
+ * sub-fit in the order of the diagnostic slots: ess(q, A, c, phi, D_max),
+ * rhat(q, A, c, phi, D_max), mcse(D_max), flags (an integer stored as double:
+ * bit 0 the row is valid). */
+#define MDFIT_NNUTSDIAG 12
+
+/*
+ * Convergence diagnostics of the chains of a finished MODE_NUTS call
+ * (MDFIT-DIAG v1): per sub-fit and per series -- q, A, c, phi
+ * and D_max (A + c of a PMD sub-fit, q of a null one) -- the effective sample
+ * size by Geyer's initial monotone sequence, capped at S log10 S, the split
+ * R-hat of the chain's two halves, and for D_max the Monte Carlo standard
+ * error sqrt(var / ess); what numpyro's print_summary shows as n_eff and r_hat
+ * for the reference's MCMC objects (fits.py:440), in the single-chain case.  A
+ * constant series (a null sub-fit's A and c) gives NaN.  A row is valid when
+ * the chain's status slot (MDFIT_F_DIAG + 8k + 6) is 0 and every draw of the
+ * sub-fit is finite; otherwise its eleven statistics are NaN and flags is 0.
+ *   workspace : the workspace of that call (device; read only): the draws
+ *               double[n_taxa][6][num_samples][4] behind its first 256 bytes,
+ *               intact until the next mdfit_fit_batch on it
+ *   out       : its records (device; read only)
+ *   opts      : the options of that call: mode MDFIT_MODE_NUTS, num_samples in
+ *               [2, 4096] (else MDFIT_E_ARG)
+ *   diag      : double[n_taxa][6][MDFIT_NNUTSDIAG]                (device)
+ * One launch on hip_stream, one wave per sub-fit; no allocation, no side
+ * stream, no host synchronisation.  n_taxa: at most 2^25 per call.
+ */
+int mdfit_nuts_diag(const void* workspace, const double* out, int64_t n_taxa,
+                    const mdfit_opts* opts, double* diag, void* hip_stream);
+
 /*
  * Pointwise beta-binomial log-pmf (numpyro BetaBinomial.log_prob, used by
  * fits.py:59,67 and log_likelihood fits.py:126-133):

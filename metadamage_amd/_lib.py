@@ -29,6 +29,7 @@ NOUT = 80
 NSUBFIT = 6
 DIAG_STRIDE = 8
 NLAPLACE = 8
+NNUTSDIAG = 12
 
 # output record field order (enum mdfit_field) == fit_results numeric columns
 RESULT_FIELDS = [
@@ -63,6 +64,10 @@ DIAG_FIELDS = ["q", "A", "c", "phi", "objective", "evals", "status"]
 # Laplace record (mdfit_map_laplace): float64 [T][3][NLAPLACE], rows PMD-all, PMD-forward, PMD-reverse
 LAPLACE_FIELDS = ["q_std", "A_std", "c_std", "phi_std", "D_max_std", "rho_Ac", "significance", "flags"]
 LAPLACE_VALID = 16  # flags: bits 0..3 coordinate (q, A, c, phi) free, bit 4 valid
+# sampling diagnostics record (mdfit_nuts_diag): float64 [T][6][NNUTSDIAG], rows in SUBFITS order
+NUTSDIAG_FIELDS = ["ess_q", "ess_A", "ess_c", "ess_phi", "ess_D_max", "rhat_q", "rhat_A", "rhat_c", "rhat_phi",
+                   "rhat_D_max", "mcse_D_max", "flags"]
+NUTSDIAG_VALID = 1  # flags: bit 0 valid
 
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
@@ -72,6 +77,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_noise",
     "mdfit_map_laplace",
     "mdfit_map_laplace_u",
+    "mdfit_nuts_diag",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
     "mdfit_hpdi68",
@@ -147,6 +153,8 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_map_laplace.restype = ctypes.c_int
     lib.mdfit_map_laplace_u.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp]
     lib.mdfit_map_laplace_u.restype = ctypes.c_int
+    lib.mdfit_nuts_diag.argtypes = [vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp]
+    lib.mdfit_nuts_diag.restype = ctypes.c_int
     lib.mdfit_betabinom_logpmf.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.mdfit_betabinom_logpmf.restype = ctypes.c_int
     lib.mdfit_special.argtypes = [vp, i64, vp, vp]

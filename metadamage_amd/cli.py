@@ -53,7 +53,8 @@ def cli_fit(
     substitution_bases_reverse: utils.SubstitutionBases = typer.Option(utils.SubstitutionBases.GA),
     forced: bool = typer.Option(False, "--forced"),
     inference: str = typer.Option("nuts", help="nuts: NUTS sampling as the reference; map: MAP fit; "
-                                  "map-laplace: MAP fit with Laplace standard errors and significance"),
+                                  "map-laplace: MAP fit with Laplace standard errors and significance; "
+                                  "nuts-diag: NUTS with per-chain ESS, split R-hat, MCSE and divergences"),
 ):
     """Fitting Ancient Damage.
 
@@ -75,8 +76,8 @@ def cli_fit(
         "version": "0.0.0",
         "inference": inference,
     }
-    if inference not in ("nuts", "map", "map-laplace"):
-        raise typer.BadParameter("--inference must be nuts, map or map-laplace")
+    if inference not in ("nuts", "map", "map-laplace", "nuts-diag"):
+        raise typer.BadParameter("--inference must be nuts, map, map-laplace or nuts-diag")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

@@ -76,4 +76,9 @@ int potential(const int32_t* model, const int32_t* subset, const uint32_t* y, co
 // launches the chain and post-processing kernels (workspace already zeroed)
 int fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts& o,
               double* out, float* pred, int32_t* status, void* workspace, hipStream_t s);
+// MDFIT-DIAG v1 of the chains a finished fit_batch left in `workspace`: one
+// launch, reads the draws and out's chain status slots, writes
+// diag[n_taxa][6][MDFIT_NNUTSDIAG]
+int diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* diag_out,
+         hipStream_t s);
 }  // namespace mdfit::nuts

@@ -32,6 +32,7 @@
 #include "../../include/mdfit.h"
 #include "mdfit_host.h"
 #include "mdfit_model.h"
+#include "mdfit_nutsdiag.h"
 #include "mdfit_special.h"
 
 namespace mdfit::nuts {
@@ -1759,8 +1760,101 @@ __global__ __launch_bounds__(kWave) void nuts_potential_kernel(const int32_t* __
 }
 
 // ---------------------------------------------------------------------------
+// MDFIT-DIAG v1: ESS, split R-hat and MCSE of finished chains
+// ---------------------------------------------------------------------------
+// the 64 lanes of a wave over the sample index: per-lane strided partial sums
+// (mdfit_nutsdiag.h), then this fixed butterfly; lane 0's value is broadcast,
+// so every decision taken from a sum is wave-uniform
+struct DiagWave {
+  __device__ __forceinline__ int lane() const { return (int)threadIdx.x; }
+  __device__ __forceinline__ int nlanes() const { return kWave; }
+  __device__ __forceinline__ double sum(double v) const {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return __shfl(v, 0, kWave);
+  }
+  __device__ __forceinline__ void sum2(double& a, double& b) const {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      a += __shfl_xor(a, o, kWave);
+      b += __shfl_xor(b, o, kWave);
+    }
+    a = __shfl(a, 0, kWave);
+    b = __shfl(b, 0, kWave);
+  }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+
+// One wave per (taxon, sub-fit): the five series one after another, the centred
+// series of the current one in LDS (S x 8 B: 8 KB at the default S = 1000, so
+// LDS admits 20 blocks per CU and binds before the 32-wave cap; 32 KB, 5 blocks,
+// at S = 4096).  Reads samples and out only; lane 0 writes the record.
+__global__ __launch_bounds__(kWave) void nuts_diag_kernel(const double* __restrict__ samples,
+                                                          const double* __restrict__ out, int64_t n_rows, int S,
+                                                          double* __restrict__ diag) {
+  extern __shared__ double s_d[];
+  const int64_t row = blockIdx.x;
+  if (row >= n_rows) return;
+  const int lane = threadIdx.x;
+  const int64_t taxon = row / MDFIT_NSUBFIT;
+  const int sub = (int)(row - taxon * MDFIT_NSUBFIT);
+  const bool pmd = sub == 0 || sub == 2 || sub == 3;
+  const double* x = samples + row * (int64_t)S * 4;
+  double* rec = diag + row * MDFIT_NNUTSDIAG;
+  const double chain_status = out[taxon * MDFIT_NOUT + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * sub + 6];
+  bool ok = chain_status == 0.0;  // (wave-uniform)
+  const DiagWave w;
+  nutsdiag::SeriesStats r{}, rq{};
+  // lane 0 writes each series' fields as they come; a non-finite draw found
+  // later overwrites the row
+  for (int s = 0; s < nutsdiag::kNSeries && ok; ++s) {
+    bool bad = false;
+    if (s == 4 && !pmd) {  // a null sub-fit's D_max is its q
+      r = rq;
+    } else {
+      for (int t = lane; t < S; t += kWave) {
+        const double v = s < 4 ? x[4 * (int64_t)t + s] : x[4 * (int64_t)t + 1] + x[4 * (int64_t)t + 2];
+        bad |= s < 4 && !isfinite(v);  // (the draws; an overflowing A + c gives NaN statistics)
+        s_d[t] = v;
+      }
+      __syncthreads();
+      if (__any(bad)) {
+        ok = false;
+        break;
+      }
+      r = nutsdiag::series_stats(w, s_d, S);
+      __syncthreads();  // (the next series overwrites s_d)
+      if (s == 0) rq = r;
+    }
+    if (lane == 0) {
+      rec[nutsdiag::kEss + s] = r.ess;
+      rec[nutsdiag::kRhat + s] = r.rhat;
+      if (s == 4) {
+        rec[nutsdiag::kMcse] = r.mcse;
+        rec[nutsdiag::kFlags] = nutsdiag::kValid;
+      }
+    }
+  }
+  if (!ok && lane == 0) nutsdiag::invalid_row(rec);
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
+int diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* diag_out,
+         hipStream_t s) {
+  if (o.mode != MDFIT_MODE_NUTS)
+    return host::set_err(MDFIT_E_ARG, "mdfit_nuts_diag needs opts->mode == MDFIT_MODE_NUTS");
+  if (o.num_samples < 2 || o.num_samples > kMaxSamples)  // (the LDS bound)
+    return host::set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
+  const double* samples = (const double*)((const char*)workspace + kSamplesOffset);
+  const int64_t n_rows = n_taxa * MDFIT_NSUBFIT;
+  host::debug_poison(s);
+  hipLaunchKernelGGL(nuts_diag_kernel, dim3((unsigned)n_rows), dim3(kWave), (size_t)o.num_samples * sizeof(double), s,
+                     samples, out, n_rows, (int)o.num_samples, diag_out);
+  return host::check_launch("nuts_diag_kernel");
+}
+
 // Register-only throughput probe of the sampler's point evaluation: the chain
 // kernel's potential_cd (value + gradient of 15 points per 16-lane slot, the
 // transform of the position, the five row sums) in the chain kernel's lane

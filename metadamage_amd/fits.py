@@ -19,6 +19,7 @@ whose fit timed out (fits.py:520-522, 603-606).
 from __future__ import annotations
 
 import logging
+import warnings
 
 import numpy as np
 import pandas as pd
@@ -47,6 +48,18 @@ LAPLACE_COLUMNS = (
     + [("D_max_std_forward", 1, "D_max_std"), ("q_std_forward", 1, "q_std"),
        ("D_max_std_reverse", 2, "D_max_std"), ("q_std_reverse", 2, "q_std")]
 )
+# "nuts-diag": the sampling diagnostics appended after shortname,
+# float32 -- (column, row of the diag record: 0 PMD-all, 1 null-all, its field);
+# n_sigma is a WAIC difference of those two chains
+_NUTS_DIAG_PICKS = (
+    [(f, 0, f) for f in _lib.NUTSDIAG_FIELDS[:11]]
+    + [("ess_q_null", 1, "ess_q"), ("ess_phi_null", 1, "ess_phi"), ("rhat_q_null", 1, "rhat_q"),
+       ("rhat_phi_null", 1, "rhat_phi")]
+)
+# ... then the worst series of all six sub-fits (nanmin / nanmax), then uint32
+# divergences (summed over the six chains) and nuts_diag_valid (all six rows valid)
+NUTS_DIAG_COLUMNS = [name for name, _, _ in _NUTS_DIAG_PICKS] + ["ess_min", "rhat_max"]
+NUTS_DIAG_UINT_COLUMNS = ["divergences", "nuts_diag_valid"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -234,12 +247,14 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
-def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False):
+def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
     laplace (MAP): mdfit_map_laplace follows the fit and a fourth array, the
-    Laplace records lap[T, 3, 8] f32, is returned."""
+    Laplace records lap[T, 3, 8] f32, is returned.  diag (NUTS): mdfit_nuts_diag
+    follows the fit and the fourth array is the sampling diagnostics diag[T, 6,
+    12] f32 (flags: bit 0 valid, above it the chain's divergence count)."""
     import torch
 
     from . import engine
@@ -262,16 +277,16 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False):
     # share of a multi-file pipeline that is host-bound
     if not grouped:
         try:
-            return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace)
+            return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace)
+        return _fit_sharded(p, opts, dev, rank, world, laplace, diag)
     finally:
         p.release_pinned()
 
 
-def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False):
+def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False):
     import torch
 
     from . import engine
@@ -282,16 +297,17 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts = _lib.MdfitOpts.from_buffer_copy(opts)
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
-    rec = alloc_records(cap, dev, with_laplace=laplace)
+    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag)
     if hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
         # records written in place into the gather buffers
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
-                                with_laplace=laplace)
+                                with_laplace=laplace, with_diag=diag)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
-                                               lap=rec.lap[: hi - lo] if laplace else None))
+                                               lap=rec.lap[: hi - lo] if laplace else None,
+                                               diag=rec.diag[: hi - lo] if diag else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -299,7 +315,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     parts = gather_records(buf, cap, rank, world)
     if rank != 0:
         return None
-    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace)
+    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag)
 
 
 # --------------------------------------------------------------------------
@@ -355,12 +371,15 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
     return cols
 
 
-def make_df_fit_results(p: Packed, out, keep, cfg, lap=None) -> pd.DataFrame:
+def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
     records [T, 3, 8] of a "map-laplace" run): the LAPLACE_COLUMNS follow as
-    float32, then laplace_valid (uint32: the valid bit of the PMD-all row)."""
+    float32, then laplace_valid (uint32: the valid bit of the PMD-all row).
+    diag (the sampling diagnostics [T, 6, 12] of a "nuts-diag" run, as
+    fit_packed returns them): the NUTS_DIAG_COLUMNS follow as float32, then the
+    NUTS_DIAG_UINT_COLUMNS."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -382,6 +401,18 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None) -> pd.DataFrame:
         flags = kl[:, 0, _lib.LAPLACE_FIELDS.index("flags")].astype(np.int64)
         data["laplace_valid"] = ((flags & _lib.LAPLACE_VALID) != 0).astype(np.uint32)
         columns += [name for name, _, _ in LAPLACE_COLUMNS] + ["laplace_valid"]
+    if diag is not None:
+        kd = np.asarray(diag) if keep is None else np.asarray(diag)[keep]
+        for name, row, field in _NUTS_DIAG_PICKS:
+            data[name] = np.ascontiguousarray(kd[:, row, _lib.NUTSDIAG_FIELDS.index(field)], dtype=np.float32)
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)  # (a row of NaN: NaN)
+            data["ess_min"] = np.nanmin(kd[:, :, 0:5].reshape(n, -1), axis=1).astype(np.float32)
+            data["rhat_max"] = np.nanmax(kd[:, :, 5:10].reshape(n, -1), axis=1).astype(np.float32)
+        flags = np.nan_to_num(kd[:, :, _lib.NUTSDIAG_FIELDS.index("flags")]).astype(np.int64)
+        data["divergences"] = _uint32((flags >> 1).sum(axis=1))
+        data["nuts_diag_valid"] = ((flags & _lib.NUTSDIAG_VALID) != 0).all(axis=1).astype(np.uint32)
+        columns += NUTS_DIAG_COLUMNS + NUTS_DIAG_UINT_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
@@ -405,15 +436,29 @@ def make_df_fit_predictions(p: Packed, pred, keep, cfg) -> pd.DataFrame:
 def make_opts(cfg, mcmc_kwargs=None):
     """Engine options for cfg.inference: "nuts" (the reference's sampler,
     num_warmup / num_samples from mcmc_kwargs as fits.py:792-799 passes them)
-    "map" or "map-laplace" (the MAP fit; wants_laplace adds the standard errors)."""
+    "nuts-diag" (the same call; wants_diag adds the sampling diagnostics), "map"
+    or "map-laplace" (the MAP fit; wants_laplace adds the standard errors)."""
     inference = getattr(cfg, "inference", "nuts")
-    if inference in ("map", "map-laplace"):
+    if mode_of(inference) == _lib.MODE_MAP:
         return _lib.default_opts(mode=_lib.MODE_MAP)
-    if inference != "nuts":
-        raise ValueError(f"inference must be 'nuts', 'map' or 'map-laplace', got {inference!r}")
     kw = mcmc_kwargs or {}
     return _lib.default_opts(mode=_lib.MODE_NUTS, num_warmup=int(kw.get("num_warmup", 500)),
                              num_samples=int(kw.get("num_samples", 1000)))
+
+
+def mode_of(inference: str) -> int:
+    """The engine mode of an --inference value: "nuts" and "nuts-diag" (the
+    sampler; wants_diag adds mdfit_nuts_diag) or "map" and "map-laplace"."""
+    if inference in ("map", "map-laplace"):
+        return _lib.MODE_MAP
+    if inference in ("nuts", "nuts-diag"):
+        return _lib.MODE_NUTS
+    raise ValueError(f"inference must be 'nuts', 'map', 'map-laplace' or 'nuts-diag', got {inference!r}")
+
+
+def wants_diag(cfg) -> bool:
+    """cfg.inference "nuts-diag": the sampler followed by mdfit_nuts_diag."""
+    return getattr(cfg, "inference", "nuts") == "nuts-diag"
 
 
 def wants_laplace(cfg) -> bool:
@@ -429,15 +474,16 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     if opts is None:
         opts = make_opts(cfg, mcmc_kwargs)
     p = pack_counts(df_counts, cfg)
-    res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg))
+    res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
-    lap = rest[0] if rest else None
+    lap = rest[0] if rest and wants_laplace(cfg) else None
+    diag = rest[0] if rest and wants_diag(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return make_df_fit_results(p, out, keep, cfg, lap=lap), make_df_fit_predictions(p, pred, keep, cfg)
+    return make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag), make_df_fit_predictions(p, pred, keep, cfg)
 
 
 def extract_top_max_fits(df_counts, max_fits):
@@ -532,11 +578,12 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     # fits.py:792-799
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
-                     laplace=wants_laplace(cfg))
+                     laplace=wants_laplace(cfg), diag=wants_diag(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
-    lap = rest[0] if rest else None
+    lap = rest[0] if rest and wants_laplace(cfg) else None
+    diag = rest[0] if rest and wants_diag(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -544,7 +591,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     def finish():
         from .counts import _save
 
-        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap)
+        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
