@@ -264,6 +264,42 @@ int mdfit_map_laplace_u(const uint32_t* y, const uint32_t* N, const double* out,
 int mdfit_nuts_diag(const void* workspace, const double* out, int64_t n_taxa,
                     const mdfit_opts* opts, double* diag, void* hip_stream);
 
+/* Posterior summary record: double summ[T][6][MDFIT_NNUTSSUMM], one row per
+ * sub-fit in the order of the diagnostic slots: std(q, A, c, phi, D_max) with
+ * ddof 1, D_max_mean, D_max (median, lo, hi), q (median, lo, hi), phi_median,
+ * rho_Ac, significance, flags (an integer stored as double: bit 0 the row is
+ * valid). */
+#define MDFIT_NNUTSSUMM 16
+
+/*
+ * Posterior summary of the chains of a finished MODE_NUTS call (MDFIT-SUMM v1,
+ * DESIGN.md §9.2): per sub-fit the standard deviations (ddof 1) of q, A, c,
+ * phi and D_max (A + c of a PMD sub-fit, q of a null one), the mean of D_max,
+ * the median (np.median) and the 68 % highest-posterior-density interval
+ * (numpyro's hpdi: the narrowest window of int(0.68 S) + 1 sorted draws, the
+ * lowest index among equal widths) of D_max, q and phi's median, the Pearson
+ * correlation of A and c, and significance = D_max_mean / D_max_std; what the
+ * reference's user computes from the MCMC objects kept at fits.py:440.  A
+ * constant series has std 0; rho_Ac is NaN when A or c is constant (a null
+ * sub-fit), significance when D_max_std is 0.  The order statistics are draws
+ * or one subtraction of two: exact.  A row is valid when the chain's status
+ * slot (MDFIT_F_DIAG + 8k + 6) is 0 and every draw of the sub-fit is finite;
+ * otherwise its fifteen statistics are NaN and flags is 0.
+ *   workspace : the workspace of that call (device; read only): the draws
+ *               double[n_taxa][6][num_samples][4] behind its first 256 bytes,
+ *               intact until the next mdfit_fit_batch on it
+ *   out       : its records (device; read only)
+ *   opts      : the options of that call: mode MDFIT_MODE_NUTS, num_samples in
+ *               [2, 4096] (else MDFIT_E_ARG)
+ *   summ      : double[n_taxa][6][MDFIT_NNUTSSUMM]                (device)
+ * One launch on hip_stream, one wave per sub-fit; no allocation, no side
+ * stream, no host synchronisation.  n_taxa: at most 2^25 per call.
+ * Independent of mdfit_nuts_diag: both may run on one finished call's
+ * workspace, in either order.
+ */
+int mdfit_nuts_summary(const void* workspace, const double* out, int64_t n_taxa,
+                       const mdfit_opts* opts, double* summ, void* hip_stream);
+
 /*
  * Pointwise beta-binomial log-pmf (numpyro BetaBinomial.log_prob, used by
  * fits.py:59,67 and log_likelihood fits.py:126-133):

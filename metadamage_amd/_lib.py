@@ -30,6 +30,7 @@ NSUBFIT = 6
 DIAG_STRIDE = 8
 NLAPLACE = 8
 NNUTSDIAG = 12
+NNUTSSUMM = 16
 
 # output record field order (enum mdfit_field) == fit_results numeric columns
 RESULT_FIELDS = [
@@ -68,6 +69,10 @@ LAPLACE_VALID = 16  # flags: bits 0..3 coordinate (q, A, c, phi) free, bit 4 val
 NUTSDIAG_FIELDS = ["ess_q", "ess_A", "ess_c", "ess_phi", "ess_D_max", "rhat_q", "rhat_A", "rhat_c", "rhat_phi",
                    "rhat_D_max", "mcse_D_max", "flags"]
 NUTSDIAG_VALID = 1  # flags: bit 0 valid
+# posterior summary record (mdfit_nuts_summary): float64 [T][6][NNUTSSUMM], rows in SUBFITS order
+NUTSSUMM_FIELDS = ["q_std", "A_std", "c_std", "phi_std", "D_max_std", "D_max_mean", "D_max_median", "D_max_lo",
+                   "D_max_hi", "q_median", "q_lo", "q_hi", "phi_median", "rho_Ac", "significance", "flags"]
+NUTSSUMM_VALID = 1  # flags: bit 0 valid
 
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
@@ -78,6 +83,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_laplace",
     "mdfit_map_laplace_u",
     "mdfit_nuts_diag",
+    "mdfit_nuts_summary",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
     "mdfit_hpdi68",
@@ -155,6 +161,8 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_map_laplace_u.restype = ctypes.c_int
     lib.mdfit_nuts_diag.argtypes = [vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp]
     lib.mdfit_nuts_diag.restype = ctypes.c_int
+    lib.mdfit_nuts_summary.argtypes = [vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp]
+    lib.mdfit_nuts_summary.restype = ctypes.c_int
     lib.mdfit_betabinom_logpmf.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.mdfit_betabinom_logpmf.restype = ctypes.c_int
     lib.mdfit_special.argtypes = [vp, i64, vp, vp]

@@ -54,7 +54,8 @@ def cli_fit(
     forced: bool = typer.Option(False, "--forced"),
     inference: str = typer.Option("nuts", help="nuts: NUTS sampling as the reference; map: MAP fit; "
                                   "map-laplace: MAP fit with Laplace standard errors and significance; "
-                                  "nuts-diag: NUTS with per-chain ESS, split R-hat, MCSE and divergences"),
+                                  "nuts-diag: NUTS with per-chain ESS, split R-hat, MCSE and divergences; "
+                                  "nuts-summary: NUTS with posterior std, median, 68 % HPDI and significance"),
 ):
     """Fitting Ancient Damage.
 
@@ -76,8 +77,8 @@ def cli_fit(
         "version": "0.0.0",
         "inference": inference,
     }
-    if inference not in ("nuts", "map", "map-laplace", "nuts-diag"):
-        raise typer.BadParameter("--inference must be nuts, map, map-laplace or nuts-diag")
+    if inference not in ("nuts", "map", "map-laplace", "nuts-diag", "nuts-summary"):
+        raise typer.BadParameter("--inference must be nuts, map, map-laplace, nuts-diag or nuts-summary")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

@@ -81,4 +81,8 @@ int fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t 
 // diag[n_taxa][6][MDFIT_NNUTSDIAG]
 int diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* diag_out,
          hipStream_t s);
+// MDFIT-SUMM v1 of the same chains: one launch, reads the draws and out's chain
+// status slots, writes summ[n_taxa][6][MDFIT_NNUTSSUMM]
+int summary(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* summ_out,
+            hipStream_t s);
 }  // namespace mdfit::nuts

@@ -33,6 +33,7 @@
 #include "mdfit_host.h"
 #include "mdfit_model.h"
 #include "mdfit_nutsdiag.h"
+#include "mdfit_nutssumm.h"
 #include "mdfit_special.h"
 
 namespace mdfit::nuts {
@@ -165,6 +166,12 @@ __device__ __noinline__ double2 normal_pair(const Stream& s, uint32_t w2, uint32
 // registers (reg_sort_u32); else the LDS bitonic sort
 #ifndef MDFIT_REG_SORT
 #define MDFIT_REG_SORT 1
+#endif
+// (MDFIT_SUMM_REG_SORT) the summary kernel's series of 513..1024 draws sorted
+// in registers (reg_sort_f64); else the LDS bitonic sort
+// (profiles/nuts_summary_cost.txt)
+#ifndef MDFIT_SUMM_REG_SORT
+#define MDFIT_SUMM_REG_SORT 1
 #endif
 #ifndef MDFIT_NUTS_SST
 #define MDFIT_NUTS_SST 1
@@ -1839,6 +1846,147 @@ __global__ __launch_bounds__(kWave) void nuts_diag_kernel(const double* __restri
 }
 
 // ---------------------------------------------------------------------------
+// MDFIT-SUMM v1: posterior std, median and 68 % HPDI of finished chains
+// ---------------------------------------------------------------------------
+// reg_sort_u32's layout for doubles -- lane L holds elements R L .. R L + R - 1
+// of n <= 64 R finite values in registers, the padding +inf -- over the bitonic
+// network in its ascending-only form: the first step of a merge of width K
+// pairs element e with its mirror e ^ (K - 1), the later steps with e ^ s, and
+// every pair leaves its smaller value at the lower index.  So an exchange
+// inside a lane is one min and one max, and across lanes the partner is lane ^
+// M with M a constant: 1, 2, 3, 7, 8 and 15 are DPP moves inside a row of 16
+// lanes, the others a shuffle through the LDS crossbar (4, 16, 31, 63: 6 of
+// the 21 cross-lane steps at R = 16).  A sort's result is unique up to the
+// order of equal values.
+template <int M>
+__device__ __forceinline__ double lane_xor_f64(double v) {
+  if constexpr (M == 1 || M == 2 || M == 3 || M == 7 || M == 8 || M == 15) {
+    // quad_perm [1,0,3,2], [2,3,0,1], [3,2,1,0]; row_half_mirror; row_ror:8; row_mirror
+    constexpr int ctrl = M == 1 ? 0xB1 : M == 2 ? 0x4E : M == 3 ? 0x1B : M == 7 ? 0x141 : M == 8 ? 0x128 : 0x140;
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+  } else {
+    return __shfl_xor(v, M, kWave);
+  }
+}
+// the lane's side of an exchange with value p: the lower index keeps the smaller
+__device__ __forceinline__ double keep_f64(double v, double p, bool lower) {
+  const double lo = fmin(v, p), hi = fmax(v, p);
+  return lower ? lo : hi;
+}
+template <int R, int S>
+__device__ __forceinline__ void sort_plain_steps(double (&v)[R], int lane) {
+  if constexpr (S >= R) {
+    constexpr int M = S / R;
+    const bool lower = (lane & M) == 0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) v[j] = keep_f64(v[j], lane_xor_f64<M>(v[j]), lower);
+  } else if constexpr (S >= 1) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      if (j & S) continue;
+      const double a = v[j], b = v[j | S];
+      v[j] = fmin(a, b);
+      v[j | S] = fmax(a, b);
+    }
+  }
+  if constexpr (S > 1) sort_plain_steps<R, S / 2>(v, lane);
+}
+template <int R, int K>
+__device__ __forceinline__ void sort_merges(double (&v)[R], int lane) {
+  if constexpr (K <= R) {  // the mirror inside the lane
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int jj = j ^ (K - 1);
+      if (jj < j) continue;
+      const double a = v[j], b = v[jj];
+      v[j] = fmin(a, b);
+      v[jj] = fmax(a, b);
+    }
+  } else {  // element R L + j against element R (L ^ M) + R - 1 - j
+    constexpr int M = K / R - 1;
+    const bool lower = (lane & ((M + 1) >> 1)) == 0;
+#pragma unroll
+    for (int j = 0; j < R / 2; ++j) {
+      const double pa = lane_xor_f64<M>(v[R - 1 - j]), pb = lane_xor_f64<M>(v[j]);
+      v[j] = keep_f64(v[j], pa, lower);
+      v[R - 1 - j] = keep_f64(v[R - 1 - j], pb, lower);
+    }
+  }
+  if constexpr (K >= 4) sort_plain_steps<R, K / 4>(v, lane);
+  if constexpr (K < kWave * R) sort_merges<R, 2 * K>(v, lane);
+}
+// The caller's writes of v_lds are behind a barrier.
+template <int R>
+__device__ void reg_sort_f64(double* v_lds, int n) {
+  const int lane = threadIdx.x;
+  double v[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const int e = lane * R + j;
+    v[j] = e < n ? v_lds[e] : INFINITY;
+  }
+  sort_merges<R, 2>(v, lane);
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const int e = lane * R + j;
+    if (e < n) v_lds[e] = v[j];
+  }
+  __syncthreads();
+}
+
+// DiagWave's sums, and the narrowest window across lanes: the same butterfly
+// over (width, index) by "smaller width, else smaller index", so the lowest
+// index among equal widths wins whichever lane holds it
+struct SummWave : DiagWave {
+  __device__ __forceinline__ void sort(double* v, int S) const {
+#if MDFIT_SUMM_REG_SORT
+    if (S > kWave * 8 && S <= kWave * 16) {
+      __syncthreads();  // (the series is written)
+      reg_sort_f64<16>(v, S);
+      return;
+    }
+#endif
+    nutssumm::sort_series(*this, v, S);
+  }
+  __device__ __forceinline__ void argmin(double& wd, int& i) const {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const double wo = __shfl_xor(wd, o, kWave);
+      const int io = __shfl_xor(i, o, kWave);
+      if (nutssumm::window_before(wo, io, wd, i)) {
+        wd = wo;
+        i = io;
+      }
+    }
+    wd = __shfl(wd, 0, kWave);  // lane 0's, as the sums: every lane reads the same window
+    i = __shfl(i, 0, kWave);
+  }
+};
+
+// One wave per (taxon, sub-fit): one pass over the row's whole draws (32 B per
+// lane and step) for every moment, then D_max, q and phi sorted one after
+// another through the one LDS buffer (S rounded up to a power of two doubles: 8
+// KB at the default S = 1000, 32 KB at S = 4096), in registers at 513..1024
+// draws and in the buffer otherwise.  The sorts bind, not the pass
+// (profiles/nuts_summary_cost.txt).  Reads samples and out only; lane 0 writes
+// the record.
+__global__ __launch_bounds__(kWave) void nuts_summary_kernel(const double* __restrict__ samples,
+                                                             const double* __restrict__ out, int64_t n_rows, int S,
+                                                             double* __restrict__ summ) {
+  extern __shared__ double s_v[];
+  const int64_t row = blockIdx.x;
+  if (row >= n_rows) return;
+  const int64_t taxon = row / MDFIT_NSUBFIT;
+  const int sub = (int)(row - taxon * MDFIT_NSUBFIT);
+  const bool pmd = sub == 0 || sub == 2 || sub == 3;
+  const double chain_status = out[taxon * MDFIT_NOUT + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * sub + 6];
+  nutssumm::summary_row(SummWave{}, samples + row * (int64_t)S * 4, S, pmd, chain_status, s_v,
+                        summ + row * MDFIT_NNUTSSUMM);
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 int diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* diag_out,
@@ -1853,6 +2001,21 @@ int diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_o
   hipLaunchKernelGGL(nuts_diag_kernel, dim3((unsigned)n_rows), dim3(kWave), (size_t)o.num_samples * sizeof(double), s,
                      samples, out, n_rows, (int)o.num_samples, diag_out);
   return host::check_launch("nuts_diag_kernel");
+}
+
+int summary(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* summ_out,
+            hipStream_t s) {
+  if (o.mode != MDFIT_MODE_NUTS)
+    return host::set_err(MDFIT_E_ARG, "mdfit_nuts_summary needs opts->mode == MDFIT_MODE_NUTS");
+  if (o.num_samples < 2 || o.num_samples > kMaxSamples)  // (the LDS bound)
+    return host::set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
+  const double* samples = (const double*)((const char*)workspace + kSamplesOffset);
+  const int64_t n_rows = n_taxa * MDFIT_NSUBFIT;
+  host::debug_poison(s);
+  hipLaunchKernelGGL(nuts_summary_kernel, dim3((unsigned)n_rows), dim3(kWave),
+                     (size_t)nutssumm::sort_len((int)o.num_samples) * sizeof(double), s, samples, out, n_rows,
+                     (int)o.num_samples, summ_out);
+  return host::check_launch("nuts_summary_kernel");
 }
 
 // Register-only throughput probe of the sampler's point evaluation: the chain

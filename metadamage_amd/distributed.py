@@ -41,12 +41,17 @@ REC_LAP = 3 * _lib.NLAPLACE * 4
 # with_diag (a "nuts-diag" run; never together with with_laplace): the same for
 # the sampling diagnostics, one more f32 block [n, 6, NNUTSDIAG], 288 B per taxon
 REC_DIAG = _lib.NSUBFIT * _lib.NNUTSDIAG * 4
+# with_summary (a "nuts-summary" run; never together with either): the same for
+# the posterior summaries, one more f32 block [n, 6, NNUTSSUMM], 384 B per taxon
+REC_SUMM = _lib.NSUBFIT * _lib.NNUTSSUMM * 4
 
 
-def _extra(with_laplace: bool, with_diag: bool) -> int:
+def _extra(with_laplace: bool, with_diag: bool, with_summary: bool = False) -> int:
     if with_laplace and with_diag:
         raise ValueError("with_laplace (MAP) and with_diag (NUTS) are mutually exclusive")
-    return REC_LAP if with_laplace else (REC_DIAG if with_diag else 0)
+    if with_summary and (with_laplace or with_diag):
+        raise ValueError("with_summary, with_diag and with_laplace are mutually exclusive: one extra block per run")
+    return REC_LAP if with_laplace else (REC_DIAG if with_diag else (REC_SUMM if with_summary else 0))
 
 
 def shard_range(n_taxa: int, rank: int, world: int) -> tuple[int, int]:
@@ -74,19 +79,24 @@ class Records:
     copies, the second rounding to f32) before the gather.  with_laplace: the
     buffer is n * REC_LAP bytes longer, `lap` f32[n, 3, 8] after the status,
     written in place by the chunked dispatch.  with_diag: likewise n * REC_DIAG
-    bytes, `diag` f32[n, 6, 12]."""
+    bytes, `diag` f32[n, 6, 12]; with_summary: n * REC_SUMM bytes, `summ` f32[n,
+    6, 16].  At most one of the three."""
 
-    def __init__(self, n: int, device, with_laplace: bool = False, with_diag: bool = False):
+    def __init__(self, n: int, device, with_laplace: bool = False, with_diag: bool = False,
+                 with_summary: bool = False):
         import torch
 
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
-        self.buf = torch.empty(n * (REC_BYTES + _extra(with_laplace, with_diag)), dtype=torch.uint8, device=device)
-        self.lap = self.diag = None
+        self.buf = torch.empty(n * (REC_BYTES + _extra(with_laplace, with_diag, with_summary)), dtype=torch.uint8,
+                               device=device)
+        self.lap = self.diag = self.summ = None
         if with_laplace:
             self.pred, self.status, self.ints, self.floats, self.lap = packed_views(self.buf, n, with_laplace=True)
         elif with_diag:
             self.pred, self.status, self.ints, self.floats, self.diag = packed_views(self.buf, n, with_diag=True)
+        elif with_summary:
+            self.pred, self.status, self.ints, self.floats, self.summ = packed_views(self.buf, n, with_summary=True)
         else:
             self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
         self._fidx = torch.as_tensor(FLOAT_COLS, device=device)
@@ -97,14 +107,15 @@ class Records:
         return self.buf
 
 
-def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = False):
+def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False):
     """Views (pred[n, 3, 30] f32, status[n] i32, ints[n, 8] f64, floats[n, 17]
     f32) into one uint8 gather buffer of n * REC_BYTES bytes laid out ints |
     floats | pred | status (torch tensor; the f64 block first keeps it 8-byte
     aligned for any n).  with_laplace: the buffer holds n * REC_LAP more bytes
     and a fifth view, lap[n, 3, 8] f32, follows the status; with_diag: n *
-    REC_DIAG more bytes and the fifth view is diag[n, 6, 12] f32."""
-    _extra(with_laplace, with_diag)
+    REC_DIAG more bytes and the fifth view is diag[n, 6, 12] f32; with_summary: n
+    * REC_SUMM more bytes and the fifth view is summ[n, 6, 16] f32."""
+    _extra(with_laplace, with_diag, with_summary)
     o1 = n * REC_INT
     o2 = o1 + n * REC_F32
     o3 = o2 + n * REC_PRED
@@ -120,6 +131,10 @@ def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = Fals
         o4 = o3 + 4 * n
         diag = buf[o4 : o4 + n * REC_DIAG].view(dtype=_torch_dtype("float32")).view(n, _lib.NSUBFIT, _lib.NNUTSDIAG)
         return pred, status, ints, floats, diag
+    if with_summary:
+        o4 = o3 + 4 * n
+        summ = buf[o4 : o4 + n * REC_SUMM].view(dtype=_torch_dtype("float32")).view(n, _lib.NSUBFIT, _lib.NNUTSSUMM)
+        return pred, status, ints, floats, summ
     return pred, status, ints, floats
 
 
@@ -137,8 +152,9 @@ def _torch_dtype(name):
     return getattr(torch, name)
 
 
-def alloc_records(n: int, device, with_laplace: bool = False, with_diag: bool = False) -> Records:
-    return Records(n, device, with_laplace, with_diag)
+def alloc_records(n: int, device, with_laplace: bool = False, with_diag: bool = False,
+                  with_summary: bool = False) -> Records:
+    return Records(n, device, with_laplace, with_diag, with_summary)
 
 
 def gather_records(buf, n_cap: int, rank: int, world: int, group=None, async_op: bool = False):
@@ -243,15 +259,18 @@ def run_distributed(fn, *args, **kwargs):
     return result
 
 
-def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, with_diag: bool = False):
+def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, with_diag: bool = False,
+                    with_summary: bool = False):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  with_laplace: the
     parts carry the Laplace block and a fourth array lap[T, 3, 8] f32 is returned;
-    with_diag: the diagnostics block, returned as diag[T, 6, 12] f32."""
+    with_diag: the diagnostics block, returned as diag[T, 6, 12] f32;
+    with_summary: the summaries block, returned as summ[T, 6, 16] f32."""
     import torch
 
     outs, preds, sts, laps = [], [], [], []
-    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag)
+    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag, with_summary)
+    extra = with_laplace or with_diag or with_summary
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)
@@ -268,8 +287,9 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
     for r, part in enumerate(parts):
         lo, hi = shard_range(n_taxa, r, world)
         n_cap = part.numel() // rec_bytes
-        p, s, ints, floats, *rest = packed_views(part, n_cap, with_laplace=with_laplace, with_diag=with_diag)
-        if with_laplace or with_diag:
+        p, s, ints, floats, *rest = packed_views(part, n_cap, with_laplace=with_laplace, with_diag=with_diag,
+                                                 with_summary=with_summary)
+        if extra:
             laps.append(rest[0][: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)
         o[:, INT_LO:INT_HI] = ints[: hi - lo].numpy()
@@ -277,7 +297,7 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
         outs.append(o)
         preds.append(p[: hi - lo].numpy())
         sts.append(s[: hi - lo].numpy())
-    if with_laplace or with_diag:
+    if extra:
         return np.concatenate(outs), np.concatenate(preds), np.concatenate(sts), np.concatenate(laps)
     return np.concatenate(outs), np.concatenate(preds), np.concatenate(sts)
 

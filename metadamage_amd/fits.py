@@ -60,6 +60,24 @@ _NUTS_DIAG_PICKS = (
 # divergences (summed over the six chains) and nuts_diag_valid (all six rows valid)
 NUTS_DIAG_COLUMNS = [name for name, _, _ in _NUTS_DIAG_PICKS] + ["ess_min", "rhat_max"]
 NUTS_DIAG_UINT_COLUMNS = ["divergences", "nuts_diag_valid"]
+# "nuts-summary": the posterior summaries appended after shortname (DESIGN.md
+# §9.2), float32 -- (column, row of the summary record: 0 PMD-all, 2
+# PMD-forward, 3 PMD-reverse, its field).  The first eleven are the
+# LAPLACE_COLUMNS' names in their order: downstream code reads one set of names,
+# and the metadata's `inference` says which estimate they hold
+_NUTS_SUMMARY_PICKS = (
+    [("D_max_std", 0, "D_max_std"), ("significance", 0, "significance"), ("q_std", 0, "q_std"),
+     ("A_std", 0, "A_std"), ("c_std", 0, "c_std"), ("concentration_std", 0, "phi_std"), ("rho_Ac", 0, "rho_Ac"),
+     ("D_max_std_forward", 2, "D_max_std"), ("q_std_forward", 2, "q_std"),
+     ("D_max_std_reverse", 3, "D_max_std"), ("q_std_reverse", 3, "q_std"),
+     ("D_max_posterior_median", 0, "D_max_median"), ("D_max_posterior_lower_hpdi", 0, "D_max_lo"),
+     ("D_max_posterior_upper_hpdi", 0, "D_max_hi"), ("q_median", 0, "q_median"), ("q_lower_hpdi", 0, "q_lo"),
+     ("q_upper_hpdi", 0, "q_hi"), ("concentration_median", 0, "phi_median")]
+)
+NUTS_SUMMARY_COLUMNS = [name for name, _, _ in _NUTS_SUMMARY_PICKS]
+# ... then uint32 nuts_summary_valid: the rows 0, 2 and 3 all valid
+NUTS_SUMMARY_UINT_COLUMNS = ["nuts_summary_valid"]
+_NUTS_SUMMARY_ROWS = (0, 2, 3)
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -247,14 +265,17 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
-def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False):
+def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
+               summary: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
     laplace (MAP): mdfit_map_laplace follows the fit and a fourth array, the
     Laplace records lap[T, 3, 8] f32, is returned.  diag (NUTS): mdfit_nuts_diag
     follows the fit and the fourth array is the sampling diagnostics diag[T, 6,
-    12] f32 (flags: bit 0 valid, above it the chain's divergence count)."""
+    12] f32 (flags: bit 0 valid, above it the chain's divergence count).  summary
+    (NUTS): mdfit_nuts_summary follows the fit and the fourth array is the
+    posterior summaries summ[T, 6, 16] f32.  At most one of the three."""
     import torch
 
     from . import engine
@@ -277,16 +298,18 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     # share of a multi-file pipeline that is host-bound
     if not grouped:
         try:
-            return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag)
+            return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
+                                         summary=summary)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace, diag)
+        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary)
     finally:
         p.release_pinned()
 
 
-def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False):
+def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
+                 summary: bool = False):
     import torch
 
     from . import engine
@@ -297,17 +320,18 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts = _lib.MdfitOpts.from_buffer_copy(opts)
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
-    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag)
+    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary)
     if hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
         # records written in place into the gather buffers
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
-                                with_laplace=laplace, with_diag=diag)
+                                with_laplace=laplace, with_diag=diag, with_summary=summary)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                                                lap=rec.lap[: hi - lo] if laplace else None,
-                                               diag=rec.diag[: hi - lo] if diag else None))
+                                               diag=rec.diag[: hi - lo] if diag else None,
+                                               summ=rec.summ[: hi - lo] if summary else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -315,7 +339,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     parts = gather_records(buf, cap, rank, world)
     if rank != 0:
         return None
-    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag)
+    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary)
 
 
 # --------------------------------------------------------------------------
@@ -371,7 +395,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
     return cols
 
 
-def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None) -> pd.DataFrame:
+def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -379,7 +403,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None) -> pd.Da
     float32, then laplace_valid (uint32: the valid bit of the PMD-all row).
     diag (the sampling diagnostics [T, 6, 12] of a "nuts-diag" run, as
     fit_packed returns them): the NUTS_DIAG_COLUMNS follow as float32, then the
-    NUTS_DIAG_UINT_COLUMNS."""
+    NUTS_DIAG_UINT_COLUMNS.  summ (the posterior summaries [T, 6, 16] of a
+    "nuts-summary" run): the NUTS_SUMMARY_COLUMNS follow as float32, then
+    nuts_summary_valid (uint32: the PMD rows 0, 2 and 3 all valid)."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -413,6 +439,13 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None) -> pd.Da
         data["divergences"] = _uint32((flags >> 1).sum(axis=1))
         data["nuts_diag_valid"] = ((flags & _lib.NUTSDIAG_VALID) != 0).all(axis=1).astype(np.uint32)
         columns += NUTS_DIAG_COLUMNS + NUTS_DIAG_UINT_COLUMNS
+    if summ is not None:
+        ks = np.asarray(summ) if keep is None else np.asarray(summ)[keep]
+        for name, row, field in _NUTS_SUMMARY_PICKS:
+            data[name] = np.ascontiguousarray(ks[:, row, _lib.NUTSSUMM_FIELDS.index(field)], dtype=np.float32)
+        flags = np.nan_to_num(ks[:, _NUTS_SUMMARY_ROWS, _lib.NUTSSUMM_FIELDS.index("flags")]).astype(np.int64)
+        data["nuts_summary_valid"] = ((flags & _lib.NUTSSUMM_VALID) != 0).all(axis=1).astype(np.uint32)
+        columns += NUTS_SUMMARY_COLUMNS + NUTS_SUMMARY_UINT_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
@@ -436,7 +469,8 @@ def make_df_fit_predictions(p: Packed, pred, keep, cfg) -> pd.DataFrame:
 def make_opts(cfg, mcmc_kwargs=None):
     """Engine options for cfg.inference: "nuts" (the reference's sampler,
     num_warmup / num_samples from mcmc_kwargs as fits.py:792-799 passes them)
-    "nuts-diag" (the same call; wants_diag adds the sampling diagnostics), "map"
+    "nuts-diag" (the same call; wants_diag adds the sampling diagnostics),
+    "nuts-summary" (the same call; wants_summary adds the posterior summaries), "map"
     or "map-laplace" (the MAP fit; wants_laplace adds the standard errors)."""
     inference = getattr(cfg, "inference", "nuts")
     if mode_of(inference) == _lib.MODE_MAP:
@@ -447,18 +481,25 @@ def make_opts(cfg, mcmc_kwargs=None):
 
 
 def mode_of(inference: str) -> int:
-    """The engine mode of an --inference value: "nuts" and "nuts-diag" (the
-    sampler; wants_diag adds mdfit_nuts_diag) or "map" and "map-laplace"."""
+    """The engine mode of an --inference value: "nuts", "nuts-diag" and
+    "nuts-summary" (the sampler; wants_diag adds mdfit_nuts_diag, wants_summary
+    mdfit_nuts_summary) or "map" and "map-laplace"."""
     if inference in ("map", "map-laplace"):
         return _lib.MODE_MAP
-    if inference in ("nuts", "nuts-diag"):
+    if inference in ("nuts", "nuts-diag", "nuts-summary"):
         return _lib.MODE_NUTS
-    raise ValueError(f"inference must be 'nuts', 'map', 'map-laplace' or 'nuts-diag', got {inference!r}")
+    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'nuts-diag' or 'nuts-summary', "
+                     f"got {inference!r}")
 
 
 def wants_diag(cfg) -> bool:
     """cfg.inference "nuts-diag": the sampler followed by mdfit_nuts_diag."""
     return getattr(cfg, "inference", "nuts") == "nuts-diag"
+
+
+def wants_summary(cfg) -> bool:
+    """cfg.inference "nuts-summary": the sampler followed by mdfit_nuts_summary."""
+    return getattr(cfg, "inference", "nuts") == "nuts-summary"
 
 
 def wants_laplace(cfg) -> bool:
@@ -474,16 +515,19 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     if opts is None:
         opts = make_opts(cfg, mcmc_kwargs)
     p = pack_counts(df_counts, cfg)
-    res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg))
+    res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
+                     summary=wants_summary(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
+    summ = rest[0] if rest and wants_summary(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag), make_df_fit_predictions(p, pred, keep, cfg)
+    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ),
+            make_df_fit_predictions(p, pred, keep, cfg))
 
 
 def extract_top_max_fits(df_counts, max_fits):
@@ -578,12 +622,13 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     # fits.py:792-799
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
-                     laplace=wants_laplace(cfg), diag=wants_diag(cfg))
+                     laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
+    summ = rest[0] if rest and wants_summary(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -591,7 +636,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     def finish():
         from .counts import _save
 
-        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag)
+        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
