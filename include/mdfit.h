@@ -300,6 +300,55 @@ int mdfit_nuts_diag(const void* workspace, const double* out, int64_t n_taxa,
 int mdfit_nuts_summary(const void* workspace, const double* out, int64_t n_taxa,
                        const mdfit_opts* opts, double* summ, void* hip_stream);
 
+/* PSIS-LOO record: double loo[T][7][MDFIT_NNUTSLOO].  Rows 0..5, one per
+ * sub-fit in the order of the diagnostic slots: elpd_loo, p_loo, elpd_se,
+ * khat_max, khat_argmax (the point's column 0..29, the lowest on ties), n_bad
+ * (points with khat > min(1 - 1 / log10 S, 0.7)), lppd, flags (an integer stored
+ * as double: bit 0 the row is valid).  Row 6, the comparisons: n_sigma_loo,
+ * n_sigma_loo_forward, n_sigma_loo_reverse, asymmetry_loo, khat_max and n_bad
+ * over the six rows, 0, flags (valid when all six rows are). */
+#define MDFIT_NNUTSLOO 8
+
+/*
+ * Pareto-smoothed importance-sampling leave-one-out of the chains of a finished
+ * MODE_NUTS call (MDFIT-LOO v1): per sub-fit and point the
+ * pointwise log-likelihood of every draw (the full beta-binomial log-pmf, as
+ * the record's WAIC forms it), the generalised Pareto fit of the top M =
+ * min(S / 5, ceil(3 sqrt S)) importance ratios (Zhang & Stephens 2009 with
+ * loo's priors) giving the point's shape khat, the smoothed tail and elpd_i;
+ * per sub-fit their sums and khat's maximum; in row 6 the reference's n_sigma
+ * comparisons (fits.py:194-227) on looic_i = -2 elpd_i in place of waic_i.
+ * khat is +inf when S < 25 and 0 when the tail is constant (a position with N
+ * = 0); neither is smoothed.  A row is valid when the chain's status slot is
+ * 0 and every pointwise log-likelihood of the sub-fit is finite; otherwise
+ * its seven statistics are NaN and flags is 0, as are all seven rows of a taxon
+ * with some y > N.
+ *   y, N      : the counts of that call, uint32[n_taxa][MDFIT_LD] (device; read only)
+ *   workspace : the workspace of that call (device; read only)
+ *   out       : its records (device; read only)
+ *   opts      : the options of that call: mode MDFIT_MODE_NUTS, num_samples in
+ *               [2, 4096] (else MDFIT_E_ARG)
+ *   loo       : double[n_taxa][7][MDFIT_NNUTSLOO]                  (device)
+ *   pointwise : double[n_taxa][6][30][2] = (elpd_i, khat_i), NaN outside a
+ *               sub-fit's points and in an invalid row, or NULL    (device)
+ * One launch on hip_stream, one wave per taxon; no allocation, no side stream,
+ * no host synchronisation, no atomics.  n_taxa: at most 2^25 per call.
+ * Independent of mdfit_nuts_diag and mdfit_nuts_summary: all may run on one
+ * finished call's workspace, in any order.
+ */
+int mdfit_nuts_loo(const uint32_t* y, const uint32_t* N, const void* workspace, const double* out,
+                   int64_t n_taxa, const mdfit_opts* opts, double* loo, double* pointwise,
+                   void* hip_stream);
+
+/*
+ * Test helper: the estimator of mdfit_nuts_loo (its device function) on given
+ * pointwise log-likelihood series ll[n_series][S], one wave per series:
+ * elpd[i] and khat[i]; NaN for a series with a value that is not finite.  S in
+ * [2, 4096] (else MDFIT_E_ARG); n_series at most 2^25.  Device pointers.
+ */
+int mdfit_psis(const double* ll, int64_t n_series, int32_t S, double* elpd, double* khat,
+               void* hip_stream);
+
 /*
  * Pointwise beta-binomial log-pmf (numpyro BetaBinomial.log_prob, used by
  * fits.py:59,67 and log_likelihood fits.py:126-133):

@@ -31,6 +31,8 @@ DIAG_STRIDE = 8
 NLAPLACE = 8
 NNUTSDIAG = 12
 NNUTSSUMM = 16
+NNUTSLOO = 8
+NLOOROW = 7  # rows of a PSIS-LOO record: the six sub-fits, then the comparisons
 
 # output record field order (enum mdfit_field) == fit_results numeric columns
 RESULT_FIELDS = [
@@ -73,6 +75,12 @@ NUTSDIAG_VALID = 1  # flags: bit 0 valid
 NUTSSUMM_FIELDS = ["q_std", "A_std", "c_std", "phi_std", "D_max_std", "D_max_mean", "D_max_median", "D_max_lo",
                    "D_max_hi", "q_median", "q_lo", "q_hi", "phi_median", "rho_Ac", "significance", "flags"]
 NUTSSUMM_VALID = 1  # flags: bit 0 valid
+# PSIS-LOO record (mdfit_nuts_loo): float64 [T][NLOOROW][NNUTSLOO], rows 0..5 in SUBFITS order ...
+NUTSLOO_FIELDS = ["elpd_loo", "p_loo", "elpd_se", "khat_max", "khat_argmax", "n_bad", "lppd", "flags"]
+# ... and row 6, the comparisons
+NUTSLOO_COMPARE_FIELDS = ["n_sigma_loo", "n_sigma_loo_forward", "n_sigma_loo_reverse", "asymmetry_loo", "khat_max",
+                          "n_bad", "reserved", "flags"]
+NUTSLOO_VALID = 1  # flags: bit 0 valid
 
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
@@ -84,6 +92,8 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_laplace_u",
     "mdfit_nuts_diag",
     "mdfit_nuts_summary",
+    "mdfit_nuts_loo",
+    "mdfit_psis",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
     "mdfit_hpdi68",
@@ -163,6 +173,10 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_nuts_diag.restype = ctypes.c_int
     lib.mdfit_nuts_summary.argtypes = [vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp]
     lib.mdfit_nuts_summary.restype = ctypes.c_int
+    lib.mdfit_nuts_loo.argtypes = [vp, vp, vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp, vp]
+    lib.mdfit_nuts_loo.restype = ctypes.c_int
+    lib.mdfit_psis.argtypes = [vp, i64, i32, vp, vp, vp]
+    lib.mdfit_psis.restype = ctypes.c_int
     lib.mdfit_betabinom_logpmf.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.mdfit_betabinom_logpmf.restype = ctypes.c_int
     lib.mdfit_special.argtypes = [vp, i64, vp, vp]

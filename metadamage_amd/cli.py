@@ -55,7 +55,8 @@ def cli_fit(
     inference: str = typer.Option("nuts", help="nuts: NUTS sampling as the reference; map: MAP fit; "
                                   "map-laplace: MAP fit with Laplace standard errors and significance; "
                                   "nuts-diag: NUTS with per-chain ESS, split R-hat, MCSE and divergences; "
-                                  "nuts-summary: NUTS with posterior std, median, 68 % HPDI and significance"),
+                                  "nuts-summary: NUTS with posterior std, median, 68 % HPDI and significance; "
+                                  "nuts-loo: NUTS with PSIS-LOO model comparison and Pareto-k diagnostics"),
 ):
     """Fitting Ancient Damage.
 
@@ -77,8 +78,8 @@ def cli_fit(
         "version": "0.0.0",
         "inference": inference,
     }
-    if inference not in ("nuts", "map", "map-laplace", "nuts-diag", "nuts-summary"):
-        raise typer.BadParameter("--inference must be nuts, map, map-laplace, nuts-diag or nuts-summary")
+    if inference not in ("nuts", "map", "map-laplace", "nuts-diag", "nuts-summary", "nuts-loo"):
+        raise typer.BadParameter("--inference must be nuts, map, map-laplace, nuts-diag, nuts-summary or nuts-loo")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

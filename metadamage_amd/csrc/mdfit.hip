@@ -2086,6 +2086,28 @@ int mdfit_nuts_summary(const void* workspace, const double* out, int64_t n_taxa,
   return mdfit::nuts::summary(workspace, out, n_taxa, *opts, summ, (hipStream_t)hip_stream);
 }
 
+int mdfit_nuts_loo(const uint32_t* y, const uint32_t* N, const void* workspace, const double* out, int64_t n_taxa,
+                   const mdfit_opts* opts, double* loo, double* pointwise, void* hip_stream) {
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (!opts) return set_err(MDFIT_E_ARG, "opts is required (the options of the NUTS call)");
+  if (opts->mode != MDFIT_MODE_NUTS) return set_err(MDFIT_E_ARG, "mdfit_nuts_loo needs opts->mode == MDFIT_MODE_NUTS");
+  if (opts->num_samples < 2 || opts->num_samples > 4096)
+    return set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !workspace || !out || !loo) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  return mdfit::nuts::loo(y, N, workspace, out, n_taxa, *opts, loo, pointwise, (hipStream_t)hip_stream);
+}
+
+int mdfit_psis(const double* ll, int64_t n_series, int32_t S, double* elpd, double* khat, void* hip_stream) {
+  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
+  if (S < 2 || S > 4096) return set_err(MDFIT_E_ARG, "S must be in [2, 4096]");
+  if (n_series == 0) return 0;
+  if (!ll || !elpd || !khat) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  return mdfit::nuts::psis(ll, n_series, (int)S, elpd, khat, (hipStream_t)hip_stream);
+}
+
 int mdfit_nuts_peak_probe(int64_t n_waves, int32_t iters, double* sink, void* hip_stream) {
   if (n_waves <= 0 || iters <= 0 || !sink) return set_err(MDFIT_E_ARG, "bad arguments");
   return mdfit::nuts::peak_probe(n_waves, iters, sink, (hipStream_t)hip_stream);

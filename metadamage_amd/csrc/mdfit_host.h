@@ -85,4 +85,11 @@ int diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_o
 // status slots, writes summ[n_taxa][6][MDFIT_NNUTSSUMM]
 int summary(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* summ_out,
             hipStream_t s);
+// MDFIT-LOO v1 of the same chains: one launch, reads y, N, the draws and out's
+// chain status slots, writes loo[n_taxa][7][MDFIT_NNUTSLOO] and, unless null,
+// pointwise[n_taxa][6][30][2]
+int loo(const uint32_t* y, const uint32_t* N, const void* workspace, const double* out, int64_t n_taxa,
+        const mdfit_opts& o, double* loo_out, double* pointwise, hipStream_t s);
+// steps 1-6 of MDFIT-LOO v1 on given series ll[n_series][S], one wave per series
+int psis(const double* ll, int64_t n_series, int S, double* elpd, double* khat, hipStream_t s);
 }  // namespace mdfit::nuts

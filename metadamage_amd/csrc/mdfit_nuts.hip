@@ -33,6 +33,7 @@
 #include "mdfit_host.h"
 #include "mdfit_model.h"
 #include "mdfit_nutsdiag.h"
+#include "mdfit_nutsloo.h"
 #include "mdfit_nutssumm.h"
 #include "mdfit_special.h"
 
@@ -1987,6 +1988,150 @@ __global__ __launch_bounds__(kWave) void nuts_summary_kernel(const double* __res
 }
 
 // ---------------------------------------------------------------------------
+// MDFIT-LOO v1: PSIS-LOO and Pareto-k of finished chains
+// ---------------------------------------------------------------------------
+// SummWave's sums and sorts, and the maximum by the same butterfly
+struct LooWave : SummWave {
+  __device__ __forceinline__ double max(double v) const {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, kWave));
+    return __shfl(v, 0, kWave);
+  }
+};
+
+// One wave per taxon, its six sub-fits one after another (the comparisons of
+// row 6 read all six, and there is neither a second launch nor an atomic to
+// bring them together across blocks).  Per point: the pointwise log-likelihood
+// of every draw by the WAIC loop's own arithmetic (lanes over draws; the lppd
+// out of the same pass), its negative into the LDS sort buffer, then
+// nutsloo::psis_point -- the sort of §9.2, the M excesses in LDS, one lane per
+// grid point of the Pareto fit walking them by broadcast reads.  A sub-fit
+// with a log-likelihood that is not finite still takes the pass over all its
+// points and skips their fits.  Reads y, N, samples and out only.
+__global__ __launch_bounds__(kWave) void nuts_loo_kernel(const uint32_t* __restrict__ gy,
+                                                         const uint32_t* __restrict__ gN,
+                                                         const double* __restrict__ samples,
+                                                         const double* __restrict__ out, int64_t n_taxa, int S,
+                                                         double tau, double* __restrict__ loo,
+                                                         double* __restrict__ pointwise) {
+  extern __shared__ double s_v[];
+  __shared__ double s_y[kLD], s_N[kLD];
+  __shared__ double s_pt[3][kNPos];                  // the current sub-fit's elpd_i, lppd_i, khat_i
+  __shared__ double s_loo[MDFIT_NSUBFIT + 1][kNPos];  // looic_i; row 6: PMD-forward | PMD-reverse
+  const int lane = threadIdx.x;
+  const int64_t t = blockIdx.x;
+  if (t >= n_taxa) return;
+  if (lane < kLD) {
+    s_y[lane] = (double)gy[t * kLD + lane];
+    s_N[lane] = (double)gN[t * kLD + lane];
+  }
+  for (int x = lane; x < (MDFIT_NSUBFIT + 1) * kNPos; x += kWave) (&s_loo[0][0])[x] = NAN;
+  __syncthreads();
+  const bool taxon_ok = !__any(lane < kNPos && s_y[lane] > s_N[lane]);  // (status 3: every row NaN)
+  const LooWave w;
+  const double* smp = samples + t * MDFIT_NSUBFIT * (int64_t)S * 4;
+  double* rec = loo + t * (MDFIT_NSUBFIT + 1) * MDFIT_NNUTSLOO;
+  double all_kmax = -INFINITY, all_nbad = 0.0;
+  bool all_ok = true;
+  for (int s = 0; s < MDFIT_NSUBFIT; ++s) {
+#pragma clang fp contract(off)  // (the WAIC loop's rounding of every lp)
+    const bool pmd = s == 0 || s == 2 || s == 3;
+    const int lo = (s == 3 || s == 5) ? kNHalf : 0, hi = s < 2 ? kNPos : lo + kNHalf;
+    bool ok = taxon_ok && out[t * MDFIT_NOUT + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * s + 6] == 0.0;  // (wave-uniform)
+    for (int col = lo; col < hi && taxon_ok; ++col) {
+      const double yy = s_y[col], nn = s_N[col];
+      const int k = col < kNHalf ? col : col - kNHalf;
+      const double lc = lg3<false, MDFIT_TLOG_NUTS>(nn + 1.0).l - lg3<false, MDFIT_TLOG_NUTS>(yy + 1.0).l -
+                        lg3<false, MDFIT_TLOG_NUTS>(nn - yy + 1.0).l;
+      double mxl = -INFINITY, sel = 0.0;
+      bool bad = false;
+      for (int x = lane; x < S; x += kWave) {
+        const double* th = smp + ((int64_t)s * S + x) * 4;
+        const double D = d_at(th, pmd, k), phi = th[3];
+        const double a = D * phi, b = (1.0 - D) * phi;
+        const double lw = lc + (lg3<false, MDFIT_TLOG_NUTS>(yy + a).l - lg3<false, MDFIT_TLOG_NUTS>(a).l) +
+                          (lg3<false, MDFIT_TLOG_NUTS>(nn - yy + b).l - lg3<false, MDFIT_TLOG_NUTS>(b).l) -
+                          (lg3<false, MDFIT_TLOG_NUTS>(nn + phi).l - lg3<false, MDFIT_TLOG_NUTS>(a + b).l);
+        // N = 0: the pmf is 1 and l is 0, exactly (the sum above leaves a + b against phi, ~1e-14,
+        // which would pass for a tail); a draw that is not finite still shows
+        const double lp = nn == 0.0 ? lw - lw : lw;
+        bad = bad || !isfinite(lp);
+        s_v[x] = -lp;
+        if (lp > mxl) {
+          sel = sel * pexp(mxl - lp) + 1.0;
+          mxl = lp;
+        } else {
+          sel += pexp(lp - mxl);
+        }
+      }
+      if (__any(bad)) ok = false;
+      if (!ok) continue;  // (wave-uniform; the fit is skipped, the pass over the draws is not)
+      const double mx = wmax(mxl);
+      const double se = wsum(sel * pexp(mxl - mx));
+      const double lppd = mx + log(se) - log((double)S);
+      double elpd, khat;
+      nutsloo::psis_point(w, s_v, S, elpd, khat);
+      if (lane == 0) {
+        s_pt[0][col - lo] = elpd;
+        s_pt[1][col - lo] = lppd;
+        s_pt[2][col - lo] = khat;
+        s_loo[s][col] = -2.0 * elpd;
+        if (s == 2 || s == 3) s_loo[MDFIT_NSUBFIT][col] = -2.0 * elpd;
+      }
+    }
+    __syncthreads();
+    if (ok) {
+      double km, nb;
+      nutsloo::row_stats(w, s_pt[0], s_pt[1], s_pt[2], hi - lo, lo, tau, rec + s * MDFIT_NNUTSLOO, km, nb);
+      all_kmax = fmax(all_kmax, km);
+      all_nbad += nb;
+    } else {
+      all_ok = false;
+      if (lane == 0) nutsloo::invalid_row(rec + s * MDFIT_NNUTSLOO);
+      if (lane < kNPos) s_loo[s][lane] = NAN;
+      if ((s == 2 || s == 3) && lane >= lo && lane < hi) s_loo[MDFIT_NSUBFIT][lane] = NAN;
+    }
+    if (pointwise != nullptr && lane < 2 * kNPos) {
+      const int col = lane >> 1;
+      const bool in = ok && col >= lo && col < hi;
+      pointwise[((t * MDFIT_NSUBFIT + s) * kNPos) * 2 + lane] = in ? s_pt[(lane & 1) ? 2 : 0][col - lo] : NAN;
+    }
+    __syncthreads();  // (the next sub-fit overwrites s_pt)
+  }
+  // row 6: fits.py:194-227 on looic_i (an invalid row's column is NaN: its comparisons are)
+  const double ns = nutsloo::n_sigma(w, s_loo[0], s_loo[1], kNPos);
+  const double nsf = nutsloo::n_sigma(w, s_loo[2], s_loo[4], kNHalf);
+  const double nsr = nutsloo::n_sigma(w, s_loo[3] + kNHalf, s_loo[5] + kNHalf, kNHalf);
+  const double asy = nutsloo::n_sigma(w, s_loo[0], s_loo[MDFIT_NSUBFIT], kNPos);
+  if (lane == 0) {
+    double* r6 = rec + MDFIT_NSUBFIT * MDFIT_NNUTSLOO;
+    r6[nutsloo::kNSigma] = ns;
+    r6[nutsloo::kNSigmaForward] = nsf;
+    r6[nutsloo::kNSigmaReverse] = nsr;
+    r6[nutsloo::kAsymmetry] = asy;
+    r6[nutsloo::kAllKhatMax] = taxon_ok && all_kmax > -INFINITY ? all_kmax : NAN;
+    r6[nutsloo::kAllNBad] = taxon_ok ? all_nbad : NAN;
+    r6[6] = taxon_ok ? 0.0 : NAN;
+    r6[nutsloo::kFlags] = all_ok ? nutsloo::kValid : 0.0;
+  }
+}
+
+// mdfit_psis: one wave per series ll[row][0..S)
+__global__ __launch_bounds__(kWave) void psis_kernel(const double* __restrict__ ll, int64_t n_series, int S,
+                                                     double* __restrict__ elpd, double* __restrict__ khat) {
+  extern __shared__ double s_v[];
+  const int64_t row = blockIdx.x;
+  if (row >= n_series) return;
+  for (int x = threadIdx.x; x < S; x += kWave) s_v[x] = -ll[row * (int64_t)S + x];
+  double e, k;
+  nutsloo::psis_point(LooWave{}, s_v, S, e, k);
+  if (threadIdx.x == 0) {
+    elpd[row] = e;
+    khat[row] = k;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 int diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts& o, double* diag_out,
@@ -2016,6 +2161,29 @@ int summary(const void* workspace, const double* out, int64_t n_taxa, const mdfi
                      (size_t)nutssumm::sort_len((int)o.num_samples) * sizeof(double), s, samples, out, n_rows,
                      (int)o.num_samples, summ_out);
   return host::check_launch("nuts_summary_kernel");
+}
+
+int loo(const uint32_t* y, const uint32_t* N, const void* workspace, const double* out, int64_t n_taxa,
+        const mdfit_opts& o, double* loo_out, double* pointwise, hipStream_t s) {
+  if (o.mode != MDFIT_MODE_NUTS)
+    return host::set_err(MDFIT_E_ARG, "mdfit_nuts_loo needs opts->mode == MDFIT_MODE_NUTS");
+  if (o.num_samples < 2 || o.num_samples > kMaxSamples)  // (the LDS bound)
+    return host::set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
+  const double* samples = (const double*)((const char*)workspace + kSamplesOffset);
+  const int S = (int)o.num_samples;
+  host::debug_poison(s);
+  hipLaunchKernelGGL(nuts_loo_kernel, dim3((unsigned)n_taxa), dim3(kWave),
+                     (size_t)nutsloo::work_len(S) * sizeof(double), s, y, N, samples, out, n_taxa, S,
+                     nutsloo::khat_threshold(S), loo_out, pointwise);
+  return host::check_launch("nuts_loo_kernel");
+}
+
+int psis(const double* ll, int64_t n_series, int S, double* elpd, double* khat, hipStream_t s) {
+  if (S < 2 || S > kMaxSamples) return host::set_err(MDFIT_E_ARG, "S must be in [2, 4096]");
+  host::debug_poison(s);
+  hipLaunchKernelGGL(psis_kernel, dim3((unsigned)n_series), dim3(kWave),
+                     (size_t)nutsloo::work_len(S) * sizeof(double), s, ll, n_series, S, elpd, khat);
+  return host::check_launch("psis_kernel");
 }
 
 // Register-only throughput probe of the sampler's point evaluation: the chain

@@ -40,6 +40,7 @@ class FitBatch:
     lap: "object" = None  # torch.float32 [T, 3, NLAPLACE]: the Laplace records (ChunkedFitter with_laplace)
     diag: "object" = None  # torch.float32 [T, 6, NNUTSDIAG]: the sampling diagnostics (ChunkedFitter with_diag)
     summ: "object" = None  # torch.float32 [T, 6, NNUTSSUMM]: the posterior summaries (ChunkedFitter with_summary)
+    loo: "object" = None  # torch.float32 [T, 7, NNUTSLOO]: the PSIS-LOO records (ChunkedFitter with_loo)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -202,6 +203,64 @@ def nuts_summary_device(res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, summ=N
     return summ
 
 
+def nuts_loo_device(y, N, res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, loo=None, pointwise=None, stream=None):
+    """Launch mdfit_nuts_loo on the chains a finished NUTS call left in
+    res.workspace (asynchronous on `stream`; before the next call on that
+    workspace): PSIS-LOO per sub-fit -- elpd_loo, p_loo, its standard error, the
+    largest Pareto k and where, the count of bad points, lppd -- and in row 6 the
+    n_sigma comparisons on looic, float64 loo[T, 7, NNUTSLOO]
+    (_lib.NUTSLOO_FIELDS, _lib.NUTSLOO_COMPARE_FIELDS).  y, N: the call's device
+    counts [T, LD].  pointwise: None, True (allocated) or a float64 tensor [T, 6,
+    30, 2] = (elpd_i, khat_i).  Reads y, N, res.workspace and res.out only;
+    independent of nuts_diag_device and nuts_summary_device (any order on one
+    workspace).  Returns loo, or (loo, pointwise) when pointwise is asked for."""
+    torch = _torch()
+    lib = _lib.load()
+    T = int(n_taxa)
+    if loo is None:
+        loo = torch.empty((T, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float64, device=res.out.device)
+    if not (loo.is_cuda and loo.is_contiguous() and loo.dtype == torch.float64
+            and loo.numel() == T * _lib.NLOOROW * _lib.NNUTSLOO):
+        raise ValueError(f"loo must be a contiguous cuda float64 tensor of {T * _lib.NLOOROW * _lib.NNUTSLOO} elements")
+    if pointwise is True:
+        pointwise = torch.empty((T, _lib.NSUBFIT, _lib.NPOS, 2), dtype=torch.float64, device=res.out.device)
+    if pointwise is not None and not (pointwise.is_cuda and pointwise.is_contiguous()
+                                      and pointwise.dtype == torch.float64
+                                      and pointwise.numel() == T * _lib.NSUBFIT * _lib.NPOS * 2):
+        raise ValueError(f"pointwise must be a contiguous cuda float64 tensor of {T * _lib.NSUBFIT * _lib.NPOS * 2} elements")
+    for name, a in (("y", y), ("N", N)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and int(res.out.shape[0]) >= T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    if int(opts.mode) == _lib.MODE_NUTS and (res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts)):
+        raise ValueError("res.workspace does not hold the draws of T taxa under opts")
+    _lib.check(lib.mdfit_nuts_loo(ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(N.data_ptr()),
+                                  ctypes.c_void_p(res.workspace.data_ptr()) if res.workspace is not None else None,
+                                  ctypes.c_void_p(res.out.data_ptr()), T, ctypes.byref(opts),
+                                  ctypes.c_void_p(loo.data_ptr()),
+                                  ctypes.c_void_p(pointwise.data_ptr()) if pointwise is not None else None,
+                                  _stream_handle(torch, stream)))
+    return loo if pointwise is None else (loo, pointwise)
+
+
+def psis(ll, device="cuda"):
+    """(elpd[n], khat[n]) float64 host arrays of the pointwise log-likelihood
+    series ll[n, S] by the device's PSIS estimator (MDFIT-LOO v1, mdfit_psis;
+    parity tests)."""
+    torch = _torch()
+    lib = _lib.load()
+    ll = np.ascontiguousarray(ll, dtype=np.float64)
+    n, S = ll.shape
+    t = torch.from_numpy(ll).to(device)
+    elpd = torch.empty(n, dtype=torch.float64, device=device)
+    khat = torch.empty(n, dtype=torch.float64, device=device)
+    _lib.check(lib.mdfit_psis(ctypes.c_void_p(t.data_ptr()), n, S, ctypes.c_void_p(elpd.data_ptr()),
+                              ctypes.c_void_p(khat.data_ptr()), _stream_handle(torch, None)))
+    torch.cuda.current_stream().synchronize()
+    return elpd.cpu().numpy(), khat.cpu().numpy()
+
+
 def fit_batch(y, N, mm=None, opts: _lib.MdfitOpts | None = None, device="cuda"):
     """Host arrays in, host arrays out: (out[T,80] f64, pred[T,3,30] f32, status[T] i32)."""
     torch = _torch()
@@ -240,6 +299,23 @@ def _check_summary_mode(with_summary: bool, opts: _lib.MdfitOpts | None, with_la
         raise ValueError("with_summary, with_diag and with_laplace are mutually exclusive: one extra block per run")
 
 
+LOO_BYTES = _lib.NLOOROW * _lib.NNUTSLOO * 4  # one taxon's PSIS-LOO records on the way out: f32 [7][8]
+
+
+def _check_loo_mode(with_loo: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
+                    with_diag: bool = False, with_summary: bool = False) -> None:
+    """with_loo is the sampling mode's (opts None: the default options, MAP) and
+    the run's one optional extra block: not together with with_diag,
+    with_summary or with_laplace."""
+    if not with_loo:
+        return
+    if opts is None or int(opts.mode) != _lib.MODE_NUTS:
+        raise ValueError("with_loo needs the chains of a sampling call (opts.mode == MODE_NUTS)")
+    if with_diag or with_summary or with_laplace:
+        raise ValueError("with_loo, with_summary, with_diag and with_laplace are mutually exclusive: "
+                         "one extra block per run")
+
+
 def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
     """with_diag is the sampling mode's (opts None: the default options, MAP)."""
     if with_diag and (opts is None or int(opts.mode) != _lib.MODE_NUTS):
@@ -248,7 +324,7 @@ def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
 
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
                  dest_on_device: bool = False, with_laplace: bool = False, with_diag: bool = False,
-                 with_summary: bool = False) -> int:
+                 with_summary: bool = False, with_loo: bool = False) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -260,10 +336,14 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     device buffer -- 288 B rounded to f32 (NUTS only: ValueError under MAP).
     with_summary: the posterior summaries, 768 B as computed (f64) and --
     unless they go to the caller's device buffer -- 384 B rounded to f32 (NUTS
-    only, and not together with with_diag or with_laplace: ValueError)."""
+    only, and not together with with_diag or with_laplace: ValueError).
+    with_loo: the PSIS-LOO records, 448 B as computed (f64) and -- unless they
+    go to the caller's device buffer -- 224 B rounded to f32 (NUTS only, and the
+    run's only extra block: ValueError)."""
     C = int(C)
     _check_diag_mode(with_diag, opts)
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
+    _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
@@ -273,13 +353,16 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
         b += C * (2 * DIAG_BYTES + (0 if dest_on_device else DIAG_BYTES))
     if with_summary:
         b += C * (2 * SUMM_BYTES + (0 if dest_on_device else SUMM_BYTES))
+    if with_loo:
+        b += C * (2 * LOO_BYTES + (0 if dest_on_device else LOO_BYTES))
     return b + workspace_bytes(C, opts)
 
 
 def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | None = None, *,
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
                 dest_on_device: bool = False, with_laplace: bool = False,
-                with_diag: bool = False, with_summary: bool = False) -> list[tuple[int, int]]:
+                with_diag: bool = False, with_summary: bool = False,
+                with_loo: bool = False) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk fit in budget_bytes (None: no memory
     bound), no chunk exceeds the per-call limit (2^25 taxa) or chunk_taxa (> 0;
@@ -289,6 +372,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     T = int(T)
     _check_diag_mode(with_diag, opts)
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
+    _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -298,7 +382,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
         per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, with_laplace,  # noqa: E731
-                                              with_diag, with_summary)
+                                              with_diag, with_summary, with_loo)
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
         if per(cap) > budget_bytes:  # largest c with per(c) <= budget (per is monotone in c)
@@ -330,7 +414,8 @@ class _Set:
     run one after another on the compute stream)."""
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
-                 with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False):
+                 with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
+                 with_loo: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -355,6 +440,11 @@ class _Set:
             self.summ64 = torch.empty((C, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.summ = torch.empty((C, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float32, device=device)
+        self.loo64 = self.loo = None
+        if with_loo:  # as mdfit_nuts_loo writes them, and rounded to f32 for the way out
+            self.loo64 = torch.empty((C, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float64, device=device)
+            if not dest_on_device:
+                self.loo = torch.empty((C, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -399,31 +489,38 @@ class ChunkedFitter:
     optional extra block per run keeps the gather record's layout a single
     switch): mdfit_nuts_summary follows each chunk's fit on the compute stream
     in the same way, and its records, rounded to f32 there, leave as f32 [T, 6,
-    16], 384 B per taxon (run's fourth array; dest.summ)."""
+    16], 384 B per taxon (run's fourth array; dest.summ).
+
+    with_loo (NUTS only; the run's only extra block): mdfit_nuts_loo follows
+    each chunk's fit on the compute stream in the same way, reading the chunk's
+    device counts beside its draws, and its records, rounded to f32 there, leave
+    as f32 [T, 7, 8], 224 B per taxon (run's fourth array; dest.loo)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False,
-                 with_diag: bool = False, with_summary: bool = False):
+                 with_diag: bool = False, with_summary: bool = False, with_loo: bool = False):
         _check_diag_mode(with_diag, opts)
         _check_summary_mode(with_summary, opts, with_laplace, with_diag)
+        _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
         torch = _torch()
         if with_laplace and opts is not None and int(opts.mode) != _lib.MODE_MAP:
             raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
         self.with_laplace = bool(with_laplace)
         self.with_diag = bool(with_diag)
         self.with_summary = bool(with_summary)
+        self.with_loo = bool(with_loo)
         self.chunk_cap = int(chunk_cap)
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.with_laplace,
-                          self.with_diag, self.with_summary)
+                          self.with_diag, self.with_summary, self.with_loo)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = self.h_lap = None
-        self.h_diag = self.h_summ = None
+        self.h_diag = self.h_summ = self.h_loo = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -445,6 +542,8 @@ class ChunkedFitter:
                 self.h_diag = torch.empty((cap, _lib.NSUBFIT, _lib.NNUTSDIAG), dtype=torch.float32).pin_memory()
             if self.with_summary:
                 self.h_summ = torch.empty((cap, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float32).pin_memory()
+            if self.with_loo:
+                self.h_loo = torch.empty((cap, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -480,6 +579,9 @@ class ChunkedFitter:
         _check_summary_mode(self.with_summary, o0)
         if self.with_summary and dest is not None and dest.summ is None:
             raise ValueError("with_summary: dest.summ (float32 [T, 6, NNUTSSUMM]) required")
+        _check_loo_mode(self.with_loo, o0)
+        if self.with_loo and dest is not None and dest.loo is None:
+            raise ValueError("with_loo: dest.loo (float32 [T, 7, NNUTSLOO]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -544,6 +646,12 @@ class ChunkedFitter:
                 summ32 = dest.summ[lo:hi] if dest is not None else st.summ[:n]
                 with torch.cuda.stream(comp):
                     summ32.copy_(st.summ64[:n])
+            loo32 = None
+            if self.with_loo:  # this chunk's draws and counts, before the next chunk's fit overwrites the workspace
+                nuts_loo_device(st.d_y[:n], st.d_N[:n], res, n, o, loo=st.loo64[:n], stream=comp)
+                loo32 = dest.loo[lo:hi] if dest is not None else st.loo[:n]
+                with torch.cuda.stream(comp):
+                    loo32.copy_(st.loo64[:n])
             ev_done = torch.cuda.Event()
             ev_done.record(comp)
             done.append(ev_done)
@@ -560,6 +668,8 @@ class ChunkedFitter:
                         self.h_diag[lo:hi].copy_(diag32, non_blocking=True)
                     if summ32 is not None:
                         self.h_summ[lo:hi].copy_(summ32, non_blocking=True)
+                    if loo32 is not None:
+                        self.h_loo[lo:hi].copy_(loo32, non_blocking=True)
                 last_d2h = cp
         end = torch.cuda.Event()
         end.record(cp if last_d2h is not None else comp)
@@ -570,7 +680,7 @@ class ChunkedFitter:
             pinned: PinnedPack | None = None, chunks=None):
         """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status -- and,
         with_laplace, lap[:, 3, 8] f32, or, with_diag, diag[:, 6, 12] f32, or,
-        with_summary, summ[:, 6, 16] f32) of the
+        with_summary, summ[:, 6, 16] f32, or, with_loo, loo[:, 7, 8] f32) of the
         pinned buffers (valid until the next run).  pinned: y, N, mm are that
         PinnedPack's views.  chunks: the split (default plan_chunks at this
         staging's chunk_cap)."""
@@ -590,12 +700,15 @@ class ChunkedFitter:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_diag[:T].numpy()
         if self.with_summary:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_summ[:T].numpy()
+        if self.with_loo:
+            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_loo[:T].numpy()
         return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy()
 
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
         (out[T, NOUT], pred, status -- with_laplace also lap, f32 [T, 3, 8],
-        with_diag also diag, f32 [T, 6, 12], with_summary also summ, f32 [T, 6, 16]: rows written in place),
+        with_diag also diag, f32 [T, 6, 12], with_summary also summ, f32 [T, 6, 16], with_loo also loo, f32
+        [T, 7, 8]: rows written in place),
         ordered on the caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
@@ -663,7 +776,8 @@ _STAGING_LOCK = __import__("threading").Lock()
 
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
             dest_on_device: bool = False, budget_bytes: int | None = None,
-            with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False) -> ChunkedFitter:
+            with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
+            with_loo: bool = False) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind and sampler length): the
     multi-file pipeline fits one file after another, and pinned + device
@@ -680,7 +794,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     o = opts if opts is not None else _lib.default_opts()
     env_chunk = int(os.environ.get("MDFIT_CHUNK_TAXA", "0") or 0)
     key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
-           bool(with_laplace), bool(with_diag), bool(with_summary))
+           bool(with_laplace), bool(with_diag), bool(with_summary), bool(with_loo))
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -697,10 +811,12 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     if T < _lib.STREAM_MAX_TAXA:
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
-                      with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary)[0]
+                      with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
+                      with_loo=with_loo)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
-                       with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary)
+                       with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
+                       with_loo=with_loo)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -709,13 +825,14 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, laplace: bool = False, diag: bool = False,
-                   summary: bool = False):
+                   summary: bool = False, loo: bool = False):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
     the PMD sub-fits (_lib.LAPLACE_FIELDS), or, with diag (NUTS only), diag[T, 6,
     12] f32, the sampling diagnostics of the six sub-fits (_lib.NUTSDIAG_FIELDS), or, with summary
     (NUTS only; at most one of the three), summ[T, 6, 16] f32, their posterior
-    summaries (_lib.NUTSSUMM_FIELDS) --, chunked
+    summaries (_lib.NUTSSUMM_FIELDS), or, with loo (NUTS only; the only one),
+    loo[T, 7, 8] f32, the PSIS-LOO records (_lib.NUTSLOO_FIELDS) --, chunked
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
@@ -723,14 +840,14 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     T = int(y.shape[0])
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace, with_diag=diag,
-                     with_summary=summary)
+                     with_summary=summary, with_loo=loo)
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
-        extra = got[3].copy() if laplace or diag or summary else None
+        extra = got[3].copy() if laplace or diag or summary or loo else None
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
-    if laplace or diag or summary:
+    if laplace or diag or summary or loo:
         return out, pred, status, extra
     return out, pred, status
 

@@ -78,6 +78,18 @@ NUTS_SUMMARY_COLUMNS = [name for name, _, _ in _NUTS_SUMMARY_PICKS]
 # ... then uint32 nuts_summary_valid: the rows 0, 2 and 3 all valid
 NUTS_SUMMARY_UINT_COLUMNS = ["nuts_summary_valid"]
 _NUTS_SUMMARY_ROWS = (0, 2, 3)
+# "nuts-loo": the PSIS-LOO model comparison appended after shortname (DESIGN.md
+# §9.3), float32 -- (column, row of the loo record: 0 PMD-all, 1 null-all, 6 the
+# comparisons, its field index)
+_NUTS_LOO_PICKS = (
+    [("elpd_loo", 0, 0), ("p_loo", 0, 1), ("elpd_loo_se", 0, 2), ("pareto_k_max", 0, 3),
+     ("elpd_loo_null", 1, 0), ("p_loo_null", 1, 1), ("pareto_k_max_null", 1, 3),
+     ("n_sigma_loo", 6, 0), ("n_sigma_loo_forward", 6, 1), ("n_sigma_loo_reverse", 6, 2), ("asymmetry_loo", 6, 3)]
+)
+NUTS_LOO_COLUMNS = [name for name, _, _ in _NUTS_LOO_PICKS]
+# ... then uint32 pareto_k_bad (the points of the six sub-fits with khat above the
+# threshold: row 6's count) and nuts_loo_valid (row 6's valid bit: all six rows valid)
+NUTS_LOO_UINT_COLUMNS = ["pareto_k_bad", "nuts_loo_valid"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -266,7 +278,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
-               summary: bool = False):
+               summary: bool = False, loo: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -275,7 +287,9 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     follows the fit and the fourth array is the sampling diagnostics diag[T, 6,
     12] f32 (flags: bit 0 valid, above it the chain's divergence count).  summary
     (NUTS): mdfit_nuts_summary follows the fit and the fourth array is the
-    posterior summaries summ[T, 6, 16] f32.  At most one of the three."""
+    posterior summaries summ[T, 6, 16] f32.  loo (NUTS): mdfit_nuts_loo follows
+    the fit and the fourth array is the PSIS-LOO records loo[T, 7, 8] f32.  At
+    most one of the four."""
     import torch
 
     from . import engine
@@ -299,17 +313,17 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     if not grouped:
         try:
             return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
-                                         summary=summary)
+                                         summary=summary, loo=loo)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary)
+        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo)
     finally:
         p.release_pinned()
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
-                 summary: bool = False):
+                 summary: bool = False, loo: bool = False):
     import torch
 
     from . import engine
@@ -320,18 +334,19 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts = _lib.MdfitOpts.from_buffer_copy(opts)
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
-    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary)
+    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo)
     if hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
         # records written in place into the gather buffers
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
-                                with_laplace=laplace, with_diag=diag, with_summary=summary)
+                                with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                                                lap=rec.lap[: hi - lo] if laplace else None,
                                                diag=rec.diag[: hi - lo] if diag else None,
-                                               summ=rec.summ[: hi - lo] if summary else None))
+                                               summ=rec.summ[: hi - lo] if summary else None,
+                                               loo=rec.loo[: hi - lo] if loo else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -339,7 +354,8 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     parts = gather_records(buf, cap, rank, world)
     if rank != 0:
         return None
-    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary)
+    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
+                           with_loo=loo)
 
 
 # --------------------------------------------------------------------------
@@ -395,7 +411,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
     return cols
 
 
-def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None) -> pd.DataFrame:
+def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -405,7 +421,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     fit_packed returns them): the NUTS_DIAG_COLUMNS follow as float32, then the
     NUTS_DIAG_UINT_COLUMNS.  summ (the posterior summaries [T, 6, 16] of a
     "nuts-summary" run): the NUTS_SUMMARY_COLUMNS follow as float32, then
-    nuts_summary_valid (uint32: the PMD rows 0, 2 and 3 all valid)."""
+    nuts_summary_valid (uint32: the PMD rows 0, 2 and 3 all valid).  loo (the
+    PSIS-LOO records [T, 7, 8] of a "nuts-loo" run): the NUTS_LOO_COLUMNS follow
+    as float32, then pareto_k_bad and nuts_loo_valid (uint32)."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -446,6 +464,15 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         flags = np.nan_to_num(ks[:, _NUTS_SUMMARY_ROWS, _lib.NUTSSUMM_FIELDS.index("flags")]).astype(np.int64)
         data["nuts_summary_valid"] = ((flags & _lib.NUTSSUMM_VALID) != 0).all(axis=1).astype(np.uint32)
         columns += NUTS_SUMMARY_COLUMNS + NUTS_SUMMARY_UINT_COLUMNS
+    if loo is not None:
+        kl = np.asarray(loo) if keep is None else np.asarray(loo)[keep]
+        for name, row, field in _NUTS_LOO_PICKS:
+            data[name] = np.ascontiguousarray(kl[:, row, field], dtype=np.float32)
+        cmp_ = _lib.NUTSLOO_COMPARE_FIELDS.index
+        data["pareto_k_bad"] = _uint32(np.nan_to_num(kl[:, 6, cmp_("n_bad")]).astype(np.int64))
+        flags = np.nan_to_num(kl[:, 6, cmp_("flags")]).astype(np.int64)
+        data["nuts_loo_valid"] = ((flags & _lib.NUTSLOO_VALID) != 0).astype(np.uint32)
+        columns += NUTS_LOO_COLUMNS + NUTS_LOO_UINT_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
@@ -470,7 +497,8 @@ def make_opts(cfg, mcmc_kwargs=None):
     """Engine options for cfg.inference: "nuts" (the reference's sampler,
     num_warmup / num_samples from mcmc_kwargs as fits.py:792-799 passes them)
     "nuts-diag" (the same call; wants_diag adds the sampling diagnostics),
-    "nuts-summary" (the same call; wants_summary adds the posterior summaries), "map"
+    "nuts-summary" (the same call; wants_summary adds the posterior summaries),
+    "nuts-loo" (the same call; wants_loo adds the PSIS-LOO model comparison), "map"
     or "map-laplace" (the MAP fit; wants_laplace adds the standard errors)."""
     inference = getattr(cfg, "inference", "nuts")
     if mode_of(inference) == _lib.MODE_MAP:
@@ -481,14 +509,15 @@ def make_opts(cfg, mcmc_kwargs=None):
 
 
 def mode_of(inference: str) -> int:
-    """The engine mode of an --inference value: "nuts", "nuts-diag" and
-    "nuts-summary" (the sampler; wants_diag adds mdfit_nuts_diag, wants_summary
-    mdfit_nuts_summary) or "map" and "map-laplace"."""
+    """The engine mode of an --inference value: "nuts", "nuts-diag",
+    "nuts-summary" and "nuts-loo" (the sampler; wants_diag adds mdfit_nuts_diag,
+    wants_summary mdfit_nuts_summary, wants_loo mdfit_nuts_loo) or "map" and
+    "map-laplace"."""
     if inference in ("map", "map-laplace"):
         return _lib.MODE_MAP
-    if inference in ("nuts", "nuts-diag", "nuts-summary"):
+    if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo"):
         return _lib.MODE_NUTS
-    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'nuts-diag' or 'nuts-summary', "
+    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'nuts-diag', 'nuts-summary' or 'nuts-loo', "
                      f"got {inference!r}")
 
 
@@ -500,6 +529,11 @@ def wants_diag(cfg) -> bool:
 def wants_summary(cfg) -> bool:
     """cfg.inference "nuts-summary": the sampler followed by mdfit_nuts_summary."""
     return getattr(cfg, "inference", "nuts") == "nuts-summary"
+
+
+def wants_loo(cfg) -> bool:
+    """cfg.inference "nuts-loo": the sampler followed by mdfit_nuts_loo."""
+    return getattr(cfg, "inference", "nuts") == "nuts-loo"
 
 
 def wants_laplace(cfg) -> bool:
@@ -516,17 +550,18 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
         opts = make_opts(cfg, mcmc_kwargs)
     p = pack_counts(df_counts, cfg)
     res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
-                     summary=wants_summary(cfg))
+                     summary=wants_summary(cfg), loo=wants_loo(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
     summ = rest[0] if rest and wants_summary(cfg) else None
+    loo = rest[0] if rest and wants_loo(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ),
+    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo),
             make_df_fit_predictions(p, pred, keep, cfg))
 
 
@@ -622,13 +657,15 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     # fits.py:792-799
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
-                     laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg))
+                     laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
+                     loo=wants_loo(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
     summ = rest[0] if rest and wants_summary(cfg) else None
+    loo = rest[0] if rest and wants_loo(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -636,7 +673,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     def finish():
         from .counts import _save
 
-        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ)
+        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())

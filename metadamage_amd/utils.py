@@ -61,8 +61,8 @@ class Config:
     N_fits: Optional[int] = None
     # this engine's addition: "nuts" samples like the reference (fits.py:382-387),
     # "map" is the frequentist MAP fit (BASELINE config 2); "map-laplace",
-    # "nuts-diag" and "nuts-summary" add their columns to fit_results; saved in
-    # the parquet metadata and part of the cache key
+    # "nuts-diag", "nuts-summary" and "nuts-loo" add their columns to
+    # fit_results; saved in the parquet metadata and part of the cache key
     inference: str = "nuts"
     N_cores: int = field(init=False)
 
