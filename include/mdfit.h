@@ -349,6 +349,64 @@ int mdfit_nuts_loo(const uint32_t* y, const uint32_t* N, const void* workspace, 
 int mdfit_psis(const double* ll, int64_t n_series, int32_t S, double* elpd, double* khat,
                void* hip_stream);
 
+/* Importance-sampled posterior record: double psis[T][3][MDFIT_NMAPPSIS], rows
+ * PMD-all, PMD-forward, PMD-reverse: q_mean A_mean c_mean phi_mean D_max_mean,
+ * q_std A_std c_std phi_std D_max_std, rho_Ac, significance, khat, ess,
+ * n_infeasible, flags (an integer stored as double: bit 0 the row is valid,
+ * bit 1 khat <= min(1 - 1 / log10 S, 0.7), bits 2..5 coordinate (q, A, c, phi)
+ * free). */
+#define MDFIT_NMAPPSIS 16
+
+/*
+ * Importance-sampled posterior of the PMD sub-fits of a finished MODE_MAP call
+ * (MDFIT-PSIS v1).  Per sub-fit: num_draws points from a
+ * multivariate Student-t (nu = 4) centred on the mode with the Laplace
+ * covariance of mdfit_map_laplace (its held set and factorisation, bit for
+ * bit; a c held on 0 is drawn from the exponential of its gradient and moves
+ * the centre of the free block), each weighted by the density the sampling
+ * mode draws from -- the full beta-binomial log-pmf, the priors and the
+ * Jacobian of u = (logit q, logit A, c, log delta) -- over the proposal's.  A
+ * draw with c < 0 or A + c >= 1 is infeasible: weight 0.  The weights are
+ * Pareto-smoothed (the top M = min(S / 5, ceil(3 sqrt S)) by rank, ties by draw
+ * index, take the quantiles of the generalised Pareto fit of mdfit_nuts_loo)
+ * and normalised; the record holds the weighted means and standard deviations
+ * of q, A, c, phi and D_max = A + c, the weighted A-c correlation,
+ * significance = D_max_mean / D_max_std, the fit's shape khat, ess = 1 / sum
+ * w^2 and the number of infeasible draws.  khat above the threshold of bit 1
+ * says that the estimates cannot be trusted and the taxon needs the sampling
+ * mode.  A row is invalid -- NaN statistics, the free bits alone in flags --
+ * when q, A or phi is held or c is held elsewhere than on 0, when the Laplace
+ * row is invalid, when a log-weight is NaN or +inf, or when the draw that sets
+ * the tail's cut-off is infeasible.  A taxon with status != MDFIT_OK gets NaN
+ * statistics and flags 0.
+ *   y, N, out, status : those of the MODE_MAP call (device; read only)
+ *   num_draws  : S in [25, 1024] (else MDFIT_E_ARG): 25 is the smallest S with
+ *                a five-draw tail; at 1024 a wave takes 22,016 B of LDS, so six
+ *                blocks still share a CU's 160 KB
+ *   seed, index_base : the Philox streams are keyed by (seed, index_base +
+ *                taxon, sub-fit): a chunked or sharded run draws what one call
+ *                draws
+ *   psis       : double[n_taxa][3][MDFIT_NMAPPSIS]                 (device)
+ *   draws      : double[n_taxa][3][num_draws][6] = u[4], the raw log-weight,
+ *                the weight; NaN in an invalid row; or NULL         (device)
+ * One launch on hip_stream, one wave per taxon; no workspace, no allocation,
+ * no side stream, no host synchronisation, no atomics; capturable in a graph.
+ * n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_psis(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                   int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base,
+                   double* psis, double* draws, void* hip_stream);
+
+/*
+ * Test helper: the smoothing of mdfit_map_psis (its device function) on given
+ * log-weight series lw[n_series][S], one wave per series: the normalised
+ * weights w[n_series][S] and khat[i]; -inf is an infeasible draw; NaN for a
+ * series with a NaN or +inf or an infeasible cut-off draw.  S in [25, 1024]
+ * (else MDFIT_E_ARG); n_series at most 2^25.  Device pointers.
+ */
+int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w, double* khat,
+                       void* hip_stream);
+
 /*
  * Pointwise beta-binomial log-pmf (numpyro BetaBinomial.log_prob, used by
  * fits.py:59,67 and log_likelihood fits.py:126-133):

@@ -32,6 +32,7 @@ NLAPLACE = 8
 NNUTSDIAG = 12
 NNUTSSUMM = 16
 NNUTSLOO = 8
+NMAPPSIS = 16
 NLOOROW = 7  # rows of a PSIS-LOO record: the six sub-fits, then the comparisons
 
 # output record field order (enum mdfit_field) == fit_results numeric columns
@@ -82,6 +83,11 @@ NUTSLOO_COMPARE_FIELDS = ["n_sigma_loo", "n_sigma_loo_forward", "n_sigma_loo_rev
                           "n_bad", "reserved", "flags"]
 NUTSLOO_VALID = 1  # flags: bit 0 valid
 
+# importance-sampled posterior record (mdfit_map_psis): float64 [T][3][NMAPPSIS], rows PMD-all, -forward, -reverse
+MAPPSIS_FIELDS = ["q_mean", "A_mean", "c_mean", "phi_mean", "D_max_mean", "q_std", "A_std", "c_std", "phi_std",
+                  "D_max_std", "rho_Ac", "significance", "khat", "ess", "n_infeasible", "flags"]
+MAPPSIS_VALID, MAPPSIS_RELIABLE = 1, 2  # flags: bit 0 valid, bit 1 khat <= threshold, bits 2..5 coordinate free
+
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
     "mdfit_default_opts",
@@ -94,6 +100,8 @@ EXPORTED_SYMBOLS = [
     "mdfit_nuts_summary",
     "mdfit_nuts_loo",
     "mdfit_psis",
+    "mdfit_map_psis",
+    "mdfit_psis_weights",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
     "mdfit_hpdi68",
@@ -177,6 +185,10 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_nuts_loo.restype = ctypes.c_int
     lib.mdfit_psis.argtypes = [vp, i64, i32, vp, vp, vp]
     lib.mdfit_psis.restype = ctypes.c_int
+    lib.mdfit_map_psis.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp]
+    lib.mdfit_map_psis.restype = ctypes.c_int
+    lib.mdfit_psis_weights.argtypes = [vp, i64, i32, vp, vp, vp]
+    lib.mdfit_psis_weights.restype = ctypes.c_int
     lib.mdfit_betabinom_logpmf.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.mdfit_betabinom_logpmf.restype = ctypes.c_int
     lib.mdfit_special.argtypes = [vp, i64, vp, vp]

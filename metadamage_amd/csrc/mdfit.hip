@@ -42,6 +42,7 @@
 #include "mdfit_hpdi.h"
 #include "mdfit_host.h"
 #include "mdfit_laplace.h"
+#include "mdfit_mappsis.h"
 #include "mdfit_model.h"
 #include "mdfit_special.h"
 
@@ -2043,6 +2044,38 @@ int mdfit_map_laplace_u(const uint32_t* y, const uint32_t* N, const double* out,
   hipLaunchKernelGGL(mdfit::laplace_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave), 0,
                      (hipStream_t)hip_stream, y, N, out, status, n_taxa, lap, gh, u);
   return check_launch("laplace_kernel");
+}
+
+int mdfit_map_psis(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                   int32_t num_draws, uint64_t seed, int64_t index_base, double* psis, double* draws,
+                   void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)  // (a five-draw tail; the LDS bound)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !psis) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mp::map_psis_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), psis, draws);
+  return check_launch("map_psis_kernel");
+}
+
+int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w, double* khat, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
+  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
+  if (n_series == 0) return 0;
+  if (!lw || !w || !khat) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mp::psis_weights_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
+                     (size_t)mp::work_len((int)S) * sizeof(double), (hipStream_t)hip_stream, lw, n_series, (int)S, w,
+                     khat);
+  return check_launch("psis_weights_kernel");
 }
 
 #ifdef MDFIT_STAMP

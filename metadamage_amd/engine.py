@@ -41,6 +41,7 @@ class FitBatch:
     diag: "object" = None  # torch.float32 [T, 6, NNUTSDIAG]: the sampling diagnostics (ChunkedFitter with_diag)
     summ: "object" = None  # torch.float32 [T, 6, NNUTSSUMM]: the posterior summaries (ChunkedFitter with_summary)
     loo: "object" = None  # torch.float32 [T, 7, NNUTSLOO]: the PSIS-LOO records (ChunkedFitter with_loo)
+    psis: "object" = None  # torch.float32 [T, 3, NMAPPSIS]: the importance-sampled posteriors (ChunkedFitter with_psis)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -151,6 +152,55 @@ def map_laplace_device(ty, tN, res: FitBatch, lap=None, gh=None, stream=None, u=
     else:
         _lib.check(lib.mdfit_map_laplace(*args, _stream_handle(torch, stream)))
     return lap
+
+
+def map_psis_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, psis=None,
+                    draws=None, stream=None):
+    """Launch mdfit_map_psis on the records of a finished MAP call (asynchronous
+    on `stream`): the importance-sampled posterior of the three PMD sub-fits
+    (MDFIT-PSIS v1), float64 psis[T, 3, NMAPPSIS] (_lib.MAPPSIS_FIELDS).  The
+    Philox streams are keyed by (seed, index_base + taxon, sub-fit).  draws:
+    None, True (allocated) or a float64 tensor [T, 3, num_draws, 6] = u[4], the
+    raw log-weight, the weight.  Returns psis, or (psis, draws) when draws is
+    asked for."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S = int(ty.shape[0]), int(num_draws)
+    if psis is None:
+        psis = torch.empty((T, 3, _lib.NMAPPSIS), dtype=torch.float64, device=ty.device)
+    if draws is True:
+        draws = torch.empty((T, 3, S, 6), dtype=torch.float64, device=ty.device)
+    for name, t, n in (("psis", psis, T * 3 * _lib.NMAPPSIS), ("draws", draws, T * 3 * S * 6)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    _lib.check(lib.mdfit_map_psis(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
+                                  ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S,
+                                  int(seed), int(index_base), ctypes.c_void_p(psis.data_ptr()),
+                                  ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
+                                  _stream_handle(torch, stream)))
+    return psis if draws is None else (psis, draws)
+
+
+def psis_weights(lw, device="cuda"):
+    """(w[n, S], khat[n]) float64 host arrays of the raw log-weight series
+    lw[n, S] by the device's smoothing (MDFIT-PSIS v1, mdfit_psis_weights;
+    parity tests)."""
+    torch = _torch()
+    lib = _lib.load()
+    lw = np.array(lw, dtype=np.float64, order="C")  # (a copy: the caller's array may be read only)
+    n, S = lw.shape
+    t = torch.from_numpy(lw).to(device)
+    w = torch.empty((n, S), dtype=torch.float64, device=device)
+    khat = torch.empty(n, dtype=torch.float64, device=device)
+    _lib.check(lib.mdfit_psis_weights(ctypes.c_void_p(t.data_ptr()), n, S, ctypes.c_void_p(w.data_ptr()),
+                                      ctypes.c_void_p(khat.data_ptr()), _stream_handle(torch, None)))
+    torch.cuda.current_stream().synchronize()
+    return w.cpu().numpy(), khat.cpu().numpy()
 
 
 def nuts_diag_device(res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, diag=None, stream=None):
@@ -316,6 +366,23 @@ def _check_loo_mode(with_loo: bool, opts: _lib.MdfitOpts | None, with_laplace: b
                          "one extra block per run")
 
 
+PSIS_BYTES = 3 * _lib.NMAPPSIS * 4  # one taxon's importance-sampled posteriors on the way out: f32 [3][16]
+PSIS_DRAWS = 256  # the default number of draws per sub-fit
+
+
+def _check_psis_mode(with_psis: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
+                     with_diag: bool = False, with_summary: bool = False, with_loo: bool = False) -> None:
+    """with_psis is the MAP mode's (opts None: the default options, MAP) and the
+    run's one optional extra block."""
+    if not with_psis:
+        return
+    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
+        raise ValueError("with_psis needs MAP records (opts.mode == MODE_MAP)")
+    if with_laplace or with_diag or with_summary or with_loo:
+        raise ValueError("with_psis, with_loo, with_summary, with_diag and with_laplace are mutually exclusive: "
+                         "one extra block per run")
+
+
 def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
     """with_diag is the sampling mode's (opts None: the default options, MAP)."""
     if with_diag and (opts is None or int(opts.mode) != _lib.MODE_NUTS):
@@ -324,7 +391,7 @@ def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
 
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
                  dest_on_device: bool = False, with_laplace: bool = False, with_diag: bool = False,
-                 with_summary: bool = False, with_loo: bool = False) -> int:
+                 with_summary: bool = False, with_loo: bool = False, with_psis: bool = False) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -339,11 +406,15 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     only, and not together with with_diag or with_laplace: ValueError).
     with_loo: the PSIS-LOO records, 448 B as computed (f64) and -- unless they
     go to the caller's device buffer -- 224 B rounded to f32 (NUTS only, and the
-    run's only extra block: ValueError)."""
+    run's only extra block: ValueError).  with_psis: the importance-sampled
+    posteriors, 384 B as computed (f64) and -- unless they go to the caller's
+    device buffer -- 192 B rounded to f32 (MAP only, and the run's only extra
+    block: ValueError)."""
     C = int(C)
     _check_diag_mode(with_diag, opts)
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
+    _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
@@ -355,6 +426,8 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
         b += C * (2 * SUMM_BYTES + (0 if dest_on_device else SUMM_BYTES))
     if with_loo:
         b += C * (2 * LOO_BYTES + (0 if dest_on_device else LOO_BYTES))
+    if with_psis:
+        b += C * (2 * PSIS_BYTES + (0 if dest_on_device else PSIS_BYTES))
     return b + workspace_bytes(C, opts)
 
 
@@ -362,7 +435,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
                 dest_on_device: bool = False, with_laplace: bool = False,
                 with_diag: bool = False, with_summary: bool = False,
-                with_loo: bool = False) -> list[tuple[int, int]]:
+                with_loo: bool = False, with_psis: bool = False) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk fit in budget_bytes (None: no memory
     bound), no chunk exceeds the per-call limit (2^25 taxa) or chunk_taxa (> 0;
@@ -373,6 +446,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     _check_diag_mode(with_diag, opts)
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
+    _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -382,7 +456,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
         per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, with_laplace,  # noqa: E731
-                                              with_diag, with_summary, with_loo)
+                                              with_diag, with_summary, with_loo, with_psis)
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
         if per(cap) > budget_bytes:  # largest c with per(c) <= budget (per is monotone in c)
@@ -415,7 +489,7 @@ class _Set:
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
                  with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-                 with_loo: bool = False):
+                 with_loo: bool = False, with_psis: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -445,6 +519,11 @@ class _Set:
             self.loo64 = torch.empty((C, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.loo = torch.empty((C, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float32, device=device)
+        self.psis64 = self.psis = None
+        if with_psis:  # as mdfit_map_psis writes them, and rounded to f32 for the way out
+            self.psis64 = torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float64, device=device)
+            if not dest_on_device:
+                self.psis = torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -494,14 +573,22 @@ class ChunkedFitter:
     with_loo (NUTS only; the run's only extra block): mdfit_nuts_loo follows
     each chunk's fit on the compute stream in the same way, reading the chunk's
     device counts beside its draws, and its records, rounded to f32 there, leave
-    as f32 [T, 7, 8], 224 B per taxon (run's fourth array; dest.loo)."""
+    as f32 [T, 7, 8], 224 B per taxon (run's fourth array; dest.loo).
+
+    with_psis (MAP only; the run's only extra block): mdfit_map_psis follows
+    each chunk's fit on the compute stream with psis_draws draws per sub-fit,
+    its streams keyed by opts.seed and the chunk's global taxon index, and its
+    records, rounded to f32 there, leave as f32 [T, 3, 16], 192 B per taxon
+    (run's fourth array; dest.psis)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False,
-                 with_diag: bool = False, with_summary: bool = False, with_loo: bool = False):
+                 with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
+                 with_psis: bool = False, psis_draws: int = PSIS_DRAWS):
         _check_diag_mode(with_diag, opts)
         _check_summary_mode(with_summary, opts, with_laplace, with_diag)
         _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
+        _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
         torch = _torch()
         if with_laplace and opts is not None and int(opts.mode) != _lib.MODE_MAP:
             raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
@@ -509,18 +596,20 @@ class ChunkedFitter:
         self.with_diag = bool(with_diag)
         self.with_summary = bool(with_summary)
         self.with_loo = bool(with_loo)
+        self.with_psis = bool(with_psis)
+        self.psis_draws = int(psis_draws)
         self.chunk_cap = int(chunk_cap)
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.with_laplace,
-                          self.with_diag, self.with_summary, self.with_loo)
+                          self.with_diag, self.with_summary, self.with_loo, self.with_psis)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = self.h_lap = None
-        self.h_diag = self.h_summ = self.h_loo = None
+        self.h_diag = self.h_summ = self.h_loo = self.h_psis = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -544,6 +633,8 @@ class ChunkedFitter:
                 self.h_summ = torch.empty((cap, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float32).pin_memory()
             if self.with_loo:
                 self.h_loo = torch.empty((cap, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float32).pin_memory()
+            if self.with_psis:
+                self.h_psis = torch.empty((cap, 3, _lib.NMAPPSIS), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -582,6 +673,9 @@ class ChunkedFitter:
         _check_loo_mode(self.with_loo, o0)
         if self.with_loo and dest is not None and dest.loo is None:
             raise ValueError("with_loo: dest.loo (float32 [T, 7, NNUTSLOO]) required")
+        _check_psis_mode(self.with_psis, o0)
+        if self.with_psis and dest is not None and dest.psis is None:
+            raise ValueError("with_psis: dest.psis (float32 [T, 3, NMAPPSIS]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -652,6 +746,13 @@ class ChunkedFitter:
                 loo32 = dest.loo[lo:hi] if dest is not None else st.loo[:n]
                 with torch.cuda.stream(comp):
                     loo32.copy_(st.loo64[:n])
+            psis32 = None
+            if self.with_psis:  # the records are final: their posteriors, rounded to f32 in place
+                map_psis_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
+                                psis=st.psis64[:n], stream=comp)
+                psis32 = dest.psis[lo:hi] if dest is not None else st.psis[:n]
+                with torch.cuda.stream(comp):
+                    psis32.copy_(st.psis64[:n])
             ev_done = torch.cuda.Event()
             ev_done.record(comp)
             done.append(ev_done)
@@ -670,6 +771,8 @@ class ChunkedFitter:
                         self.h_summ[lo:hi].copy_(summ32, non_blocking=True)
                     if loo32 is not None:
                         self.h_loo[lo:hi].copy_(loo32, non_blocking=True)
+                    if psis32 is not None:
+                        self.h_psis[lo:hi].copy_(psis32, non_blocking=True)
                 last_d2h = cp
         end = torch.cuda.Event()
         end.record(cp if last_d2h is not None else comp)
@@ -680,7 +783,8 @@ class ChunkedFitter:
             pinned: PinnedPack | None = None, chunks=None):
         """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status -- and,
         with_laplace, lap[:, 3, 8] f32, or, with_diag, diag[:, 6, 12] f32, or,
-        with_summary, summ[:, 6, 16] f32, or, with_loo, loo[:, 7, 8] f32) of the
+        with_summary, summ[:, 6, 16] f32, or, with_loo, loo[:, 7, 8] f32, or,
+        with_psis, psis[:, 3, 16] f32) of the
         pinned buffers (valid until the next run).  pinned: y, N, mm are that
         PinnedPack's views.  chunks: the split (default plan_chunks at this
         staging's chunk_cap)."""
@@ -702,6 +806,8 @@ class ChunkedFitter:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_summ[:T].numpy()
         if self.with_loo:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_loo[:T].numpy()
+        if self.with_psis:
+            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_psis[:T].numpy()
         return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy()
 
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
@@ -777,7 +883,7 @@ _STAGING_LOCK = __import__("threading").Lock()
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
             dest_on_device: bool = False, budget_bytes: int | None = None,
             with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-            with_loo: bool = False) -> ChunkedFitter:
+            with_loo: bool = False, with_psis: bool = False, psis_draws: int = PSIS_DRAWS) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind and sampler length): the
     multi-file pipeline fits one file after another, and pinned + device
@@ -794,7 +900,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     o = opts if opts is not None else _lib.default_opts()
     env_chunk = int(os.environ.get("MDFIT_CHUNK_TAXA", "0") or 0)
     key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
-           bool(with_laplace), bool(with_diag), bool(with_summary), bool(with_loo))
+           bool(with_laplace), bool(with_diag), bool(with_summary), bool(with_loo),
+           int(psis_draws) if with_psis else 0)
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -812,11 +919,11 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
                       with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                      with_loo=with_loo)[0]
+                      with_loo=with_loo, with_psis=with_psis)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
                        with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                       with_loo=with_loo)
+                       with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -825,14 +932,17 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, laplace: bool = False, diag: bool = False,
-                   summary: bool = False, loo: bool = False):
+                   summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = PSIS_DRAWS):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
     the PMD sub-fits (_lib.LAPLACE_FIELDS), or, with diag (NUTS only), diag[T, 6,
     12] f32, the sampling diagnostics of the six sub-fits (_lib.NUTSDIAG_FIELDS), or, with summary
     (NUTS only; at most one of the three), summ[T, 6, 16] f32, their posterior
     summaries (_lib.NUTSSUMM_FIELDS), or, with loo (NUTS only; the only one),
-    loo[T, 7, 8] f32, the PSIS-LOO records (_lib.NUTSLOO_FIELDS) --, chunked
+    loo[T, 7, 8] f32, the PSIS-LOO records (_lib.NUTSLOO_FIELDS), or, with psis
+    (MAP only; the only one), psis[T, 3, 16] f32, the importance-sampled
+    posteriors of the PMD sub-fits from psis_draws draws each
+    (_lib.MAPPSIS_FIELDS) --, chunked
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
@@ -840,14 +950,14 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     T = int(y.shape[0])
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace, with_diag=diag,
-                     with_summary=summary, with_loo=loo)
+                     with_summary=summary, with_loo=loo, with_psis=psis, psis_draws=psis_draws)
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
-        extra = got[3].copy() if laplace or diag or summary or loo else None
+        extra = got[3].copy() if laplace or diag or summary or loo or psis else None
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
-    if laplace or diag or summary or loo:
+    if laplace or diag or summary or loo or psis:
         return out, pred, status, extra
     return out, pred, status
 

@@ -90,6 +90,22 @@ NUTS_LOO_COLUMNS = [name for name, _, _ in _NUTS_LOO_PICKS]
 # ... then uint32 pareto_k_bad (the points of the six sub-fits with khat above the
 # threshold: row 6's count) and nuts_loo_valid (row 6's valid bit: all six rows valid)
 NUTS_LOO_UINT_COLUMNS = ["pareto_k_bad", "nuts_loo_valid"]
+# "map-psis": the importance-sampled posterior appended after shortname
+# (DESIGN.md §3.8), float32 -- (column, row of the record: 0 PMD-all, 1 forward,
+# 2 reverse, its field).  The first eleven are the LAPLACE_COLUMNS' names in
+# their order, as in "nuts-summary"
+_MAP_PSIS_PICKS = (
+    [(name, row, f) for name, row, f in LAPLACE_COLUMNS]
+    + [("D_max_posterior_mean", 0, "D_max_mean"), ("q_posterior_mean", 0, "q_mean"),
+       ("concentration_posterior_mean", 0, "phi_mean"),
+       ("D_max_posterior_mean_forward", 1, "D_max_mean"), ("D_max_posterior_mean_reverse", 2, "D_max_mean"),
+       ("pareto_k", 0, "khat"), ("pareto_k_forward", 1, "khat"), ("pareto_k_reverse", 2, "khat"),
+       ("psis_ess", 0, "ess")]
+)
+MAP_PSIS_COLUMNS = [name for name, _, _ in _MAP_PSIS_PICKS]
+# ... then uint32 map_psis_valid (all three rows valid) and map_psis_reliable
+# (valid, and all three khat at or below the threshold)
+MAP_PSIS_UINT_COLUMNS = ["map_psis_valid", "map_psis_reliable"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -278,7 +294,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
-               summary: bool = False, loo: bool = False):
+               summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -288,8 +304,10 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     12] f32 (flags: bit 0 valid, above it the chain's divergence count).  summary
     (NUTS): mdfit_nuts_summary follows the fit and the fourth array is the
     posterior summaries summ[T, 6, 16] f32.  loo (NUTS): mdfit_nuts_loo follows
-    the fit and the fourth array is the PSIS-LOO records loo[T, 7, 8] f32.  At
-    most one of the four."""
+    the fit and the fourth array is the PSIS-LOO records loo[T, 7, 8] f32.
+    psis (MAP): mdfit_map_psis follows the fit with psis_draws draws per sub-fit
+    and the fourth array is the importance-sampled posteriors psis[T, 3, 16]
+    f32.  At most one of the five."""
     import torch
 
     from . import engine
@@ -313,17 +331,17 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     if not grouped:
         try:
             return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
-                                         summary=summary, loo=loo)
+                                         summary=summary, loo=loo, psis=psis, psis_draws=psis_draws)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo)
+        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws)
     finally:
         p.release_pinned()
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
-                 summary: bool = False, loo: bool = False):
+                 summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256):
     import torch
 
     from . import engine
@@ -334,19 +352,22 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts = _lib.MdfitOpts.from_buffer_copy(opts)
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
-    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo)
+    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
+                        with_psis=psis)
     if hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
         # records written in place into the gather buffers
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
-                                with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo)
+                                with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
+                                with_psis=psis, psis_draws=psis_draws)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                                                lap=rec.lap[: hi - lo] if laplace else None,
                                                diag=rec.diag[: hi - lo] if diag else None,
                                                summ=rec.summ[: hi - lo] if summary else None,
-                                               loo=rec.loo[: hi - lo] if loo else None))
+                                               loo=rec.loo[: hi - lo] if loo else None,
+                                               psis=rec.psis[: hi - lo] if psis else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -355,7 +376,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     if rank != 0:
         return None
     return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
-                           with_loo=loo)
+                           with_loo=loo, with_psis=psis)
 
 
 # --------------------------------------------------------------------------
@@ -411,7 +432,8 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
     return cols
 
 
-def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None) -> pd.DataFrame:
+def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
+                        psis=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -423,7 +445,10 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     "nuts-summary" run): the NUTS_SUMMARY_COLUMNS follow as float32, then
     nuts_summary_valid (uint32: the PMD rows 0, 2 and 3 all valid).  loo (the
     PSIS-LOO records [T, 7, 8] of a "nuts-loo" run): the NUTS_LOO_COLUMNS follow
-    as float32, then pareto_k_bad and nuts_loo_valid (uint32)."""
+    as float32, then pareto_k_bad and nuts_loo_valid (uint32).  psis (the
+    importance-sampled posteriors [T, 3, 16] of a "map-psis" run): the
+    MAP_PSIS_COLUMNS follow as float32, then map_psis_valid and
+    map_psis_reliable (uint32)."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -473,6 +498,15 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         flags = np.nan_to_num(kl[:, 6, cmp_("flags")]).astype(np.int64)
         data["nuts_loo_valid"] = ((flags & _lib.NUTSLOO_VALID) != 0).astype(np.uint32)
         columns += NUTS_LOO_COLUMNS + NUTS_LOO_UINT_COLUMNS
+    if psis is not None:
+        kp = np.asarray(psis) if keep is None else np.asarray(psis)[keep]
+        for name, row, field in _MAP_PSIS_PICKS:
+            data[name] = np.ascontiguousarray(kp[:, row, _lib.MAPPSIS_FIELDS.index(field)], dtype=np.float32)
+        flags = np.nan_to_num(kp[:, :, _lib.MAPPSIS_FIELDS.index("flags")]).astype(np.int64)
+        valid = ((flags & _lib.MAPPSIS_VALID) != 0).all(axis=1)
+        data["map_psis_valid"] = valid.astype(np.uint32)
+        data["map_psis_reliable"] = (valid & ((flags & _lib.MAPPSIS_RELIABLE) != 0).all(axis=1)).astype(np.uint32)
+        columns += MAP_PSIS_COLUMNS + MAP_PSIS_UINT_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
@@ -499,7 +533,8 @@ def make_opts(cfg, mcmc_kwargs=None):
     "nuts-diag" (the same call; wants_diag adds the sampling diagnostics),
     "nuts-summary" (the same call; wants_summary adds the posterior summaries),
     "nuts-loo" (the same call; wants_loo adds the PSIS-LOO model comparison), "map"
-    or "map-laplace" (the MAP fit; wants_laplace adds the standard errors)."""
+    "map-laplace" (the MAP fit; wants_laplace adds the standard errors) or
+    "map-psis" (the MAP fit; wants_psis adds the importance-sampled posterior)."""
     inference = getattr(cfg, "inference", "nuts")
     if mode_of(inference) == _lib.MODE_MAP:
         return _lib.default_opts(mode=_lib.MODE_MAP)
@@ -512,12 +547,13 @@ def mode_of(inference: str) -> int:
     """The engine mode of an --inference value: "nuts", "nuts-diag",
     "nuts-summary" and "nuts-loo" (the sampler; wants_diag adds mdfit_nuts_diag,
     wants_summary mdfit_nuts_summary, wants_loo mdfit_nuts_loo) or "map" and
-    "map-laplace"."""
-    if inference in ("map", "map-laplace"):
+    "map-laplace" and "map-psis"."""
+    if inference in ("map", "map-laplace", "map-psis"):
         return _lib.MODE_MAP
     if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo"):
         return _lib.MODE_NUTS
-    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'nuts-diag', 'nuts-summary' or 'nuts-loo', "
+    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'nuts-diag', 'nuts-summary' or "
+                     "'nuts-loo', "
                      f"got {inference!r}")
 
 
@@ -541,6 +577,16 @@ def wants_laplace(cfg) -> bool:
     return getattr(cfg, "inference", "nuts") == "map-laplace"
 
 
+def wants_psis(cfg) -> bool:
+    """cfg.inference "map-psis": the MAP fit followed by mdfit_map_psis."""
+    return getattr(cfg, "inference", "nuts") == "map-psis"
+
+
+def psis_draws_of(cfg) -> int:
+    """The draws per sub-fit of a "map-psis" run (cfg.psis_draws, default 256)."""
+    return int(getattr(cfg, "psis_draws", 256) or 256)
+
+
 def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     """fits.py:709-730: (df_fit_results, df_fit_predictions) for every taxon of
     df_counts, in df_counts order, by the sampler (cfg.inference "nuts", the
@@ -550,7 +596,8 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
         opts = make_opts(cfg, mcmc_kwargs)
     p = pack_counts(df_counts, cfg)
     res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
-                     summary=wants_summary(cfg), loo=wants_loo(cfg))
+                     summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
+                     psis_draws=psis_draws_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
@@ -558,10 +605,11 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     diag = rest[0] if rest and wants_diag(cfg) else None
     summ = rest[0] if rest and wants_summary(cfg) else None
     loo = rest[0] if rest and wants_loo(cfg) else None
+    psis = rest[0] if rest and wants_psis(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo),
+    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis),
             make_df_fit_predictions(p, pred, keep, cfg))
 
 
@@ -609,7 +657,7 @@ def _rank() -> int:
 
 
 CACHE_KEYS = ["min_alignments", "min_y_sum", "substitution_bases_forward", "substitution_bases_reverse",
-              "N_fits", "shortname", "filename", "inference"]
+              "N_fits", "shortname", "filename", "inference", "psis_draws"]
 
 
 def _cache_hit(cfg) -> bool:
@@ -658,7 +706,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
                      laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
-                     loo=wants_loo(cfg))
+                     loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
@@ -666,6 +714,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     diag = rest[0] if rest and wants_diag(cfg) else None
     summ = rest[0] if rest and wants_summary(cfg) else None
     loo = rest[0] if rest and wants_loo(cfg) else None
+    psis = rest[0] if rest and wants_psis(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -673,7 +722,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     def finish():
         from .counts import _save
 
-        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo)
+        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
