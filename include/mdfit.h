@@ -425,6 +425,39 @@ int mdfit_betabinom_logpmf(const double* y, const double* N, const double* alpha
  */
 int mdfit_special(const double* x, int64_t n, double* out3, void* hip_stream);
 
+/* The device primitives of csrc/mdfit_special.h that mdfit_primitive evaluates. */
+enum mdfit_primitive_id {
+  MDFIT_P_RCP = 1,           /* rcp(x): reciprocal, two Newton steps */
+  MDFIT_P_RCP1 = 2,          /* rcp1(x): one Newton step */
+  MDFIT_P_FLOG = 3,          /* flog(x) */
+  MDFIT_P_FLOG_T = 4,        /* flog_t<false>(x): table log, normal x > 0 */
+  MDFIT_P_FLOG_T_ZERO = 5,   /* flog_t<true>(x): also 0 and subnormals */
+  MDFIT_P_FLOG1P = 6,        /* flog1p(x) */
+  MDFIT_P_FEXP = 7,          /* fexp(x) */
+  MDFIT_P_FEXP_T = 8,        /* fexp_t(x): table exp */
+  MDFIT_P_LG3_L = 9,         /* lg3<true, false>(x).l: lnGamma, the accurate form */
+  MDFIT_P_LG3_P = 10,        /* lg3<true, false>(x).p: digamma */
+  MDFIT_P_LG3_Q = 11,        /* lg3<true, false>(x).q: trigamma */
+  MDFIT_P_LG3_FAST_L = 12,   /* lg3<false, true>(x).l: the sampler's fast form */
+  MDFIT_P_LG3_FAST_P = 13,   /* lg3<false, true>(x).p */
+  MDFIT_P_STIRLING_REM = 14, /* stirling_rem(x), x >= 10 */
+  MDFIT_P_LGDIFF = 15,       /* lgdiff(x, x2) = lnGamma(x + x2) - lnGamma(x) */
+  MDFIT_P_LRISE = 16,        /* lrise(x, x2) = ln((x2)_x / x!) */
+  MDFIT_P_COUNT = 17
+};
+
+/*
+ * Test helper: out[i] = the device primitive `which` (enum mdfit_primitive_id)
+ * at x[i], or at (x[i], x2[i]) for the two binary ones; one thread per element,
+ * one launch on hip_stream.  Device pointers; x2 may be NULL for a unary
+ * primitive.  which outside [1, MDFIT_P_COUNT), n < 0 or above 2^31, or a NULL
+ * x / out (x2 for a binary primitive) with n > 0: MDFIT_E_ARG before any device call;
+ * n == 0 returns 0.  tests/test_gpu_special.py holds every primitive to its
+ * derived error bar with it.
+ */
+int mdfit_primitive(int32_t which, const double* x, const double* x2, int64_t n, double* out,
+                    void* hip_stream);
+
 /*
  * Test helper: fills every CU's LDS with NaN (one launch of blocks holding the
  * largest LDS a block may take, several per CU), so that a kernel launched after

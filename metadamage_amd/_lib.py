@@ -104,6 +104,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_psis_weights",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
+    "mdfit_primitive",
     "mdfit_hpdi68",
     "mdfit_peak_probe",
     "mdfit_nuts_peak_probe",
@@ -193,6 +194,8 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_betabinom_logpmf.restype = ctypes.c_int
     lib.mdfit_special.argtypes = [vp, i64, vp, vp]
     lib.mdfit_special.restype = ctypes.c_int
+    lib.mdfit_primitive.argtypes = [i32, vp, vp, i64, vp, vp]
+    lib.mdfit_primitive.restype = ctypes.c_int
     lib.mdfit_hpdi68.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.mdfit_hpdi68.restype = ctypes.c_int
     lib.mdfit_peak_probe.argtypes = [i64, i32, vp, vp]

@@ -44,6 +44,7 @@
 #include "mdfit_laplace.h"
 #include "mdfit_mappsis.h"
 #include "mdfit_model.h"
+#include "mdfit_primitive.h"
 #include "mdfit_special.h"
 
 #ifdef MDFIT_DEV_HPTIME
@@ -1451,6 +1452,14 @@ __global__ void special_kernel(const double* __restrict__ x, int64_t n, double* 
   o[3 * i + 2] = r.q;
 }
 
+// one primitive of mdfit_special.h per element (tests/test_gpu_special.py)
+__global__ void primitive_kernel(int which, const double* __restrict__ x, const double* __restrict__ x2,
+                                 int64_t n, double* __restrict__ o) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  o[i] = primitive_eval(which, x[i], x2 != nullptr ? x2[i] : 0.0);
+}
+
 __global__ void betabinom_kernel(const double* __restrict__ y, const double* __restrict__ N,
                                  const double* __restrict__ a, const double* __restrict__ b,
                                  int64_t n, double* __restrict__ o, double* __restrict__ g) {
@@ -1987,6 +1996,19 @@ int mdfit_special(const double* x, int64_t n, double* out3, void* hip_stream) {
   hipLaunchKernelGGL(mdfit::special_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream,
                      x, n, out3);
   return check_launch("special_kernel");
+}
+
+int mdfit_primitive(int32_t which, const double* x, const double* x2, int64_t n, double* out,
+                    void* hip_stream) {
+  if (which < 1 || which >= MDFIT_P_COUNT) return set_err(MDFIT_E_ARG, "which: not a primitive");
+  const bool binary = which == MDFIT_P_LGDIFF || which == MDFIT_P_LRISE;
+  if (n < 0 || n > ((int64_t)1 << 31) || (n > 0 && (!x || !out || (binary && !x2))))
+    return set_err(MDFIT_E_ARG, "bad arguments");
+  if (n == 0) return 0;
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(mdfit::primitive_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream,
+                     (int)which, x, x2, n, out);
+  return check_launch("primitive_kernel");
 }
 
 int mdfit_poison_lds(void* hip_stream) {

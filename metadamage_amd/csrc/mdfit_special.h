@@ -13,14 +13,23 @@
 //            more reciprocal instead of ten of each;
 //   x >= 10: Stirling / asymptotic series to O(x^-15).
 //
-// Accuracy (vs scipy, tests/test_special_*): |err| <= ~4e-15 * max(1, |f|).
+// Accuracy (every primitive here is held pointwise to a
+// derived bar against 300-bit mpmath by tests/test_special_host.py -- a host
+// build of this header -- and tests/test_gpu_special.py -- the kernel, through
+// mdfit_primitive).  From 10 the three are relative: lnGamma <= 1e-15 |f|, psi
+// and psi1 <= 2.5 ulp (psi1 + B16 / x^17, its series' truncation: 3 ulp at 10).
+// Below 10 they are ABSOLUTE near the shift, not relative to f: lnGamma(x + 10)
+// ~ 13..40 and ln P cancel, so |err| <= 2.5e-14 + 4.5e-16 |f| for lnGamma (1e-14
+// on the host build on [1, 3], where f ~ 0), 1.4e-14 max(1, |f|) for psi and 6.1e-14
+// max(1, |f|) for psi1 (6.8e-15 on the host build).  Measured on gfx950 (2026-10-20, the
+// fixture's 2403 points): 0.48, 0.47 and 0.62 of those bars.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 namespace mdfit {
 
-// FP64 reciprocal: v_rcp_f64 + two Newton steps (faithful, no IEEE div sequence).
+// FP64 reciprocal: v_rcp_f64 + two Newton steps (faithful, <= 1 ulp; no IEEE div sequence).
 // Measured on gfx950 (tools/micro/rcp_accuracy.hip, 2^28 log-uniform x):
 // v_rcp_f64 alone is off by up to 2.1e8 ulp (~2^-25), one Newton step 10 ulp,
 // two 0 (the correctly rounded 1/x).
@@ -38,7 +47,8 @@ __device__ __forceinline__ double rcp1(double x) {
   return fma(fma(-x, r, 1.0), r, r);
 }
 
-// Natural log, <= ~1 ulp (the classic reduction x = 2^e (1+f), 1+f in
+// Natural log, <= 1 ulp, subnormal arguments included (0.56 ulp on the
+// fixture, gfx950, 2026-10-20; 0.70 over 1e5 points on the host build) (the classic reduction x = 2^e (1+f), 1+f in
 // [sqrt(1/2), sqrt(2)), log(1+f) = f - hfsq + s (hfsq + R(s^2)), s = f/(2+f),
 // R a degree-7 minimax polynomial in s^2 -- Cody & Waite / the fdlibm scheme).
 // 0 -> -inf, +inf -> +inf, negative / NaN -> NaN.
@@ -77,7 +87,10 @@ __device__ __forceinline__ double flog(double x) {
 namespace mdfit {
 
 // Natural log by table (the lnGamma family's logs: arguments >= 10, and the
-// shift products), ~1 ulp for x away from 1: x = 2^e m, m in [1, 2), j = the
+// shift products), <= 1 ulp for x >= 2 or x <= 0.5 (0.72 ulp on the fixture's
+// table-interval edges, gfx950, 2026-10-20, the host build's bits at every
+// point; the host build reaches 0.999 ulp in [0.25, 0.5) and [2, 4)) and
+// <= 2.3e-16 ABSOLUTE on (0.5, 2): x = 2^e m, m in [1, 2), j = the
 // top 8 mantissa bits, c_j = 1 + (2j+1)/512 the centre of its interval
 // (mdfit_logtab.h: 1/c_j and ln c_j, one 16-B load); r = (m - c_j) / c_j with
 // m - c_j exact and |r| <= 2^-9, ln(1 + r) by a degree-6 polynomial
@@ -119,7 +132,9 @@ __device__ __forceinline__ double flog_t(double x) {
   return kZero ? (x > 0.0 ? y : -INFINITY) : y;
 }
 
-// log(1 + x), x > -1: Goldberg's correction log(u) * x / (u - 1), u = 1 + x.
+// log(1 + x), x > -1: Goldberg's correction log(u) * x / (u - 1), u = 1 + x;
+// <= 3 ulp (flog 1, rcp 1, two multiplies half each; 2.6 seen over 1e5 points on
+// the host build); x itself where 1 + x rounds to 1.
 __device__ __forceinline__ double flog1p(double x) {
 #pragma clang fp contract(off)
   const double u = 1.0 + x;
@@ -127,9 +142,15 @@ __device__ __forceinline__ double flog1p(double x) {
   return um1 == 0.0 ? x : flog(u) * (x * rcp(um1));
 }
 
-// exp(x), ~1 ulp: x = n ln2 + r (Cody-Waite, |r| <= ln2/2), e^r by a degree-12
-// Taylor polynomial (|error| < 2e-17 on that range), 2^n by ldexp.  Saturates
-// to 0 / +inf outside [-745, 709.8]; NaN passes through.
+// exp(x), <= 2.5 ulp: x = n ln2 + r (Cody-Waite, |r| <= ln2/2), e^r by a
+// degree-12 Taylor polynomial, 2^n by ldexp.  The polynomial stops at r^12/12!:
+// at |r| = ln2/2 the truncation is r^13/13! = 1.7e-16, 1.53 ulp of a result in
+// [0.5, 1); with the last Horner step's rounding and what the steps before it
+// pass on, 2.5 ulp (2.29 seen over 1e5 points on the host build, 2.04 on the
+// fixture on gfx950, 2026-10-20).  A subnormal result: the larger of that and
+// 1.5 of the subnormal spacing.  Its bits are pinned by the MAP and HPDI
+// records: do not change them.  Saturates to 0 / +inf outside [-745.2, 709.8];
+// NaN passes through.
 __device__ __forceinline__ double fexp(double x) {
   constexpr double kLog2e = 1.4426950408889634074;
   constexpr double kLn2Hi = 6.93147180369123816490e-01;
@@ -153,16 +174,23 @@ __device__ __forceinline__ double fexp(double x) {
   return x < -745.2 ? 0.0 : (x > 709.8 ? INFINITY : y);
 }
 
-// exp(x) by table, ~1 ulp: x = (256 m + j) ln2 / 256 + r, |r| <= ln2 / 512,
+// exp(x) by table, <= 1.5 ulp (the table entry's rounding and the final fma's
+// are half an ulp each, the polynomial's the rest; 0.98 ulp on the fixture,
+// gfx950, 2026-10-20, the host build's bits at every point): x = (256 m + j) ln2 / 256 + r, |r| <= ln2 / 512,
 // e^x = 2^m * 2^(j/256) * e^r with 2^(j/256) from mdfit_exptab.h (rounded
 // binary64) and e^r = 1 + r + r^2 (1/2 + r (1/6 + r (1/24 + r / 120)))
 // (truncation < 2^-66).  ln2_hi / 256 times the integer k is exact for |k| <
 // 2^21.  ~20 VALU and one table load against the library exp's ~40.
+// ki is clamped to +-1100 * 256 (as fexp's n), beyond every k of the range
+// that is not saturated (|k| <= 275,226), so ki >> 8 reaches the subnormal
+// exponents and ki & 255 is k's own table index: on the tail [-745.2, -709.78)
+// the result is the subnormal exponential, within 1.5 of the subnormal
+// spacing (the value's error and ldexp's rounding).
 // Saturates to 0 / +inf outside [-745.2, 709.78]; NaN passes through.
 __device__ __forceinline__ double fexp_t(double x) {
 #pragma clang fp contract(off)
   const double k = rint(x * 369.32986822047682);
-  const int ki = (int)fmax(fmin(k, 262144.0), -262144.0);
+  const int ki = (int)fmax(fmin(k, 281600.0), -281600.0);
   const double r = fma(-k, 1.90821492927058770002e-10 / 256.0,
                        fma(-k, 6.93147180369123816490e-01 / 256.0, x));
   double q = fma(r, 1.0 / 120.0, 1.0 / 24.0);
@@ -248,7 +276,8 @@ __device__ __forceinline__ LG3 lg3(double x) {
 __device__ __forceinline__ double lgam(double x) { return lg3<false>(x).l; }
 
 // Stirling remainder lnGamma(z) - [(z - 1/2) ln z - z + ln(2 pi)/2], z >= 10
-// (the series of lg3, O(z^-15))
+// (the series of lg3, O(z^-15)): <= 4 ulp of itself + 3617 / (122400 z^15), the
+// first term left out (3e-17 at 10: 16 ulp of the remainder, 0.002 of lnGamma)
 __device__ __forceinline__ double stirling_rem(double z) {
 #pragma clang fp contract(off)
   const double r = rcp(z), r2 = r * r;

@@ -974,6 +974,23 @@ def special(x, device="cuda"):
     return o.cpu().numpy()
 
 
+def primitive(which, x, x2=None, device="cuda"):
+    """The device primitive `which` (enum mdfit_primitive_id: rcp, flog, fexp_t,
+    lg3, lrise, ...) of csrc/mdfit_special.h at x, or at (x, x2) (parity tests)."""
+    torch = _torch()
+    lib = _lib.load()
+    tx = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64).ravel(), device=device)
+    t2 = None if x2 is None else torch.as_tensor(np.ascontiguousarray(x2, dtype=np.float64).ravel(), device=device)
+    if t2 is not None and t2.numel() != tx.numel():
+        raise ValueError("x and x2 differ in size")
+    o = torch.empty(tx.numel(), dtype=torch.float64, device=device)
+    _lib.check(lib.mdfit_primitive(int(which), ctypes.c_void_p(tx.data_ptr()),
+                                   None if t2 is None else ctypes.c_void_p(t2.data_ptr()), tx.numel(),
+                                   ctypes.c_void_p(o.data_ptr()), _stream_handle(torch)))
+    torch.cuda.current_stream().synchronize()
+    return o.cpu().numpy()
+
+
 def betabinom_logpmf(y, N, a, b, device="cuda"):
     """Pointwise beta-binomial log-pmf and (d/dalpha, d/dbeta) on the device."""
     torch = _torch()

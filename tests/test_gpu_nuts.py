@@ -64,6 +64,35 @@ def test_potential_matches_oracle(nuts_engine, oracle_lib):
         assert np.abs(g[k] - go).max() <= 1e-9 * max(1.0, np.abs(go).max()), (k, g[k], go)
 
 
+def test_potential_at_the_edges(nuts_engine):
+    """mdfit_nuts_potential where test_potential_matches_oracle's typical data
+    and v in [-2, 2] do not reach: N = 4e9 at every position, ragged N = 0,
+    y = N, y = 0 and N = 1 rows crossed with logit q, A, c in {-12, 0, 6}
+    (A + c < 1) and log delta in {-20, 0, 7, 12}, both models, and one
+    infeasible item -- against a 90-digit mpmath restatement of the oracle's
+    nuts_potential (tests/golden/make_golden_primitives.py), at bars built from
+    the fast lnGamma's and psi's (tests/special_cases.py)
+    on the magnitudes of the summed terms.  test_special_host.py holds the
+    oracle to half these bars against the same reference."""
+    from tests import special_cases as sc
+
+    p = sc.load_fixture()["pot"]
+    U, g = nuts_engine.nuts_potential(p["model"], p["subset"], p["y"], p["N"], p["v"])
+    bad = np.isinf(p["U"])
+    assert bad.sum() == 1 and (U[bad] == np.inf).all() and (g[bad] == 0).all()
+    ok = ~bad
+    assert np.isfinite(U[ok]).all() and np.isfinite(g[ok]).all()
+    ru = np.abs(U[ok] - p["U"][ok]) / (sc.POT_C_U * p["U_mag"][ok] + sc.POT_ABS)
+    rg = np.abs(g[ok] - p["g"][ok]) / (sc.POT_C_G * p["g_mag"][ok] + sc.POT_ABS)
+    print(f"potential at the edges: worst error {ru.max():.3f} (U), {rg.max():.3f} (gradient) of the bar, "
+          f"items {np.flatnonzero(ok)[ru.argmax()]}, {np.flatnonzero(ok)[rg.max(1).argmax()]}")
+    assert (ru <= 1.0).all(), (np.flatnonzero(ok)[ru > 1.0], ru.max())
+    assert (rg <= 1.0).all(), (np.flatnonzero(ok)[(rg > 1.0).any(1)], rg.max())
+    # model_null has no A, c: exactly zero slope
+    null = ok & (p["model"] == 1)
+    assert (g[null][:, 1:3] == 0).all()
+
+
 def test_short_chains_follow_the_oracle_draw_for_draw(nuts_engine, oracle_lib):
     from metadamage_amd.synthetic import generate
 
