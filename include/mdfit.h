@@ -341,6 +341,48 @@ int mdfit_nuts_loo(const uint32_t* y, const uint32_t* N, const void* workspace, 
                    void* hip_stream);
 
 /*
+ * Test helper: the record assembly of a MODE_NUTS call (its post kernel, the
+ * same source lines as the product's launch) alone, on draws and chain
+ * diagnostics the caller chose.  What mdfit_fit_batch's second kernel does
+ * after the chains: the posterior means, waic_i per sub-fit and point, n_sigma
+ * x3 and asymmetry, the predictive median and 68 % HPDI, the sums and the
+ * noise.  tests/test_gpu_nuts_post.py pins it on crafted draws.
+ *   y, N, mm  : as for mdfit_fit_batch (device; read only); mm may be NULL
+ *   opts      : mode MDFIT_MODE_NUTS, num_samples in [2, 4096] (else
+ *               MDFIT_E_ARG); seed and index_base key the predictive streams
+ *   workspace : mdfit_workspace_bytes() bytes whose draws
+ *               double[n_taxa][6][num_samples][4] behind the first 256 bytes
+ *               the caller wrote (device; read only)
+ *   out       : double[n_taxa][MDFIT_NOUT]; on entry the chain diag slots 4..7
+ *               of each sub-fit (MDFIT_F_DIAG + 8k + 4..7: step, leapfrogs,
+ *               status, divergences) as the chains would have left them, the
+ *               rest zero (as mdfit_fit_batch clears it); on return the
+ *               record                                            (device)
+ *   pred      : float[n_taxa][MDFIT_NPRED][30], or NULL           (device)
+ *   status    : int32[n_taxa]                                     (device)
+ * Two taps of what the kernel forms on the way, each NULL or:
+ *   waic      : double[n_taxa][6][30], waic_i of sub-fit k at column i; NaN
+ *               where the kernel forms none (columns outside a forward /
+ *               reverse sub-fit, a taxon with y > N or a failed chain)
+ *   counts    : uint32[n_taxa][32][num_samples], the unsorted predictive
+ *               counts of job j: 0..29 the columns under the PMD-all chain, 30
+ *               and 31 column 0 under the forward and the reverse PMD chain;
+ *               0xFFFFFFFF where the draw was no count in [0, N] and in a job
+ *               that was not run
+ *   count_flags : uint8[n_taxa][32] per job: 0 every draw a count, 1 some
+ *               draw was none (the job's median and HPDI are NaN), 2 skipped
+ *               for N = 0, 0xFF not reached (y > N or a failed chain); tells
+ *               0xFFFFFFFF the count (N = 4294967295) from the marker
+ * The taps are first filled with 0xFF bytes on hip_stream, then one launch,
+ * one wave per taxon; no allocation, no host synchronisation.  n_taxa: at most
+ * 2^25 per call.
+ */
+int mdfit_nuts_post(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa,
+                    const mdfit_opts* opts, const void* workspace, double* out, float* pred,
+                    int32_t* status, double* waic, uint32_t* counts, uint8_t* count_flags,
+                    void* hip_stream);
+
+/*
  * Test helper: the estimator of mdfit_nuts_loo (its device function) on given
  * pointwise log-likelihood series ll[n_series][S], one wave per series:
  * elpd[i] and khat[i]; NaN for a series with a value that is not finite.  S in

@@ -99,6 +99,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_nuts_diag",
     "mdfit_nuts_summary",
     "mdfit_nuts_loo",
+    "mdfit_nuts_post",
     "mdfit_psis",
     "mdfit_map_psis",
     "mdfit_psis_weights",
@@ -184,6 +185,8 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_nuts_summary.restype = ctypes.c_int
     lib.mdfit_nuts_loo.argtypes = [vp, vp, vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp, vp]
     lib.mdfit_nuts_loo.restype = ctypes.c_int
+    lib.mdfit_nuts_post.argtypes = [vp, vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mdfit_nuts_post.restype = ctypes.c_int
     lib.mdfit_psis.argtypes = [vp, i64, i32, vp, vp, vp]
     lib.mdfit_psis.restype = ctypes.c_int
     lib.mdfit_map_psis.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp]

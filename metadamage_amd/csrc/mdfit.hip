@@ -2154,6 +2154,21 @@ int mdfit_nuts_loo(const uint32_t* y, const uint32_t* N, const void* workspace, 
   return mdfit::nuts::loo(y, N, workspace, out, n_taxa, *opts, loo, pointwise, (hipStream_t)hip_stream);
 }
 
+int mdfit_nuts_post(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts* opts,
+                    const void* workspace, double* out, float* pred, int32_t* status, double* waic, uint32_t* counts,
+                    uint8_t* count_flags, void* hip_stream) {
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (!opts) return set_err(MDFIT_E_ARG, "opts is required (the options of the NUTS call)");
+  if (opts->mode != MDFIT_MODE_NUTS) return set_err(MDFIT_E_ARG, "mdfit_nuts_post needs opts->mode == MDFIT_MODE_NUTS");
+  if (opts->num_samples < 2 || opts->num_samples > 4096)
+    return set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !workspace || !out || !status) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  return mdfit::nuts::post(y, N, mm, n_taxa, *opts, workspace, out, pred, status, waic, counts, count_flags,
+                           (hipStream_t)hip_stream);
+}
+
 int mdfit_psis(const double* ll, int64_t n_series, int32_t S, double* elpd, double* khat, void* hip_stream) {
   if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
   if (S < 2 || S > 4096) return set_err(MDFIT_E_ARG, "S must be in [2, 4096]");

@@ -90,6 +90,12 @@ int summary(const void* workspace, const double* out, int64_t n_taxa, const mdfi
 // pointwise[n_taxa][6][30][2]
 int loo(const uint32_t* y, const uint32_t* N, const void* workspace, const double* out, int64_t n_taxa,
         const mdfit_opts& o, double* loo_out, double* pointwise, hipStream_t s);
+// the post kernel alone (its tapped instantiation) on a workspace and chain
+// diag slots (out's 4..7 per sub-fit) the caller filled: writes out, pred
+// (unless null), status and the taps that are not null
+int post(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts& o,
+         const void* workspace, double* out, float* pred, int32_t* status, double* waic, uint32_t* counts,
+         uint8_t* count_flags, hipStream_t s);
 // steps 1-6 of MDFIT-LOO v1 on given series ll[n_series][S], one wave per series
 int psis(const double* ll, int64_t n_series, int S, double* elpd, double* khat, hipStream_t s);
 }  // namespace mdfit::nuts

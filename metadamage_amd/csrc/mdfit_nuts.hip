@@ -1486,12 +1486,25 @@ __device__ __forceinline__ void waic_cols(int lane, int S, const double* smp, bo
 }
 #endif
 
+// The taps of mdfit_nuts_post (the test entry): what the kernel forms on the
+// way to the record.  The product instantiation <false> takes an empty struct
+// and compiles every tap line out: one source, two kernels.
+template <bool kTap>
+struct PostTap {};
+template <>
+struct PostTap<true> {
+  double* waic;      // [T][6][30]: waic_i as formed (the entry pre-fills NaN), or null
+  uint32_t* counts;  // [T][32][S]: the unsorted predictive counts of each job (pre-filled 0xFFFFFFFF), or null
+  uint8_t* flags;    // [T][32]: 0 counts, 1 some draw was no count, 2 skipped for N = 0 (pre-filled 0xFF), or null
+};
+
+template <bool kTap>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_POST_WAVES))) void nuts_post_kernel(const uint32_t* __restrict__ gy,
                                                           const uint32_t* __restrict__ gN,
                                                           const uint32_t* __restrict__ gmm, int64_t n_taxa,
                                                           mdfit_opts o, const double* __restrict__ samples,
                                                           double* __restrict__ out, float* __restrict__ pred,
-                                                          int32_t* __restrict__ status) {
+                                                          int32_t* __restrict__ status, PostTap<kTap> tap) {
   __shared__ double s_y[kLD], s_N[kLD];
   __shared__ double s_rec[MDFIT_NOUT];
   __shared__ double s_waic[MDFIT_NSUBFIT][kNPos];
@@ -1621,6 +1634,14 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_POS
     }
   }
   __syncthreads();
+  if constexpr (kTap) {
+    if (tap.waic != nullptr)
+      for (int x = lane; x < MDFIT_NSUBFIT * kNPos; x += kWave) {
+        const int s = x / kNPos, col = x - s * kNPos;
+        const int lo = (s == 3 || s == 5) ? kNHalf : 0, hi = s < 2 ? kNPos : lo + kNHalf;
+        if (col >= lo && col < hi) tap.waic[t * (MDFIT_NSUBFIT * kNPos) + x] = s_waic[s][col];
+      }
+  }
   // ---- n_sigma x3, asymmetry (fits.py:194-227): lane = point ------------------
   {
     const double v30 = lane < kNPos ? 1.0 : 0.0;
@@ -1688,6 +1709,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_POS
     if (nn == 0.0) {
       m3[0] = m3[1] = m3[2] = NAN;
 #endif
+      if constexpr (kTap) {
+        if (tap.flags != nullptr && lane == 0) tap.flags[t * kLD + job] = 2;
+      }
     } else {
       const Stream st = make_stream(o.seed, o.index_base + t, s);
       bool bad = false;
@@ -1695,8 +1719,15 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_POS
         const int64_t cnt = predictive_count(st, x, col, k, nn, smp + ((int64_t)s * S + x) * 4);
         bad = bad || cnt < 0;
         s_c[x] = (uint32_t)(cnt < 0 ? 0 : cnt);
+        if constexpr (kTap) {
+          if (tap.counts != nullptr) tap.counts[(t * kLD + job) * (int64_t)S + x] = cnt < 0 ? 0xFFFFFFFFu : (uint32_t)cnt;
+        }
       }
       __syncthreads();
+      if constexpr (kTap) {
+        const bool any_bad = __any(bad);
+        if (tap.flags != nullptr && lane == 0) tap.flags[t * kLD + job] = any_bad ? 1 : 0;
+      }
       if (__any(bad)) {  // (wave-uniform) the oracle: any NaN fraction -> NaN median and HPDI
         m3[0] = m3[1] = m3[2] = NAN;
       } else {
@@ -2231,6 +2262,38 @@ int64_t workspace_bytes(int64_t n_taxa, int num_samples) {
   return kSamplesOffset + n_taxa * MDFIT_NSUBFIT * (int64_t)(num_samples > 0 ? num_samples : 0) * 4 * 8;
 }
 
+// dynamic LDS of the post kernel: the sort pads the draws' counts to 2^k
+static size_t post_lds_bytes(int num_samples) {
+  const size_t elt = sizeof(uint32_t);
+  size_t sv_bytes = elt;
+  while (sv_bytes < (size_t)num_samples * elt) sv_bytes <<= 1;
+  // (the noise's counts and scratch reuse it after the draws: 1440 + 512 B)
+  return sv_bytes < 2048 ? 2048 : sv_bytes;
+}
+
+// mdfit_nuts_post: the post kernel alone, its tapped instantiation, on a
+// workspace and chain diag slots the caller filled
+int post(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts& o,
+         const void* workspace, double* out, float* pred, int32_t* status, double* waic, uint32_t* counts,
+         uint8_t* count_flags, hipStream_t s) {
+  if (o.num_samples < 2 || o.num_samples > kMaxSamples)
+    return host::set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
+  const double* samples = (const double*)((const char*)workspace + kSamplesOffset);
+  const int S = o.num_samples;
+  // what the kernel never forms stays NaN / 0xFFFFFFFF / 0xFF
+  if (waic != nullptr &&
+      hipMemsetAsync(waic, 0xFF, (size_t)n_taxa * MDFIT_NSUBFIT * kNPos * sizeof(double), s) != hipSuccess)
+    return host::check_launch("hipMemsetAsync(waic)");
+  if (counts != nullptr && hipMemsetAsync(counts, 0xFF, (size_t)n_taxa * kLD * S * sizeof(uint32_t), s) != hipSuccess)
+    return host::check_launch("hipMemsetAsync(counts)");
+  if (count_flags != nullptr && hipMemsetAsync(count_flags, 0xFF, (size_t)n_taxa * kLD, s) != hipSuccess)
+    return host::check_launch("hipMemsetAsync(count_flags)");
+  host::debug_poison(s);
+  hipLaunchKernelGGL(nuts_post_kernel<true>, dim3((unsigned)n_taxa), dim3(kWave), post_lds_bytes(S), s, y, N, mm,
+                     n_taxa, o, samples, out, pred, status, PostTap<true>{waic, counts, count_flags});
+  return host::check_launch("nuts_post_kernel<tap>");
+}
+
 int fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts& o,
               double* out, float* pred, int32_t* status, void* workspace, hipStream_t s) {
   if (o.num_samples < 2 || o.num_samples > kMaxSamples)
@@ -2252,14 +2315,9 @@ int fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t 
   hipLaunchKernelGGL(chain, dim3((unsigned)g), dim3(kWave), 0, s, y, N, n_taxa, o, out, ws, samples);
   if (int rc = host::check_launch("nuts_chain_cd")) return rc;
   host::prof_mark(2, s);
-  const size_t elt = sizeof(uint32_t);
-  size_t sv_bytes = elt;
-  while (sv_bytes < (size_t)o.num_samples * elt) sv_bytes <<= 1;  // the sort pads to 2^k
-  // (the noise's counts and scratch reuse it after the draws: 1440 + 512 B)
-  sv_bytes = sv_bytes < 2048 ? 2048 : sv_bytes;
   host::debug_poison(s);
-  hipLaunchKernelGGL(nuts_post_kernel, dim3((unsigned)n_taxa), dim3(kWave), sv_bytes, s, y, N, mm, n_taxa, o,
-                     samples, out, pred, status);
+  hipLaunchKernelGGL(nuts_post_kernel<false>, dim3((unsigned)n_taxa), dim3(kWave), post_lds_bytes(o.num_samples), s,
+                     y, N, mm, n_taxa, o, samples, out, pred, status, PostTap<false>{});
   return host::check_launch("nuts_post_kernel");
 }
 

@@ -294,6 +294,53 @@ def nuts_loo_device(y, N, res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, loo=
     return loo if pointwise is None else (loo, pointwise)
 
 
+def nuts_post_device(y, N, res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, mm=None, taps: bool = False,
+                     waic=None, counts=None, count_flags=None, stream=None):
+    """Launch mdfit_nuts_post (test entry; asynchronous on `stream`): the record
+    assembly of a NUTS call alone -- the post kernel, the product launch's
+    source lines -- on the draws in res.workspace and the chain diag slots 4..7
+    (step, leapfrogs, status, divergences of each sub-fit) in res.out, whose
+    other slots are zero.  Fills res.out, res.pred (unless None) and
+    res.status.  y, N (and mm, or None): the device counts [T, LD] ([T, 30,
+    12]).  taps=True allocates the taps (or pass tensors): waic float64 [T, 6,
+    30] (NaN where the kernel forms none), counts int32-typed uint32 [T, 32, S]
+    (the unsorted predictive counts of the 32 jobs; 0xFFFFFFFF = no count or job
+    not run) and count_flags uint8 [T, 32] (0 counts, 1 some draw was none, 2 N
+    = 0, 255 not reached).  Returns (waic, counts, count_flags)."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S = int(n_taxa), int(opts.num_samples)
+    dev = res.out.device
+    if taps:
+        waic = torch.empty((T, _lib.NSUBFIT, _lib.NPOS), dtype=torch.float64, device=dev) if waic is None else waic
+        counts = torch.empty((T, _lib.LD, S), dtype=torch.int32, device=dev) if counts is None else counts
+        count_flags = torch.empty((T, _lib.LD), dtype=torch.uint8, device=dev) if count_flags is None else count_flags
+    for name, t, n, size in (("waic", waic, T * _lib.NSUBFIT * _lib.NPOS, 8), ("counts", counts, T * _lib.LD * S, 4),
+                             ("count_flags", count_flags, T * _lib.LD, 1)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.element_size() == size and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda tensor of {n} elements of {size} bytes")
+    for name, a in (("y", y), ("N", N)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if mm is not None and not (mm.is_cuda and mm.is_contiguous() and mm.element_size() == 4
+                               and mm.numel() == T * _lib.NPOS * _lib.NMM):
+        raise ValueError("mm must be a contiguous cuda tensor of T*30*12 uint32")
+    if not (res.out.is_contiguous() and int(res.out.shape[0]) >= T and res.status.numel() >= T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    if res.pred is not None and not (res.pred.is_contiguous() and res.pred.numel() >= T * _lib.NPRED * _lib.NPOS):
+        raise ValueError("res.pred must be contiguous float32 [T, 3, 30]")
+    if int(opts.mode) == _lib.MODE_NUTS and (res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts)):
+        raise ValueError("res.workspace does not hold the draws of T taxa under opts")
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    _lib.check(lib.mdfit_nuts_post(ptr(y), ptr(N), ptr(mm), T, ctypes.byref(opts), ptr(res.workspace), ptr(res.out),
+                                   ptr(res.pred), ptr(res.status), ptr(waic), ptr(counts), ptr(count_flags),
+                                   _stream_handle(torch, stream)))
+    return waic, counts, count_flags
+
+
 def psis(ll, device="cuda"):
     """(elpd[n], khat[n]) float64 host arrays of the pointwise log-likelihood
     series ll[n, S] by the device's PSIS estimator (MDFIT-LOO v1, mdfit_psis;

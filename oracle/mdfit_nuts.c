@@ -656,14 +656,34 @@ static double binomial_draw(ndraw* d, double n, double p) {
   return flip ? n - k : k;
 }
 
-/* frac = obs / N of predictive draw s at all-position column i (|z|-1 = k) */
-static double predictive_frac(const nstream* st, int s, int i, int k, double Nn, const double th[4], int pmd) {
+/* obs of predictive draw s at all-position column i (|z|-1 = k) */
+static double predictive_obs(const nstream* st, int s, int i, int k, double Nn, const double th[4], int pmd) {
   double D = pmd ? th[1] * pow(1.0 - th[0], (double)k) + th[2] : th[0];
   D = D < 0.0 ? 0.0 : (D > 1.0 ? 1.0 : D);
   ndraw d = {st, 0xFFFD0000u + (uint32_t)s, (uint32_t)i << 16, 0.0, 0.0, 0, 0};
   const double p = beta_draw(&d, D * th[3], (1.0 - D) * th[3]);
-  const double obs = binomial_draw(&d, Nn, p);
-  return obs / Nn; /* 0/0 -> NaN like numpy */
+  return binomial_draw(&d, Nn, p);
+}
+
+/* frac = obs / N of that draw */
+static double predictive_frac(const nstream* st, int s, int i, int k, double Nn, const double th[4], int pmd) {
+  return predictive_obs(st, s, i, k, Nn, th, pmd) / Nn; /* 0/0 -> NaN like numpy */
+}
+
+/* one predictive job: the fractions of the S draws th[S][4] into v, and (tap)
+ * their counts: 0xFFFFFFFF where obs is no count in [0, N] or N = 0; flag 0
+ * all counts, 1 some draw was none, 2 N = 0 */
+static void predictive_job(const nstream* st, int i, int k, double Nn, const double* th, int S, double* v,
+                           uint32_t* counts, uint8_t* flag) {
+  int bad = 0;
+  for (int s = 0; s < S; s++) {
+    const double obs = predictive_obs(st, s, i, k, Nn, th + 4 * s, 1);
+    v[s] = obs / Nn;
+    const int ok = Nn > 0.0 && obs >= 0.0 && obs <= Nn;
+    bad |= !ok;
+    if (counts) counts[s] = ok ? (uint32_t)obs : 0xFFFFFFFFu;
+  }
+  if (flag) *flag = Nn > 0.0 ? (uint8_t)(bad ? 1 : 0) : 2;
 }
 
 static int cmp_double(const void* a, const void* b) {
@@ -733,10 +753,21 @@ static void waic_points(const uint32_t* y, const uint32_t* N, int lo, int hi, in
   free(lp);
 }
 
-/* n_sigma / asymmetry of mdfit_oracle.c take pointwise log-likelihoods
- * (waic_i = -2 ell_i); with samples waic_i is given, so pass -waic_i / 2 */
-static void nuts_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm, const mdfit_opts* o, int64_t g,
-                       double* out, float* pred, int32_t* status, double* samples_out /* [6][S][4] or NULL */) {
+/* The post part of a taxon: the record from the six chains' draws smp[6][S][4]
+ * and the chain diag slots 4..7 already in out (the status among them).
+ * n_sigma / asymmetry of mdfit_oracle.c take pointwise log-likelihoods
+ * (waic_i = -2 ell_i); with samples waic_i is given, so pass -waic_i / 2.
+ * Taps (each NULL or): waic[6][30], NaN where none is formed; counts[32][S]
+ * and flags[32] of the 32 predictive jobs (predictive_job), 0xFFFFFFFF / 0xFF
+ * in a job not reached. */
+static void nuts_post_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm, const mdfit_opts* o, int64_t g,
+                            const double* smp, double* out, float* pred, int32_t* status, double* waic,
+                            uint32_t* counts, uint8_t* flags) {
+  const int S = o->num_samples;
+  if (waic)
+    for (int j = 0; j < 6 * NPOS; j++) waic[j] = NAN;
+  if (counts) memset(counts, 0xFF, sizeof(uint32_t) * 32 * (size_t)S);
+  if (flags) memset(flags, 0xFF, 32);
   for (int i = 0; i < NPOS; i++)
     if (y[i] > N[i]) {
       for (int j = 0; j < MDFIT_NOUT; j++) out[j] = NAN;
@@ -745,35 +776,21 @@ static void nuts_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm,
       *status = MDFIT_INVALID;
       return;
     }
-  static const int models[6] = {M_PMD, M_NULL, M_PMD, M_PMD, M_NULL, M_NULL};
-  static const int los[6] = {0, 0, 0, NHALF, 0, NHALF};
-  static const int his[6] = {NPOS, NPOS, NHALF, NPOS, NHALF, NPOS};
-  const int S = o->num_samples;
-  double* smp = samples_out ? samples_out : (double*)malloc(sizeof(double) * 6 * 4 * (size_t)S);
   int st = MDFIT_OK;
-  for (int j = 0; j < MDFIT_NOUT; j++) out[j] = 0.0;
   for (int s = 0; s < 6; s++) {
-    nctx cx = {models[s], los[s], his[s], y, N};
-    nstream ns = nstream_make(o->seed, g, s);
-    nchain_stats cs;
-    nuts_chain(&cx, &ns, o->num_warmup, S, smp + (size_t)s * 4 * S, &cs);
-    if (cs.status > st) st = cs.status;
+    double* dg = out + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * s;
+    if ((int)dg[6] > st) st = (int)dg[6];
     double m[4] = {0, 0, 0, 0};
     for (int k = 0; k < S; k++)
       for (int j = 0; j < 4; j++) m[j] += smp[(size_t)s * 4 * S + 4 * k + j];
-    double* dg = out + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * s;
     for (int j = 0; j < 4; j++) dg[j] = m[j] / S; /* posterior means of q, A, c, phi */
-    dg[4] = cs.step;
-    dg[5] = cs.leap;
-    dg[6] = cs.status;
-    dg[7] = cs.div;
   }
+  for (int j = 0; j < MDFIT_F_DIAG; j++) out[j] = 0.0;
   if (st != MDFIT_OK) {
     for (int j = 0; j < MDFIT_NRESULT; j++) out[j] = NAN;
     if (pred)
       for (int j = 0; j < 3 * NPOS; j++) pred[j] = NAN;
     *status = st;
-    if (!samples_out) free(smp);
     return;
   }
   const double* sP = smp;
@@ -789,6 +806,14 @@ static void nuts_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm,
   waic_points(y, N, NHALF, NPOS, 1, sPr, S, wPr);
   waic_points(y, N, 0, NHALF, 0, sNf, S, wNf);
   waic_points(y, N, NHALF, NPOS, 0, sNr, S, wNr);
+  if (waic) {
+    memcpy(waic, wP, sizeof(wP));
+    memcpy(waic + NPOS, wN, sizeof(wN));
+    memcpy(waic + 2 * NPOS, wPf, sizeof(wPf));
+    memcpy(waic + 3 * NPOS + NHALF, wPr, sizeof(wPr));
+    memcpy(waic + 4 * NPOS, wNf, sizeof(wNf));
+    memcpy(waic + 5 * NPOS + NHALF, wNr, sizeof(wNr));
+  }
   double lP[NPOS], lN[NPOS], lC[NPOS];
   for (int i = 0; i < NPOS; i++) {
     lP[i] = -0.5 * wP[i];
@@ -825,7 +850,8 @@ static void nuts_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm,
   double p3[3];
   for (int i = 0; i < NPOS; i++) {
     nstream ns = nstream_make(o->seed, g, 0);
-    for (int k = 0; k < S; k++) v[k] = predictive_frac(&ns, k, i, kpos(i), (double)N[i], sP + 4 * k, 1);
+    predictive_job(&ns, i, kpos(i), (double)N[i], sP, S, v, counts ? counts + (size_t)i * S : NULL,
+                   flags ? flags + i : NULL);
     median_hpdi(v, S, p3);
     if (pred)
       for (int r = 0; r < 3; r++) pred[r * NPOS + i] = (float)p3[r];
@@ -837,14 +863,16 @@ static void nuts_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm,
   }
   {
     nstream ns = nstream_make(o->seed, g, 2);
-    for (int k = 0; k < S; k++) v[k] = predictive_frac(&ns, k, 0, 0, (double)N[0], sPf + 4 * k, 1);
+    predictive_job(&ns, 0, 0, (double)N[0], sPf, S, v, counts ? counts + (size_t)NPOS * S : NULL,
+                   flags ? flags + NPOS : NULL);
     median_hpdi(v, S, p3);
     out[MDFIT_F_D_MAX_FORWARD] = p3[0];
   }
   {
     /* the reverse fit's predictive on data_forward (fits.py:343-348) */
     nstream ns = nstream_make(o->seed, g, 3);
-    for (int k = 0; k < S; k++) v[k] = predictive_frac(&ns, k, 0, 0, (double)N[0], sPr + 4 * k, 1);
+    predictive_job(&ns, 0, 0, (double)N[0], sPr, S, v, counts ? counts + (size_t)(NPOS + 1) * S : NULL,
+                   flags ? flags + NPOS + 1 : NULL);
     median_hpdi(v, S, p3);
     out[MDFIT_F_D_MAX_REVERSE] = p3[0];
   }
@@ -875,6 +903,37 @@ static void nuts_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm,
         out[MDFIT_F_NORMALIZED_NOISE_REVERSE] = NAN;
   }
   *status = st;
+}
+
+/* a taxon: the six chains (draws and diag slots 4..7), then the post part */
+static void nuts_taxon(const uint32_t* y, const uint32_t* N, const uint32_t* mm, const mdfit_opts* o, int64_t g,
+                       double* out, float* pred, int32_t* status, double* samples_out /* [6][S][4] or NULL */) {
+  for (int i = 0; i < NPOS; i++)
+    if (y[i] > N[i]) { /* no chain is run */
+      for (int j = 0; j < MDFIT_NOUT; j++) out[j] = NAN;
+      if (pred)
+        for (int j = 0; j < 3 * NPOS; j++) pred[j] = NAN;
+      *status = MDFIT_INVALID;
+      return;
+    }
+  static const int models[6] = {M_PMD, M_NULL, M_PMD, M_PMD, M_NULL, M_NULL};
+  static const int los[6] = {0, 0, 0, NHALF, 0, NHALF};
+  static const int his[6] = {NPOS, NPOS, NHALF, NPOS, NHALF, NPOS};
+  const int S = o->num_samples;
+  double* smp = samples_out ? samples_out : (double*)malloc(sizeof(double) * 6 * 4 * (size_t)S);
+  for (int j = 0; j < MDFIT_NOUT; j++) out[j] = 0.0;
+  for (int s = 0; s < 6; s++) {
+    nctx cx = {models[s], los[s], his[s], y, N};
+    nstream ns = nstream_make(o->seed, g, s);
+    nchain_stats cs;
+    nuts_chain(&cx, &ns, o->num_warmup, S, smp + (size_t)s * 4 * S, &cs);
+    double* dg = out + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * s;
+    dg[4] = cs.step;
+    dg[5] = cs.leap;
+    dg[6] = cs.status;
+    dg[7] = cs.div;
+  }
+  nuts_post_taxon(y, N, mm, o, g, smp, out, pred, status, NULL, NULL, NULL);
   if (!samples_out) free(smp);
 }
 
@@ -891,6 +950,27 @@ int oracle_nuts_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, 
     nuts_taxon(y + t * MDFIT_LD, N + t * MDFIT_LD, mm ? mm + t * NPOS * MDFIT_NMM : NULL, &o, o.index_base + t,
                out + t * MDFIT_NOUT, pred ? pred + t * MDFIT_NPRED * NPOS : NULL, status + t,
                samples ? samples + (size_t)t * 6 * 4 * o.num_samples : NULL);
+  }
+  return 0;
+}
+
+/* The post part alone (tests): the records of draws samples[T][6][S][4] the
+ * caller chose; out holds on entry the chain diag slots 4..7 of each sub-fit.
+ * Taps, each NULL or: waic[T][6][30], counts[T][32][S], flags[T][32]. */
+int oracle_nuts_post(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa,
+                     const mdfit_opts* opts, const double* samples, double* out, float* pred, int32_t* status,
+                     double* waic, uint32_t* counts, uint8_t* flags, int n_threads) {
+  mdfit_opts o = *opts;
+  const size_t S = (size_t)o.num_samples;
+#ifdef _OPENMP
+  int nt = n_threads > 0 ? n_threads : omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+#endif
+  for (int64_t t = 0; t < n_taxa; t++) {
+    nuts_post_taxon(y + t * MDFIT_LD, N + t * MDFIT_LD, mm ? mm + t * NPOS * MDFIT_NMM : NULL, &o, o.index_base + t,
+                    samples + (size_t)t * 6 * 4 * S, out + t * MDFIT_NOUT, pred ? pred + t * MDFIT_NPRED * NPOS : NULL,
+                    status + t, waic ? waic + (size_t)t * 6 * NPOS : NULL, counts ? counts + (size_t)t * 32 * S : NULL,
+                    flags ? flags + (size_t)t * 32 : NULL);
   }
   return 0;
 }
