@@ -449,6 +449,57 @@ int mdfit_map_psis(const uint32_t* y, const uint32_t* N, const double* out, cons
 int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w, double* khat,
                        void* hip_stream);
 
+/* Importance-weighted WAIC record: double waic[T][7][MDFIT_NMAPWAIC].  Rows
+ * 0..5, one per sub-fit in diagnostic-slot order (PMD-all, null-all, PMD-fwd,
+ * PMD-rev, null-fwd, null-rev): elpd_waic = sum_i (lppd_i - p_i), p_waic =
+ * sum_i p_i, lppd, khat, ess = 1 / sum w^2, n_infeasible, p_waic_max = max_i
+ * p_i, flags (an integer stored as double: bit 0 the row is valid, bit 1 khat
+ * <= min(1 - 1 / log10 S, 0.7), bits 2..5 coordinate (q, A, c, phi) free).
+ * Row 6, the comparisons: n_sigma_waic, n_sigma_waic_forward,
+ * n_sigma_waic_reverse, asymmetry_waic, khat_max and ess_min over the valid
+ * rows, 0, flags (bit 0 all six rows valid, bit 1 all six valid and at or
+ * under the khat threshold). */
+#define MDFIT_NMAPWAIC 8
+
+/*
+ * Importance-weighted WAIC of the six sub-fits of a finished MODE_MAP call and
+ * the reference's comparisons on it (MDFIT-WAIC v1, DESIGN.md §3.9;
+ * fits.py:147-227).  The PMD rows are importance-sampled as mdfit_map_psis
+ * does it: the same proposal, Philox stream (sub-fit 0 / 2 / 3), target,
+ * smoothing and validity rule, so khat, ess, n_infeasible and the free bits of
+ * rows 0, 2, 3 are mdfit_map_psis's bit for bit.  A null row (stream sub-fit
+ * 1 / 4 / 5, the same domain and block layout) draws (logit q, log delta) from
+ * a bivariate Student-t (nu = 4) on the Laplace fit of the null objective at
+ * its mode and weighs it by the null model's log-pmf, priors and Jacobian; it
+ * is valid when q and delta are free, both diagonal entries of H are positive
+ * and the Jacobi-scaled 2x2 Cholesky's pivots exceed 1e-8.  For a valid row,
+ * with the smoothed, normalised weights w_s and l_si the full beta-binomial
+ * log-pmf of draw s at point i of the row's 15 or 30 columns: lppd_i = log
+ * sum_s w_s exp(l_si), p_i = sum_s w_s (l_si - sum_s w_s l_si)^2, waic_i = -2
+ * (lppd_i - p_i); a point with N_i = 0 has lppd_i = p_i = 0 exactly.  Row 6 is
+ * the reference's n_sigma of the waic_i columns: n_sigma_waic needs rows 0 and
+ * 1, forward rows 2 and 4, reverse rows 3 and 5, asymmetry rows 0, 2 and 3;
+ * NaN when one of them is invalid.  An invalid row has NaN statistics and only
+ * its free bits in flags; a taxon with status != MDFIT_OK NaN statistics and
+ * flags 0 in all seven rows.
+ *   y, N, out, status : those of the MODE_MAP call (device; read only)
+ *   num_draws  : S in [25, 1024] (else MDFIT_E_ARG)
+ *   seed, index_base : the Philox streams are keyed by (seed, index_base +
+ *                taxon, sub-fit), as mdfit_map_psis's
+ *   waic       : double[n_taxa][7][MDFIT_NMAPWAIC]                 (device)
+ *   pointwise  : double[n_taxa][6][30][2] = (lppd_i, p_i); NaN outside a
+ *                sub-fit's columns and in an invalid row; or NULL   (device)
+ *   draws      : double[n_taxa][6][num_draws][6] = u[4] (a null row: u[1] = u[2]
+ *                = 0), the raw log-weight, the weight; NaN in an invalid row;
+ *                or NULL (parity tests)                             (device)
+ * One launch on hip_stream, one wave per taxon; no workspace, no allocation,
+ * no side stream, no host synchronisation, no atomics; capturable in a graph.
+ * n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                   int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base,
+                   double* waic, double* pointwise, double* draws, void* hip_stream);
+
 /*
  * Pointwise beta-binomial log-pmf (numpyro BetaBinomial.log_prob, used by
  * fits.py:59,67 and log_likelihood fits.py:126-133):

@@ -33,6 +33,7 @@ NNUTSDIAG = 12
 NNUTSSUMM = 16
 NNUTSLOO = 8
 NMAPPSIS = 16
+NMAPWAIC = 8
 NLOOROW = 7  # rows of a PSIS-LOO record: the six sub-fits, then the comparisons
 
 # output record field order (enum mdfit_field) == fit_results numeric columns
@@ -88,6 +89,14 @@ MAPPSIS_FIELDS = ["q_mean", "A_mean", "c_mean", "phi_mean", "D_max_mean", "q_std
                   "D_max_std", "rho_Ac", "significance", "khat", "ess", "n_infeasible", "flags"]
 MAPPSIS_VALID, MAPPSIS_RELIABLE = 1, 2  # flags: bit 0 valid, bit 1 khat <= threshold, bits 2..5 coordinate free
 
+# importance-weighted WAIC record (mdfit_map_waic): float64 [T][NWAICROW][NMAPWAIC], rows 0..5 in SUBFITS order ...
+NWAICROW = 7
+MAPWAIC_FIELDS = ["elpd_waic", "p_waic", "lppd", "khat", "ess", "n_infeasible", "p_waic_max", "flags"]
+# ... and row 6, the comparisons
+MAPWAIC_COMPARE_FIELDS = ["n_sigma_waic", "n_sigma_waic_forward", "n_sigma_waic_reverse", "asymmetry_waic", "khat_max",
+                          "ess_min", "reserved", "flags"]
+MAPWAIC_VALID, MAPWAIC_RELIABLE = 1, 2  # flags: bit 0 valid, bit 1 khat <= threshold; rows 0..5: bits 2..5 free
+
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
     "mdfit_default_opts",
@@ -103,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_psis",
     "mdfit_map_psis",
     "mdfit_psis_weights",
+    "mdfit_map_waic",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
     "mdfit_primitive",
@@ -191,6 +201,8 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_psis.restype = ctypes.c_int
     lib.mdfit_map_psis.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp]
     lib.mdfit_map_psis.restype = ctypes.c_int
+    lib.mdfit_map_waic.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp, vp]
+    lib.mdfit_map_waic.restype = ctypes.c_int
     lib.mdfit_psis_weights.argtypes = [vp, i64, i32, vp, vp, vp]
     lib.mdfit_psis_weights.restype = ctypes.c_int
     lib.mdfit_betabinom_logpmf.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]

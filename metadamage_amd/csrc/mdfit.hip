@@ -43,6 +43,7 @@
 #include "mdfit_host.h"
 #include "mdfit_laplace.h"
 #include "mdfit_mappsis.h"
+#include "mdfit_mapwaic.h"
 #include "mdfit_model.h"
 #include "mdfit_primitive.h"
 #include "mdfit_special.h"
@@ -2084,6 +2085,25 @@ int mdfit_map_psis(const uint32_t* y, const uint32_t* N, const double* out, cons
                      (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
                      seed, index_base, mp::khat_threshold(S), psis, draws);
   return check_launch("map_psis_kernel");
+}
+
+int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                   int32_t num_draws, uint64_t seed, int64_t index_base, double* waic, double* pointwise,
+                   double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace mw = mdfit::mapwaic;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !waic) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mw::map_waic_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), waic, pointwise, draws);
+  return check_launch("map_waic_kernel");
 }
 
 int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w, double* khat, void* hip_stream) {

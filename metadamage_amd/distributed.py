@@ -50,10 +50,18 @@ REC_LOO = _lib.NLOOROW * _lib.NNUTSLOO * 4
 # with_psis (a "map-psis" run; never together with any of them): the same for the
 # importance-sampled posteriors, one more f32 block [n, 3, NMAPPSIS], 192 B per taxon
 REC_PSIS = 3 * _lib.NMAPPSIS * 4
+# with_waic (a "map-waic" run; never together with any of them): the same for the
+# importance-weighted WAIC records, one more f32 block [n, 7, NMAPWAIC], 224 B per taxon
+REC_WAIC = _lib.NWAICROW * _lib.NMAPWAIC * 4
 
 
 def _extra(with_laplace: bool, with_diag: bool, with_summary: bool = False, with_loo: bool = False,
-           with_psis: bool = False) -> int:
+           with_psis: bool = False, with_waic: bool = False) -> int:
+    if with_waic:
+        if with_laplace or with_diag or with_summary or with_loo or with_psis:
+            raise ValueError("with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace are mutually "
+                             "exclusive: one extra block per run")
+        return REC_WAIC
     if with_psis:
         if with_laplace or with_diag or with_summary or with_loo:
             raise ValueError("with_psis, with_loo, with_summary, with_diag and with_laplace are mutually exclusive: "
@@ -98,17 +106,19 @@ class Records:
     written in place by the chunked dispatch.  with_diag: likewise n * REC_DIAG
     bytes, `diag` f32[n, 6, 12]; with_summary: n * REC_SUMM bytes, `summ` f32[n,
     6, 16]; with_loo: n * REC_LOO bytes, `loo` f32[n, 7, 8]; with_psis: n *
-    REC_PSIS bytes, `psis` f32[n, 3, 16].  At most one of the five."""
+    REC_PSIS bytes, `psis` f32[n, 3, 16]; with_waic: n * REC_WAIC bytes, `waic`
+    f32[n, 7, 8].  At most one of the six."""
 
     def __init__(self, n: int, device, with_laplace: bool = False, with_diag: bool = False,
-                 with_summary: bool = False, with_loo: bool = False, with_psis: bool = False):
+                 with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
+                 with_waic: bool = False):
         import torch
 
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
-        self.buf = torch.empty(n * (REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis)),
-                               dtype=torch.uint8, device=device)
-        self.lap = self.diag = self.summ = self.loo = self.psis = None
+        self.buf = torch.empty(n * (REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis,
+                                                       with_waic)), dtype=torch.uint8, device=device)
+        self.lap = self.diag = self.summ = self.loo = self.psis = self.waic = None
         if with_laplace:
             self.pred, self.status, self.ints, self.floats, self.lap = packed_views(self.buf, n, with_laplace=True)
         elif with_diag:
@@ -119,6 +129,8 @@ class Records:
             self.pred, self.status, self.ints, self.floats, self.loo = packed_views(self.buf, n, with_loo=True)
         elif with_psis:
             self.pred, self.status, self.ints, self.floats, self.psis = packed_views(self.buf, n, with_psis=True)
+        elif with_waic:
+            self.pred, self.status, self.ints, self.floats, self.waic = packed_views(self.buf, n, with_waic=True)
         else:
             self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
         self._fidx = torch.as_tensor(FLOAT_COLS, device=device)
@@ -130,7 +142,7 @@ class Records:
 
 
 def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-                 with_loo: bool = False, with_psis: bool = False):
+                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False):
     """Views (pred[n, 3, 30] f32, status[n] i32, ints[n, 8] f64, floats[n, 17]
     f32) into one uint8 gather buffer of n * REC_BYTES bytes laid out ints |
     floats | pred | status (torch tensor; the f64 block first keeps it 8-byte
@@ -139,8 +151,9 @@ def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = Fals
     REC_DIAG more bytes and the fifth view is diag[n, 6, 12] f32; with_summary: n
     * REC_SUMM more bytes and the fifth view is summ[n, 6, 16] f32; with_loo: n *
     REC_LOO more bytes and the fifth view is loo[n, 7, 8] f32; with_psis: n *
-    REC_PSIS more bytes and the fifth view is psis[n, 3, 16] f32."""
-    _extra(with_laplace, with_diag, with_summary, with_loo, with_psis)
+    REC_PSIS more bytes and the fifth view is psis[n, 3, 16] f32; with_waic: n *
+    REC_WAIC more bytes and the fifth view is waic[n, 7, 8] f32."""
+    _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
     o1 = n * REC_INT
     o2 = o1 + n * REC_F32
     o3 = o2 + n * REC_PRED
@@ -168,6 +181,10 @@ def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = Fals
         o4 = o3 + 4 * n
         psis = buf[o4 : o4 + n * REC_PSIS].view(dtype=_torch_dtype("float32")).view(n, 3, _lib.NMAPPSIS)
         return pred, status, ints, floats, psis
+    if with_waic:
+        o4 = o3 + 4 * n
+        waic = buf[o4 : o4 + n * REC_WAIC].view(dtype=_torch_dtype("float32")).view(n, _lib.NWAICROW, _lib.NMAPWAIC)
+        return pred, status, ints, floats, waic
     return pred, status, ints, floats
 
 
@@ -186,8 +203,9 @@ def _torch_dtype(name):
 
 
 def alloc_records(n: int, device, with_laplace: bool = False, with_diag: bool = False,
-                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False) -> Records:
-    return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis)
+                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
+                  with_waic: bool = False) -> Records:
+    return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
 
 
 def gather_records(buf, n_cap: int, rank: int, world: int, group=None, async_op: bool = False):
@@ -293,19 +311,21 @@ def run_distributed(fn, *args, **kwargs):
 
 
 def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, with_diag: bool = False,
-                    with_summary: bool = False, with_loo: bool = False, with_psis: bool = False):
+                    with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
+                    with_waic: bool = False):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  with_laplace: the
     parts carry the Laplace block and a fourth array lap[T, 3, 8] f32 is returned;
     with_diag: the diagnostics block, returned as diag[T, 6, 12] f32;
     with_summary: the summaries block, returned as summ[T, 6, 16] f32; with_loo:
     the PSIS-LOO block, returned as loo[T, 7, 8] f32; with_psis: the
-    importance-sampled posteriors, returned as psis[T, 3, 16] f32."""
+    importance-sampled posteriors, returned as psis[T, 3, 16] f32; with_waic: the
+    importance-weighted WAIC records, returned as waic[T, 7, 8] f32."""
     import torch
 
     outs, preds, sts, laps = [], [], [], []
-    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis)
-    extra = with_laplace or with_diag or with_summary or with_loo or with_psis
+    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
+    extra = with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)
@@ -323,7 +343,8 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
         lo, hi = shard_range(n_taxa, r, world)
         n_cap = part.numel() // rec_bytes
         p, s, ints, floats, *rest = packed_views(part, n_cap, with_laplace=with_laplace, with_diag=with_diag,
-                                                 with_summary=with_summary, with_loo=with_loo, with_psis=with_psis)
+                                                 with_summary=with_summary, with_loo=with_loo, with_psis=with_psis,
+                                                 with_waic=with_waic)
         if extra:
             laps.append(rest[0][: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)

@@ -42,6 +42,7 @@ class FitBatch:
     summ: "object" = None  # torch.float32 [T, 6, NNUTSSUMM]: the posterior summaries (ChunkedFitter with_summary)
     loo: "object" = None  # torch.float32 [T, 7, NNUTSLOO]: the PSIS-LOO records (ChunkedFitter with_loo)
     psis: "object" = None  # torch.float32 [T, 3, NMAPPSIS]: the importance-sampled posteriors (ChunkedFitter with_psis)
+    waic: "object" = None  # torch.float32 [T, 7, NMAPWAIC]: the importance-weighted WAIC records (with_waic)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -184,6 +185,46 @@ def map_psis_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
                                   ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
                                   _stream_handle(torch, stream)))
     return psis if draws is None else (psis, draws)
+
+
+def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, waic=None,
+                    pointwise=None, draws=None, stream=None):
+    """Launch mdfit_map_waic on the records of a finished MAP call (asynchronous
+    on `stream`): the importance-weighted WAIC of the six sub-fits and the
+    reference's comparisons on it (MDFIT-WAIC v1), float64 waic[T, 7, NMAPWAIC]
+    (_lib.MAPWAIC_FIELDS; row 6 _lib.MAPWAIC_COMPARE_FIELDS).  The Philox
+    streams are keyed by (seed, index_base + taxon, sub-fit).  pointwise: None,
+    True (allocated) or a float64 tensor [T, 6, 30, 2] = (lppd_i, p_i); draws:
+    None, True or a float64 tensor [T, 6, num_draws, 6] = u[4], the raw
+    log-weight, the weight.  Returns waic, or the tuple (waic[, pointwise][,
+    draws]) of what was asked for."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S = int(ty.shape[0]), int(num_draws)
+    if waic is None:
+        waic = torch.empty((T, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=ty.device)
+    if pointwise is True:
+        pointwise = torch.empty((T, _lib.NSUBFIT, _lib.NPOS, 2), dtype=torch.float64, device=ty.device)
+    if draws is True:
+        draws = torch.empty((T, _lib.NSUBFIT, S, 6), dtype=torch.float64, device=ty.device)
+    for name, t, n in (("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC),
+                       ("pointwise", pointwise, T * _lib.NSUBFIT * _lib.NPOS * 2),
+                       ("draws", draws, T * _lib.NSUBFIT * S * 6)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    _lib.check(lib.mdfit_map_waic(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
+                                  ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S,
+                                  int(seed), int(index_base), ctypes.c_void_p(waic.data_ptr()),
+                                  ctypes.c_void_p(pointwise.data_ptr()) if pointwise is not None else None,
+                                  ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
+                                  _stream_handle(torch, stream)))
+    got = (waic,) + tuple(x for x in (pointwise, draws) if x is not None)
+    return waic if len(got) == 1 else got
 
 
 def psis_weights(lw, device="cuda"):
@@ -430,6 +471,23 @@ def _check_psis_mode(with_psis: bool, opts: _lib.MdfitOpts | None, with_laplace:
                          "one extra block per run")
 
 
+WAIC_BYTES = _lib.NWAICROW * _lib.NMAPWAIC * 4  # one taxon's WAIC records on the way out: f32 [7][8]
+
+
+def _check_waic_mode(with_waic: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
+                     with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
+                     with_psis: bool = False) -> None:
+    """with_waic is the MAP mode's (opts None: the default options, MAP) and the
+    run's one optional extra block."""
+    if not with_waic:
+        return
+    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
+        raise ValueError("with_waic needs MAP records (opts.mode == MODE_MAP)")
+    if with_laplace or with_diag or with_summary or with_loo or with_psis:
+        raise ValueError("with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace are mutually "
+                         "exclusive: one extra block per run")
+
+
 def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
     """with_diag is the sampling mode's (opts None: the default options, MAP)."""
     if with_diag and (opts is None or int(opts.mode) != _lib.MODE_NUTS):
@@ -438,7 +496,8 @@ def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
 
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
                  dest_on_device: bool = False, with_laplace: bool = False, with_diag: bool = False,
-                 with_summary: bool = False, with_loo: bool = False, with_psis: bool = False) -> int:
+                 with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
+                 with_waic: bool = False) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -456,12 +515,16 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     run's only extra block: ValueError).  with_psis: the importance-sampled
     posteriors, 384 B as computed (f64) and -- unless they go to the caller's
     device buffer -- 192 B rounded to f32 (MAP only, and the run's only extra
-    block: ValueError)."""
+    block: ValueError).  with_waic: the importance-weighted WAIC records, 448 B
+    as computed (f64) and -- unless they go to the caller's device buffer --
+    224 B rounded to f32 (MAP only, and the run's only extra block:
+    ValueError)."""
     C = int(C)
     _check_diag_mode(with_diag, opts)
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
     _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
+    _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
@@ -475,6 +538,8 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
         b += C * (2 * LOO_BYTES + (0 if dest_on_device else LOO_BYTES))
     if with_psis:
         b += C * (2 * PSIS_BYTES + (0 if dest_on_device else PSIS_BYTES))
+    if with_waic:
+        b += C * (2 * WAIC_BYTES + (0 if dest_on_device else WAIC_BYTES))
     return b + workspace_bytes(C, opts)
 
 
@@ -482,7 +547,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
                 dest_on_device: bool = False, with_laplace: bool = False,
                 with_diag: bool = False, with_summary: bool = False,
-                with_loo: bool = False, with_psis: bool = False) -> list[tuple[int, int]]:
+                with_loo: bool = False, with_psis: bool = False, with_waic: bool = False) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk fit in budget_bytes (None: no memory
     bound), no chunk exceeds the per-call limit (2^25 taxa) or chunk_taxa (> 0;
@@ -494,6 +559,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
     _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
+    _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -503,7 +569,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
         per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, with_laplace,  # noqa: E731
-                                              with_diag, with_summary, with_loo, with_psis)
+                                              with_diag, with_summary, with_loo, with_psis, with_waic)
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
         if per(cap) > budget_bytes:  # largest c with per(c) <= budget (per is monotone in c)
@@ -536,7 +602,7 @@ class _Set:
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
                  with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-                 with_loo: bool = False, with_psis: bool = False):
+                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -571,6 +637,11 @@ class _Set:
             self.psis64 = torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.psis = torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float32, device=device)
+        self.waic64 = self.waic = None
+        if with_waic:  # as mdfit_map_waic writes them, and rounded to f32 for the way out
+            self.waic64 = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=device)
+            if not dest_on_device:
+                self.waic = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -626,16 +697,23 @@ class ChunkedFitter:
     each chunk's fit on the compute stream with psis_draws draws per sub-fit,
     its streams keyed by opts.seed and the chunk's global taxon index, and its
     records, rounded to f32 there, leave as f32 [T, 3, 16], 192 B per taxon
-    (run's fourth array; dest.psis)."""
+    (run's fourth array; dest.psis).
+
+    with_waic (MAP only; the run's only extra block): mdfit_map_waic follows
+    each chunk's fit on the compute stream in the same way (psis_draws draws
+    per sub-fit, opts.seed, the chunk's global taxon index), and its records,
+    rounded to f32 there, leave as f32 [T, 7, 8], 224 B per taxon (run's fourth
+    array; dest.waic)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False,
                  with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
-                 with_psis: bool = False, psis_draws: int = PSIS_DRAWS):
+                 with_psis: bool = False, psis_draws: int = PSIS_DRAWS, with_waic: bool = False):
         _check_diag_mode(with_diag, opts)
         _check_summary_mode(with_summary, opts, with_laplace, with_diag)
         _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
         _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
+        _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
         torch = _torch()
         if with_laplace and opts is not None and int(opts.mode) != _lib.MODE_MAP:
             raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
@@ -644,19 +722,20 @@ class ChunkedFitter:
         self.with_summary = bool(with_summary)
         self.with_loo = bool(with_loo)
         self.with_psis = bool(with_psis)
+        self.with_waic = bool(with_waic)
         self.psis_draws = int(psis_draws)
         self.chunk_cap = int(chunk_cap)
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.with_laplace,
-                          self.with_diag, self.with_summary, self.with_loo, self.with_psis)
+                          self.with_diag, self.with_summary, self.with_loo, self.with_psis, self.with_waic)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = self.h_lap = None
-        self.h_diag = self.h_summ = self.h_loo = self.h_psis = None
+        self.h_diag = self.h_summ = self.h_loo = self.h_psis = self.h_waic = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -682,6 +761,8 @@ class ChunkedFitter:
                 self.h_loo = torch.empty((cap, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float32).pin_memory()
             if self.with_psis:
                 self.h_psis = torch.empty((cap, 3, _lib.NMAPPSIS), dtype=torch.float32).pin_memory()
+            if self.with_waic:
+                self.h_waic = torch.empty((cap, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -723,6 +804,9 @@ class ChunkedFitter:
         _check_psis_mode(self.with_psis, o0)
         if self.with_psis and dest is not None and dest.psis is None:
             raise ValueError("with_psis: dest.psis (float32 [T, 3, NMAPPSIS]) required")
+        _check_waic_mode(self.with_waic, o0)
+        if self.with_waic and dest is not None and dest.waic is None:
+            raise ValueError("with_waic: dest.waic (float32 [T, 7, NMAPWAIC]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -800,6 +884,13 @@ class ChunkedFitter:
                 psis32 = dest.psis[lo:hi] if dest is not None else st.psis[:n]
                 with torch.cuda.stream(comp):
                     psis32.copy_(st.psis64[:n])
+            waic32 = None
+            if self.with_waic:  # the records are final: their WAIC comparisons, rounded to f32 in place
+                map_waic_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
+                                waic=st.waic64[:n], stream=comp)
+                waic32 = dest.waic[lo:hi] if dest is not None else st.waic[:n]
+                with torch.cuda.stream(comp):
+                    waic32.copy_(st.waic64[:n])
             ev_done = torch.cuda.Event()
             ev_done.record(comp)
             done.append(ev_done)
@@ -820,6 +911,8 @@ class ChunkedFitter:
                         self.h_loo[lo:hi].copy_(loo32, non_blocking=True)
                     if psis32 is not None:
                         self.h_psis[lo:hi].copy_(psis32, non_blocking=True)
+                    if waic32 is not None:
+                        self.h_waic[lo:hi].copy_(waic32, non_blocking=True)
                 last_d2h = cp
         end = torch.cuda.Event()
         end.record(cp if last_d2h is not None else comp)
@@ -831,7 +924,7 @@ class ChunkedFitter:
         """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status -- and,
         with_laplace, lap[:, 3, 8] f32, or, with_diag, diag[:, 6, 12] f32, or,
         with_summary, summ[:, 6, 16] f32, or, with_loo, loo[:, 7, 8] f32, or,
-        with_psis, psis[:, 3, 16] f32) of the
+        with_psis, psis[:, 3, 16] f32, or, with_waic, waic[:, 7, 8] f32) of the
         pinned buffers (valid until the next run).  pinned: y, N, mm are that
         PinnedPack's views.  chunks: the split (default plan_chunks at this
         staging's chunk_cap)."""
@@ -855,13 +948,15 @@ class ChunkedFitter:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_loo[:T].numpy()
         if self.with_psis:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_psis[:T].numpy()
+        if self.with_waic:
+            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_waic[:T].numpy()
         return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy()
 
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
         (out[T, NOUT], pred, status -- with_laplace also lap, f32 [T, 3, 8],
         with_diag also diag, f32 [T, 6, 12], with_summary also summ, f32 [T, 6, 16], with_loo also loo, f32
-        [T, 7, 8]: rows written in place),
+        [T, 7, 8], with_psis also psis, f32 [T, 3, 16], with_waic also waic, f32 [T, 7, 8]: rows written in place),
         ordered on the caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
@@ -930,7 +1025,8 @@ _STAGING_LOCK = __import__("threading").Lock()
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
             dest_on_device: bool = False, budget_bytes: int | None = None,
             with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-            with_loo: bool = False, with_psis: bool = False, psis_draws: int = PSIS_DRAWS) -> ChunkedFitter:
+            with_loo: bool = False, with_psis: bool = False, psis_draws: int = PSIS_DRAWS,
+            with_waic: bool = False) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind and sampler length): the
     multi-file pipeline fits one file after another, and pinned + device
@@ -948,7 +1044,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     env_chunk = int(os.environ.get("MDFIT_CHUNK_TAXA", "0") or 0)
     key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
            bool(with_laplace), bool(with_diag), bool(with_summary), bool(with_loo),
-           int(psis_draws) if with_psis else 0)
+           int(psis_draws) if with_psis else 0, int(psis_draws) if with_waic else 0)
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -966,11 +1062,11 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
                       with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                      with_loo=with_loo, with_psis=with_psis)[0]
+                      with_loo=with_loo, with_psis=with_psis, with_waic=with_waic)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
                        with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                       with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws)
+                       with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws, with_waic=with_waic)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -979,7 +1075,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, laplace: bool = False, diag: bool = False,
-                   summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = PSIS_DRAWS):
+                   summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = PSIS_DRAWS,
+                   waic: bool = False):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
     the PMD sub-fits (_lib.LAPLACE_FIELDS), or, with diag (NUTS only), diag[T, 6,
@@ -989,7 +1086,9 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     loo[T, 7, 8] f32, the PSIS-LOO records (_lib.NUTSLOO_FIELDS), or, with psis
     (MAP only; the only one), psis[T, 3, 16] f32, the importance-sampled
     posteriors of the PMD sub-fits from psis_draws draws each
-    (_lib.MAPPSIS_FIELDS) --, chunked
+    (_lib.MAPPSIS_FIELDS), or, with waic (MAP only; the only one), waic[T, 7, 8]
+    f32, the importance-weighted WAIC records from psis_draws draws per sub-fit
+    (_lib.MAPWAIC_FIELDS) --, chunked
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
@@ -997,14 +1096,15 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     T = int(y.shape[0])
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace, with_diag=diag,
-                     with_summary=summary, with_loo=loo, with_psis=psis, psis_draws=psis_draws)
+                     with_summary=summary, with_loo=loo, with_psis=psis, psis_draws=psis_draws,
+                     with_waic=waic)
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
-        extra = got[3].copy() if laplace or diag or summary or loo or psis else None
+        extra = got[3].copy() if laplace or diag or summary or loo or psis or waic else None
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
-    if laplace or diag or summary or loo or psis:
+    if laplace or diag or summary or loo or psis or waic:
         return out, pred, status, extra
     return out, pred, status
 

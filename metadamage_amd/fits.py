@@ -106,6 +106,18 @@ MAP_PSIS_COLUMNS = [name for name, _, _ in _MAP_PSIS_PICKS]
 # ... then uint32 map_psis_valid (all three rows valid) and map_psis_reliable
 # (valid, and all three khat at or below the threshold)
 MAP_PSIS_UINT_COLUMNS = ["map_psis_valid", "map_psis_reliable"]
+# "map-waic": the importance-weighted WAIC comparison appended after shortname
+# (DESIGN.md §3.9), float32 -- (column, row of the record: 0 PMD-all, 1 null-all,
+# 6 the comparisons, its field index) ...
+_MAP_WAIC_PICKS = (
+    [("n_sigma_waic", 6, 0), ("n_sigma_waic_forward", 6, 1), ("n_sigma_waic_reverse", 6, 2), ("asymmetry_waic", 6, 3),
+     ("p_waic", 0, 1), ("p_waic_null", 1, 1), ("elpd_waic", 0, 0), ("elpd_waic_null", 1, 0),
+     ("pareto_k_waic", 6, 4), ("waic_ess_min", 6, 5)]
+)
+MAP_WAIC_COLUMNS = [name for name, _, _ in _MAP_WAIC_PICKS]
+# ... then uint32 map_waic_valid (row 6's bit 0: all six rows valid) and
+# map_waic_reliable (its bit 1: valid, and all six khat at or below the threshold)
+MAP_WAIC_UINT_COLUMNS = ["map_waic_valid", "map_waic_reliable"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -294,7 +306,8 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
-               summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256):
+               summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
+               waic: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -307,7 +320,9 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     the fit and the fourth array is the PSIS-LOO records loo[T, 7, 8] f32.
     psis (MAP): mdfit_map_psis follows the fit with psis_draws draws per sub-fit
     and the fourth array is the importance-sampled posteriors psis[T, 3, 16]
-    f32.  At most one of the five."""
+    f32.  waic (MAP): mdfit_map_waic follows the fit with psis_draws draws per
+    sub-fit and the fourth array is the importance-weighted WAIC records
+    waic[T, 7, 8] f32.  At most one of the six."""
     import torch
 
     from . import engine
@@ -331,17 +346,18 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     if not grouped:
         try:
             return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
-                                         summary=summary, loo=loo, psis=psis, psis_draws=psis_draws)
+                                         summary=summary, loo=loo, psis=psis, psis_draws=psis_draws, waic=waic)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws)
+        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic)
     finally:
         p.release_pinned()
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
-                 summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256):
+                 summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
+                 waic: bool = False):
     import torch
 
     from . import engine
@@ -353,21 +369,22 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
     rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                        with_psis=psis)
+                        with_psis=psis, with_waic=waic)
     if hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
         # records written in place into the gather buffers
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
                                 with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                                with_psis=psis, psis_draws=psis_draws)
+                                with_psis=psis, psis_draws=psis_draws, with_waic=waic)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                                                lap=rec.lap[: hi - lo] if laplace else None,
                                                diag=rec.diag[: hi - lo] if diag else None,
                                                summ=rec.summ[: hi - lo] if summary else None,
                                                loo=rec.loo[: hi - lo] if loo else None,
-                                               psis=rec.psis[: hi - lo] if psis else None))
+                                               psis=rec.psis[: hi - lo] if psis else None,
+                                               waic=rec.waic[: hi - lo] if waic else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -376,7 +393,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     if rank != 0:
         return None
     return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
-                           with_loo=loo, with_psis=psis)
+                           with_loo=loo, with_psis=psis, with_waic=waic)
 
 
 # --------------------------------------------------------------------------
@@ -433,7 +450,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
-                        psis=None) -> pd.DataFrame:
+                        psis=None, waic=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -448,7 +465,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     as float32, then pareto_k_bad and nuts_loo_valid (uint32).  psis (the
     importance-sampled posteriors [T, 3, 16] of a "map-psis" run): the
     MAP_PSIS_COLUMNS follow as float32, then map_psis_valid and
-    map_psis_reliable (uint32)."""
+    map_psis_reliable (uint32).  waic (the importance-weighted WAIC records [T,
+    7, 8] of a "map-waic" run): the MAP_WAIC_COLUMNS follow as float32, then
+    map_waic_valid and map_waic_reliable (uint32)."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -507,6 +526,14 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["map_psis_valid"] = valid.astype(np.uint32)
         data["map_psis_reliable"] = (valid & ((flags & _lib.MAPPSIS_RELIABLE) != 0).all(axis=1)).astype(np.uint32)
         columns += MAP_PSIS_COLUMNS + MAP_PSIS_UINT_COLUMNS
+    if waic is not None:
+        kw = np.asarray(waic) if keep is None else np.asarray(waic)[keep]
+        for name, row, field in _MAP_WAIC_PICKS:
+            data[name] = np.ascontiguousarray(kw[:, row, field], dtype=np.float32)
+        flags = np.nan_to_num(kw[:, 6, _lib.MAPWAIC_COMPARE_FIELDS.index("flags")]).astype(np.int64)
+        data["map_waic_valid"] = ((flags & _lib.MAPWAIC_VALID) != 0).astype(np.uint32)
+        data["map_waic_reliable"] = ((flags & _lib.MAPWAIC_RELIABLE) != 0).astype(np.uint32)
+        columns += MAP_WAIC_COLUMNS + MAP_WAIC_UINT_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
@@ -534,7 +561,8 @@ def make_opts(cfg, mcmc_kwargs=None):
     "nuts-summary" (the same call; wants_summary adds the posterior summaries),
     "nuts-loo" (the same call; wants_loo adds the PSIS-LOO model comparison), "map"
     "map-laplace" (the MAP fit; wants_laplace adds the standard errors) or
-    "map-psis" (the MAP fit; wants_psis adds the importance-sampled posterior)."""
+    "map-psis" (the MAP fit; wants_psis adds the importance-sampled posterior) or
+    "map-waic" (the MAP fit; wants_waic adds the importance-weighted WAIC comparison)."""
     inference = getattr(cfg, "inference", "nuts")
     if mode_of(inference) == _lib.MODE_MAP:
         return _lib.default_opts(mode=_lib.MODE_MAP)
@@ -547,13 +575,13 @@ def mode_of(inference: str) -> int:
     """The engine mode of an --inference value: "nuts", "nuts-diag",
     "nuts-summary" and "nuts-loo" (the sampler; wants_diag adds mdfit_nuts_diag,
     wants_summary mdfit_nuts_summary, wants_loo mdfit_nuts_loo) or "map" and
-    "map-laplace" and "map-psis"."""
-    if inference in ("map", "map-laplace", "map-psis"):
+    "map-laplace", "map-psis" and "map-waic"."""
+    if inference in ("map", "map-laplace", "map-psis", "map-waic"):
         return _lib.MODE_MAP
     if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo"):
         return _lib.MODE_NUTS
-    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'nuts-diag', 'nuts-summary' or "
-                     "'nuts-loo', "
+    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'map-waic', 'nuts-diag', "
+                     "'nuts-summary' or 'nuts-loo', "
                      f"got {inference!r}")
 
 
@@ -582,8 +610,13 @@ def wants_psis(cfg) -> bool:
     return getattr(cfg, "inference", "nuts") == "map-psis"
 
 
+def wants_waic(cfg) -> bool:
+    """cfg.inference "map-waic": the MAP fit followed by mdfit_map_waic."""
+    return getattr(cfg, "inference", "nuts") == "map-waic"
+
+
 def psis_draws_of(cfg) -> int:
-    """The draws per sub-fit of a "map-psis" run (cfg.psis_draws, default 256)."""
+    """The draws per sub-fit of a "map-psis" or "map-waic" run (cfg.psis_draws, default 256)."""
     return int(getattr(cfg, "psis_draws", 256) or 256)
 
 
@@ -597,7 +630,7 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     p = pack_counts(df_counts, cfg)
     res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
                      summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
-                     psis_draws=psis_draws_of(cfg))
+                     psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
@@ -606,10 +639,11 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     summ = rest[0] if rest and wants_summary(cfg) else None
     loo = rest[0] if rest and wants_loo(cfg) else None
     psis = rest[0] if rest and wants_psis(cfg) else None
+    waic = rest[0] if rest and wants_waic(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis),
+    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic),
             make_df_fit_predictions(p, pred, keep, cfg))
 
 
@@ -706,7 +740,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
                      laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
-                     loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg))
+                     loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
@@ -715,6 +749,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     summ = rest[0] if rest and wants_summary(cfg) else None
     loo = rest[0] if rest and wants_loo(cfg) else None
     psis = rest[0] if rest and wants_psis(cfg) else None
+    waic = rest[0] if rest and wants_waic(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -722,7 +757,8 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     def finish():
         from .counts import _save
 
-        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis)
+        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis,
+                                             waic=waic)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
