@@ -180,6 +180,66 @@ int mdfit_fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm,
 int64_t mdfit_workspace_bytes(int64_t n_taxa, const mdfit_opts* opts);
 
 /*
+ * mdfit_fit_batch in MDFIT_MODE_NUTS with the random streams of each row keyed
+ * by a global taxon index the caller gives (MDFIT-AUTO v1):
+ *   taxon_index : const int64_t[n_taxa], every entry >= 0 (device), or NULL
+ * Row t's Philox streams -- the chain's, at its start, and the predictive
+ * draws' of the record assembly -- are keyed by opts->index_base +
+ * taxon_index[t] instead of opts->index_base + t.  Everything else is row t's:
+ * the rows of y, N, mm, out, pred, status, the draws in the workspace
+ * (mdfit_workspace_bytes(n_taxa, opts) bytes) and the work queues.  So fitting
+ * the rows idx of a batch with taxon_index = idx gives the rows idx of the full
+ * call bit for bit -- record, predictions, status and draws.  Duplicate
+ * indices are allowed and draw the same numbers.  taxon_index == NULL is
+ * exactly mdfit_fit_batch (which launches the same kernels as it always did);
+ * MDFIT_MODE_MAP with a non-NULL index returns MDFIT_E_ARG (the MAP fit draws
+ * nothing).  The index is read once per chain start and once per taxon of the
+ * record assembly; the sampler's inner loop is the plain call's.
+ * mdfit_nuts_diag, mdfit_nuts_summary and mdfit_nuts_loo draw nothing: they
+ * work on the workspace and records of an indexed call unchanged, row by row.
+ */
+int mdfit_fit_batch_indexed(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa,
+                            const int64_t* taxon_index, const mdfit_opts* opts, double* out, float* pred,
+                            int32_t* status, void* workspace, void* hip_stream);
+
+/* Route bits of mdfit_auto_route (route[t]); the taxon goes to the sampler iff
+ * route & MDFIT_ROUTE_SAMPLE is non-zero. */
+#define MDFIT_ROUTE_WAIC 1    /* row 6 of the waic record lacks bit 1 (not all six rows valid and reliable) */
+#define MDFIT_ROUTE_PSIS 2    /* some row 0..2 of the psis record lacks bit 0 or bit 1 */
+#define MDFIT_ROUTE_STATUS 4  /* status[t] is MDFIT_MAXITER or MDFIT_NONFINITE */
+#define MDFIT_ROUTE_INVALID 8 /* status[t] == MDFIT_INVALID: not sampled, its NaN record left alone, no other bit */
+#define MDFIT_ROUTE_SAMPLE 7
+
+/*
+ * The routing rule of the auto inference (MDFIT-AUTO v1): which
+ * taxa of a finished MODE_MAP call the importance sampling settles, and their
+ * record.
+ *   status, psis, waic : that call's status[n_taxa], its mdfit_map_psis records
+ *                [n_taxa][3][MDFIT_NMAPPSIS] and its mdfit_map_waic records
+ *                [n_taxa][7][MDFIT_NMAPWAIC], the two from the same num_draws,
+ *                seed and index_base (device; read only)
+ *   out        : that call's records double[n_taxa][MDFIT_NOUT] (device).  For a
+ *                taxon with route 0 nine result columns are overwritten with the
+ *                importance-sampled posterior statistics, copied exactly:
+ *                q_mean, concentration_mean, D_max_marginalized_mean <- psis
+ *                row 0 q_mean, phi_mean, D_max_mean; q_mean_forward,
+ *                q_mean_reverse <- psis rows 1, 2 q_mean; n_sigma,
+ *                n_sigma_forward, n_sigma_reverse, asymmetry <- waic row 6
+ *                fields 0..3.  Every other field, and every field of a taxon
+ *                with route != 0, is left as the MAP call wrote it (D_max, its
+ *                HPDI bounds, D_max_forward / _reverse and pred are predictive
+ *                quantities, exact at the mode).
+ *   route      : int32_t[n_taxa], the MDFIT_ROUTE_* bits             (device)
+ * By the bit-for-bit identity of the PMD rows of the two records,
+ * MDFIT_ROUTE_PSIS is never set without MDFIT_ROUTE_WAIC on records of one
+ * call; the rule checks it regardless.  One launch on hip_stream, one thread
+ * per taxon; no workspace, no atomics, no host synchronisation.  n_taxa: at
+ * most 2^25 per call.
+ */
+int mdfit_auto_route(const int32_t* status, const double* psis, const double* waic, int64_t n_taxa,
+                     double* out, int32_t* route, void* hip_stream);
+
+/*
  * Noise columns of records fitted with mm = NULL (both modes): the three
  * normalized_noise columns of out[n_taxa][MDFIT_NOUT] from the mismatch counts
  * mm[n_taxa][30][12] (add_noise_estimates, fits.py:359-376) -- the values a

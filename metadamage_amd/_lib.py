@@ -97,10 +97,21 @@ MAPWAIC_COMPARE_FIELDS = ["n_sigma_waic", "n_sigma_waic_forward", "n_sigma_waic_
                           "ess_min", "reserved", "flags"]
 MAPWAIC_VALID, MAPWAIC_RELIABLE = 1, 2  # flags: bit 0 valid, bit 1 khat <= threshold; rows 0..5: bits 2..5 free
 
+# route bits of mdfit_auto_route (MDFIT_ROUTE_*): the taxon is sampled iff route & ROUTE_SAMPLE
+ROUTE_WAIC, ROUTE_PSIS, ROUTE_STATUS, ROUTE_INVALID, ROUTE_SAMPLE = 1, 2, 4, 8, 7
+# the nine result columns mdfit_auto_route composes for a taxon with route 0
+AUTO_COMPOSED_FIELDS = ["q_mean", "concentration_mean", "D_max_marginalized_mean", "q_mean_forward",
+                        "q_mean_reverse", "n_sigma", "n_sigma_forward", "n_sigma_reverse", "asymmetry"]
+# the auto block that leaves the device (engine.fit_auto_device): float32 [T][NAUTO]
+NAUTO = 4
+AUTO_FIELDS = ["route", "sampled", "khat_max", "ess_min"]
+
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
     "mdfit_default_opts",
     "mdfit_fit_batch",
+    "mdfit_fit_batch_indexed",
+    "mdfit_auto_route",
     "mdfit_workspace_bytes",
     "mdfit_noise",
     "mdfit_map_laplace",
@@ -173,6 +184,10 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_default_opts.restype = None
     lib.mdfit_fit_batch.argtypes = [vp, vp, vp, i64, ctypes.POINTER(MdfitOpts), vp, vp, vp, vp, vp]
     lib.mdfit_fit_batch.restype = ctypes.c_int
+    lib.mdfit_fit_batch_indexed.argtypes = [vp, vp, vp, i64, vp, ctypes.POINTER(MdfitOpts), vp, vp, vp, vp, vp]
+    lib.mdfit_fit_batch_indexed.restype = ctypes.c_int
+    lib.mdfit_auto_route.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    lib.mdfit_auto_route.restype = ctypes.c_int
     lib.mdfit_workspace_bytes.argtypes = [i64, ctypes.c_void_p]
     if hasattr(lib, "mdfit_nuts_potential"):
         lib.mdfit_nuts_potential.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]

@@ -58,8 +58,10 @@ def cli_fit(
                                   "nuts-summary: NUTS with posterior std, median, 68 % HPDI and significance; "
                                   "nuts-loo: NUTS with PSIS-LOO model comparison and Pareto-k diagnostics; "
                                   "map-psis: MAP fit with an importance-sampled posterior and its Pareto-k; "
-                                  "map-waic: MAP fit with importance-weighted WAIC n_sigma and asymmetry"),
-    psis_draws: int = typer.Option(256, help="map-psis, map-waic: importance draws per sub-fit, 25 to 1024"),
+                                  "map-waic: MAP fit with importance-weighted WAIC n_sigma and asymmetry; "
+                                  "auto: MAP fit with its importance-sampled correction, NUTS only for the taxa "
+                                  "whose Pareto-k says it cannot be trusted"),
+    psis_draws: int = typer.Option(256, help="map-psis, map-waic, auto: importance draws per sub-fit, 25 to 1024"),
 ):
     """Fitting Ancient Damage.
 
@@ -83,9 +85,9 @@ def cli_fit(
         "psis_draws": psis_draws,
     }
     if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "nuts-diag", "nuts-summary",
-                         "nuts-loo"):
+                         "nuts-loo", "auto"):
         raise typer.BadParameter("--inference must be nuts, map, map-laplace, map-psis, map-waic, nuts-diag, "
-                                 "nuts-summary or nuts-loo")
+                                 "nuts-summary, nuts-loo or auto")
     if not 25 <= psis_draws <= 1024:
         raise typer.BadParameter("--psis-draws must be in [25, 1024]")
     cfg = utils.Config(**d_cfg)

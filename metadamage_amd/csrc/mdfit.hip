@@ -39,6 +39,7 @@
 #include <mutex>
 
 #include "../../include/mdfit.h"
+#include "mdfit_auto.h"
 #include "mdfit_hpdi.h"
 #include "mdfit_host.h"
 #include "mdfit_laplace.h"
@@ -1572,6 +1573,16 @@ __global__ __launch_bounds__(kWave) void objective_kernel(
   else objective_group<kFR>(gy, gN, i, pmd, subset[i] == 2, u, F, g, H, ell_out);
 }
 
+// MDFIT-AUTO v1 (mdfit_auto_route): one thread per taxon, the rule and the
+// nine copies of csrc/mdfit_auto.h
+__global__ __launch_bounds__(256) void auto_route_kernel(const int32_t* __restrict__ status,
+                                                         const double* __restrict__ psis,
+                                                         const double* __restrict__ waic, int64_t n_taxa,
+                                                         double* __restrict__ out, int32_t* __restrict__ route) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n_taxa) autoroute::route_one(t, status, psis, waic, out, route);
+}
+
 }  // namespace mdfit
 
 // ===========================================================================
@@ -1808,7 +1819,16 @@ int64_t mdfit_workspace_bytes(int64_t n_taxa, const mdfit_opts* opts) {
 int mdfit_fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa,
                     const mdfit_opts* opts, double* out, float* pred, int32_t* status,
                     void* workspace, void* hip_stream) {
+  return mdfit_fit_batch_indexed(y, N, mm, n_taxa, nullptr, opts, out, pred, status, workspace, hip_stream);
+}
+
+int mdfit_fit_batch_indexed(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa,
+                            const int64_t* taxon_index, const mdfit_opts* opts, double* out, float* pred,
+                            int32_t* status, void* workspace, void* hip_stream) {
   if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  // (the MAP fit draws nothing: an index would promise streams that are not there)
+  if (taxon_index != nullptr && (opts ? opts->mode : MDFIT_MODE_MAP) == MDFIT_MODE_MAP)
+    return set_err(MDFIT_E_ARG, "taxon_index needs opts->mode == MDFIT_MODE_NUTS");
   if (n_taxa == 0) return 0;
   if (!y || !N || !out || !status) return set_err(MDFIT_E_ARG, "null required pointer");
   if (!workspace) return set_err(MDFIT_E_ARG, "workspace (mdfit_workspace_bytes() bytes) required");
@@ -1825,7 +1845,7 @@ int mdfit_fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, in
   prof_record(0, s);
   if (o.mode == MDFIT_MODE_NUTS) {
     if (hipMemsetAsync(ws, 0, 256, s) != hipSuccess) return check_launch("hipMemsetAsync(workspace)");
-    if (int rc = mdfit::nuts::fit_batch(y, N, mm, n_taxa, o, out, pred, status, workspace, s)) return rc;
+    if (int rc = mdfit::nuts::fit_batch(y, N, mm, n_taxa, o, out, pred, status, workspace, s, taxon_index)) return rc;
     prof_record(3, s);
     if (g_prof.on && g_prof.n < kProfMax) ++g_prof.n;
     return 0;
@@ -2104,6 +2124,17 @@ int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, cons
                      (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
                      seed, index_base, mp::khat_threshold(S), waic, pointwise, draws);
   return check_launch("map_waic_kernel");
+}
+
+int mdfit_auto_route(const int32_t* status, const double* psis, const double* waic, int64_t n_taxa, double* out,
+                     int32_t* route, void* hip_stream) {
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (n_taxa == 0) return 0;
+  if (!status || !psis || !waic || !out || !route) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  hipLaunchKernelGGL(mdfit::auto_route_kernel, dim3((unsigned)((n_taxa + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, status, psis, waic, n_taxa, out, route);
+  return check_launch("auto_route_kernel");
 }
 
 int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w, double* khat, void* hip_stream) {

@@ -73,9 +73,14 @@ int64_t workspace_bytes(int64_t n_taxa, int num_samples);
 int peak_probe(int64_t n_waves, int iters, double* sink, hipStream_t s);
 int potential(const int32_t* model, const int32_t* subset, const uint32_t* y, const uint32_t* N, const double* v,
               int64_t n, double* U, double* g, hipStream_t s);
-// launches the chain and post-processing kernels (workspace already zeroed)
+// launches the chain and post-processing kernels (workspace already zeroed);
+// taxon_index (device int64[n_taxa], or null): row t's streams are keyed by
+// index_base + taxon_index[t] instead of index_base + t -- the INDEXED
+// instantiations of both kernels (mdfit_fit_batch_indexed); null launches the
+// plain ones
 int fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts& o,
-              double* out, float* pred, int32_t* status, void* workspace, hipStream_t s);
+              double* out, float* pred, int32_t* status, void* workspace, hipStream_t s,
+              const int64_t* taxon_index = nullptr);
 // MDFIT-DIAG v1 of the chains a finished fit_batch left in `workspace`: one
 // launch, reads the draws and out's chain status slots, writes
 // diag[n_taxa][6][MDFIT_NNUTSDIAG]

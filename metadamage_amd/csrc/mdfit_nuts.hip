@@ -527,7 +527,38 @@ struct ColdState {
 #endif
 };
 
-template <int PPL>
+// The stream key of row t (mdfit_fit_batch_indexed): the plain instantiation
+// <false> is an empty struct and keys by the row itself, from the source lines
+// it always had; <true> reads the caller's global index of the row -- once per
+// chain start in the chain kernel, once per taxon in the post kernel.
+template <bool INDEXED>
+struct TaxonKey {
+  __device__ __forceinline__ int64_t of(int64_t t) const { return t; }
+  __device__ __forceinline__ int64_t of_chain(const int*, int64_t t) const { return t; }
+};
+// The chain kernel takes no index argument: a pointer held across its loop cost
+// the INDEXED instantiation 2 SGPR and 8 more VGPR spills at the pinned 4
+// waves/SIMD.  The host leaves the pointer in the workspace header instead
+// (int slots kIndexSlot, kIndexSlot + 1: bytes 192..199, behind the queue
+// counters and the utilisation sums), and a chain's start -- once per ~1e4
+// trips -- reads it from there through the `ws` the kernel holds anyway.
+constexpr int kIndexSlot = 48;
+template <>
+struct TaxonKey<true> {
+  const int64_t* index;  // [T], every entry >= 0
+  __device__ __forceinline__ int64_t of(int64_t t) const { return index[t]; }
+  __device__ __forceinline__ int64_t of_chain(const int* ws, int64_t t) const {
+    const uint64_t p = (uint64_t)(uint32_t)ws[kIndexSlot] | ((uint64_t)(uint32_t)ws[kIndexSlot + 1] << 32);
+    return reinterpret_cast<const int64_t*>(p)[t];
+  }
+};
+__global__ void nuts_index_slot_kernel(int* __restrict__ ws, const int64_t* index) {
+  const uint64_t p = reinterpret_cast<uint64_t>(index);
+  ws[kIndexSlot] = (int)(uint32_t)p;
+  ws[kIndexSlot + 1] = (int)(uint32_t)(p >> 32);
+}
+
+template <int PPL, bool INDEXED = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_NUTS_CD_WAVES))) void nuts_chain_cd(
     const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN, int64_t T, mdfit_opts o,
     double* __restrict__ out, int* __restrict__ ws, double* __restrict__ samples) {
@@ -724,7 +755,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_NUT
         pq[p].y = pq[p].valid ? gy[taxon * kLD + colv] : 0u;
         pq[p].N = pq[p].valid ? gN[taxon * kLD + colv] : 0u;
       }
-      C.st = make_stream(o.seed, o.index_base + taxon, sub);
+      C.st = make_stream(o.seed, o.index_base + TaxonKey<INDEXED>{}.of_chain(ws, taxon), sub);
       C.nm_chunk = C.db_chunk = -1;
 #ifndef MDFIT_NO_UTIL
       C.t_start = (double)util_trips;
@@ -1498,13 +1529,14 @@ struct PostTap<true> {
   uint8_t* flags;    // [T][32]: 0 counts, 1 some draw was no count, 2 skipped for N = 0 (pre-filled 0xFF), or null
 };
 
-template <bool kTap>
+template <bool kTap, bool INDEXED = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_POST_WAVES))) void nuts_post_kernel(const uint32_t* __restrict__ gy,
                                                           const uint32_t* __restrict__ gN,
                                                           const uint32_t* __restrict__ gmm, int64_t n_taxa,
                                                           mdfit_opts o, const double* __restrict__ samples,
                                                           double* __restrict__ out, float* __restrict__ pred,
-                                                          int32_t* __restrict__ status, PostTap<kTap> tap) {
+                                                          int32_t* __restrict__ status, PostTap<kTap> tap,
+                                                          TaxonKey<INDEXED> key) {
   __shared__ double s_y[kLD], s_N[kLD];
   __shared__ double s_rec[MDFIT_NOUT];
   __shared__ double s_waic[MDFIT_NSUBFIT][kNPos];
@@ -1696,6 +1728,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_POS
   // ---- posterior predictive median / HPDI (fits.py:89-120) ---------------------
   // columns 0..29 of the PMD-all chain, then position 0 of data_forward under the
   // forward and the reverse PMD chains (the latter is the :343-348 quirk)
+  const int64_t gt = key.of(t);  // the streams' taxon: the row, or (INDEXED) its global index, read once
   for (int job = 0; job < kNPos + 2; ++job) {
     const int s = job < kNPos ? 0 : job - kNPos + 2;
     const int col = job < kNPos ? job : 0;
@@ -1713,7 +1746,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(MDFIT_POS
         if (tap.flags != nullptr && lane == 0) tap.flags[t * kLD + job] = 2;
       }
     } else {
-      const Stream st = make_stream(o.seed, o.index_base + t, s);
+      const Stream st = make_stream(o.seed, o.index_base + gt, s);
       bool bad = false;
       for (int x = lane; x < S; x += kWave) {
         const int64_t cnt = predictive_count(st, x, col, k, nn, smp + ((int64_t)s * S + x) * 4);
@@ -2290,12 +2323,42 @@ int post(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_tax
     return host::check_launch("hipMemsetAsync(count_flags)");
   host::debug_poison(s);
   hipLaunchKernelGGL(nuts_post_kernel<true>, dim3((unsigned)n_taxa), dim3(kWave), post_lds_bytes(S), s, y, N, mm,
-                     n_taxa, o, samples, out, pred, status, PostTap<true>{waic, counts, count_flags});
+                     n_taxa, o, samples, out, pred, status, PostTap<true>{waic, counts, count_flags},
+                     TaxonKey<false>{});
   return host::check_launch("nuts_post_kernel<tap>");
 }
 
+// the two launches of a sampling call, plain (TaxonKey<false>: the kernels
+// mdfit_fit_batch always launched) or INDEXED (mdfit_fit_batch_indexed)
+template <bool INDEXED>
+static int launch_fit(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts& o,
+                      double* out, float* pred, int32_t* status, int* ws, double* samples, hipStream_t s,
+                      TaxonKey<INDEXED> key) {
+  constexpr int kPPL = 1;  // (PPL 2, two points per lane: 0.91x at C3, DESIGN_HISTORY)
+  // (MDFIT_DEV_PER_CU: waves per CU forced, development A/B; the chain
+  // kernel's waves never wait on each other, so any grid drains)
+  const char* force = std::getenv("MDFIT_DEV_PER_CU");
+  auto chain = nuts_chain_cd<kPPL, INDEXED>;
+  const int64_t g = host::fit_grid(chain, 4 * n_taxa, kPPL == 1 ? 2 : 4, 0, force ? std::atoi(force) : 0);
+  if constexpr (INDEXED) {  // (the header was zeroed on s just before)
+    hipLaunchKernelGGL(nuts_index_slot_kernel, dim3(1), dim3(1), 0, s, ws, key.index);
+    if (int rc = host::check_launch("nuts_index_slot_kernel")) return rc;
+  }
+  host::prof_mark(1, s);
+  host::debug_poison(s);
+  hipLaunchKernelGGL(chain, dim3((unsigned)g), dim3(kWave), 0, s, y, N, n_taxa, o, out, ws, samples);
+  if (int rc = host::check_launch("nuts_chain_cd")) return rc;
+  host::prof_mark(2, s);
+  host::debug_poison(s);
+  hipLaunchKernelGGL((nuts_post_kernel<false, INDEXED>), dim3((unsigned)n_taxa), dim3(kWave),
+                     post_lds_bytes(o.num_samples), s, y, N, mm, n_taxa, o, samples, out, pred, status,
+                     PostTap<false>{}, key);
+  return host::check_launch("nuts_post_kernel");
+}
+
 int fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts& o,
-              double* out, float* pred, int32_t* status, void* workspace, hipStream_t s) {
+              double* out, float* pred, int32_t* status, void* workspace, hipStream_t s,
+              const int64_t* taxon_index) {
   if (o.num_samples < 2 || o.num_samples > kMaxSamples)
     return host::set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
   if (o.num_warmup < 0) return host::set_err(MDFIT_E_ARG, "num_warmup < 0");
@@ -2304,21 +2367,9 @@ int fit_batch(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t 
   // diag slots 4..7 are written by the chains; zero the record first
   if (hipMemsetAsync(out, 0, (size_t)n_taxa * MDFIT_NOUT * sizeof(double), s) != hipSuccess)
     return host::check_launch("hipMemsetAsync(out)");
-  constexpr int kPPL = 1;  // (PPL 2, two points per lane: 0.91x at C3, DESIGN_HISTORY)
-  // (MDFIT_DEV_PER_CU: waves per CU forced, development A/B; the chain
-  // kernel's waves never wait on each other, so any grid drains)
-  const char* force = std::getenv("MDFIT_DEV_PER_CU");
-  auto chain = nuts_chain_cd<kPPL>;
-  const int64_t g = host::fit_grid(chain, 4 * n_taxa, kPPL == 1 ? 2 : 4, 0, force ? std::atoi(force) : 0);
-  host::prof_mark(1, s);
-  host::debug_poison(s);
-  hipLaunchKernelGGL(chain, dim3((unsigned)g), dim3(kWave), 0, s, y, N, n_taxa, o, out, ws, samples);
-  if (int rc = host::check_launch("nuts_chain_cd")) return rc;
-  host::prof_mark(2, s);
-  host::debug_poison(s);
-  hipLaunchKernelGGL(nuts_post_kernel<false>, dim3((unsigned)n_taxa), dim3(kWave), post_lds_bytes(o.num_samples), s,
-                     y, N, mm, n_taxa, o, samples, out, pred, status, PostTap<false>{});
-  return host::check_launch("nuts_post_kernel");
+  if (taxon_index != nullptr)
+    return launch_fit<true>(y, N, mm, n_taxa, o, out, pred, status, ws, samples, s, TaxonKey<true>{taxon_index});
+  return launch_fit<false>(y, N, mm, n_taxa, o, out, pred, status, ws, samples, s, TaxonKey<false>{});
 }
 
 }  // namespace mdfit::nuts

@@ -53,10 +53,18 @@ REC_PSIS = 3 * _lib.NMAPPSIS * 4
 # with_waic (a "map-waic" run; never together with any of them): the same for the
 # importance-weighted WAIC records, one more f32 block [n, 7, NMAPWAIC], 224 B per taxon
 REC_WAIC = _lib.NWAICROW * _lib.NMAPWAIC * 4
+# with_auto (an "auto" run; never together with any of them): the same for the
+# auto block, one more f32 block [n, NAUTO] = route, sampled, khat_max, ess_min, 16 B per taxon
+REC_AUTO = _lib.NAUTO * 4
 
 
 def _extra(with_laplace: bool, with_diag: bool, with_summary: bool = False, with_loo: bool = False,
-           with_psis: bool = False, with_waic: bool = False) -> int:
+           with_psis: bool = False, with_waic: bool = False, with_auto: bool = False) -> int:
+    if with_auto:
+        if with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic:
+            raise ValueError("with_auto, with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace "
+                             "are mutually exclusive: one extra block per run")
+        return REC_AUTO
     if with_waic:
         if with_laplace or with_diag or with_summary or with_loo or with_psis:
             raise ValueError("with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace are mutually "
@@ -107,19 +115,22 @@ class Records:
     bytes, `diag` f32[n, 6, 12]; with_summary: n * REC_SUMM bytes, `summ` f32[n,
     6, 16]; with_loo: n * REC_LOO bytes, `loo` f32[n, 7, 8]; with_psis: n *
     REC_PSIS bytes, `psis` f32[n, 3, 16]; with_waic: n * REC_WAIC bytes, `waic`
-    f32[n, 7, 8].  At most one of the six."""
+    f32[n, 7, 8]; with_auto: n * REC_AUTO bytes, `auto` f32[n, 4].  At most one
+    of the seven."""
 
     def __init__(self, n: int, device, with_laplace: bool = False, with_diag: bool = False,
                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                 with_waic: bool = False):
+                 with_waic: bool = False, with_auto: bool = False):
         import torch
 
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
         self.buf = torch.empty(n * (REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis,
-                                                       with_waic)), dtype=torch.uint8, device=device)
-        self.lap = self.diag = self.summ = self.loo = self.psis = self.waic = None
-        if with_laplace:
+                                                       with_waic, with_auto)), dtype=torch.uint8, device=device)
+        self.lap = self.diag = self.summ = self.loo = self.psis = self.waic = self.auto = None
+        if with_auto:
+            self.pred, self.status, self.ints, self.floats, self.auto = packed_views(self.buf, n, with_auto=True)
+        elif with_laplace:
             self.pred, self.status, self.ints, self.floats, self.lap = packed_views(self.buf, n, with_laplace=True)
         elif with_diag:
             self.pred, self.status, self.ints, self.floats, self.diag = packed_views(self.buf, n, with_diag=True)
@@ -142,7 +153,7 @@ class Records:
 
 
 def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False):
+                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False, with_auto: bool = False):
     """Views (pred[n, 3, 30] f32, status[n] i32, ints[n, 8] f64, floats[n, 17]
     f32) into one uint8 gather buffer of n * REC_BYTES bytes laid out ints |
     floats | pred | status (torch tensor; the f64 block first keeps it 8-byte
@@ -152,8 +163,9 @@ def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = Fals
     * REC_SUMM more bytes and the fifth view is summ[n, 6, 16] f32; with_loo: n *
     REC_LOO more bytes and the fifth view is loo[n, 7, 8] f32; with_psis: n *
     REC_PSIS more bytes and the fifth view is psis[n, 3, 16] f32; with_waic: n *
-    REC_WAIC more bytes and the fifth view is waic[n, 7, 8] f32."""
-    _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
+    REC_WAIC more bytes and the fifth view is waic[n, 7, 8] f32; with_auto: n *
+    REC_AUTO more bytes and the fifth view is auto[n, 4] f32."""
+    _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto)
     o1 = n * REC_INT
     o2 = o1 + n * REC_F32
     o3 = o2 + n * REC_PRED
@@ -161,6 +173,10 @@ def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = Fals
     floats = buf[o1:o2].view(dtype=_torch_dtype("float32")).view(n, len(FLOAT_COLS))
     pred = buf[o2:o3].view(dtype=_torch_dtype("float32")).view(n, _lib.NPRED, _lib.NPOS)
     status = buf[o3 : o3 + 4 * n].view(dtype=_torch_dtype("int32"))
+    if with_auto:
+        o4 = o3 + 4 * n
+        auto = buf[o4 : o4 + n * REC_AUTO].view(dtype=_torch_dtype("float32")).view(n, _lib.NAUTO)
+        return pred, status, ints, floats, auto
     if with_laplace:
         o4 = o3 + 4 * n
         lap = buf[o4 : o4 + n * REC_LAP].view(dtype=_torch_dtype("float32")).view(n, 3, _lib.NLAPLACE)
@@ -204,8 +220,8 @@ def _torch_dtype(name):
 
 def alloc_records(n: int, device, with_laplace: bool = False, with_diag: bool = False,
                   with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                  with_waic: bool = False) -> Records:
-    return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
+                  with_waic: bool = False, with_auto: bool = False) -> Records:
+    return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto)
 
 
 def gather_records(buf, n_cap: int, rank: int, world: int, group=None, async_op: bool = False):
@@ -312,7 +328,7 @@ def run_distributed(fn, *args, **kwargs):
 
 def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, with_diag: bool = False,
                     with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                    with_waic: bool = False):
+                    with_waic: bool = False, with_auto: bool = False):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  with_laplace: the
     parts carry the Laplace block and a fourth array lap[T, 3, 8] f32 is returned;
@@ -320,12 +336,13 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
     with_summary: the summaries block, returned as summ[T, 6, 16] f32; with_loo:
     the PSIS-LOO block, returned as loo[T, 7, 8] f32; with_psis: the
     importance-sampled posteriors, returned as psis[T, 3, 16] f32; with_waic: the
-    importance-weighted WAIC records, returned as waic[T, 7, 8] f32."""
+    importance-weighted WAIC records, returned as waic[T, 7, 8] f32; with_auto:
+    the auto block, returned as auto[T, 4] f32."""
     import torch
 
     outs, preds, sts, laps = [], [], [], []
-    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
-    extra = with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic
+    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto)
+    extra = with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic or with_auto
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)
@@ -344,7 +361,7 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
         n_cap = part.numel() // rec_bytes
         p, s, ints, floats, *rest = packed_views(part, n_cap, with_laplace=with_laplace, with_diag=with_diag,
                                                  with_summary=with_summary, with_loo=with_loo, with_psis=with_psis,
-                                                 with_waic=with_waic)
+                                                 with_waic=with_waic, with_auto=with_auto)
         if extra:
             laps.append(rest[0][: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)

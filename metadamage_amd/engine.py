@@ -43,6 +43,7 @@ class FitBatch:
     loo: "object" = None  # torch.float32 [T, 7, NNUTSLOO]: the PSIS-LOO records (ChunkedFitter with_loo)
     psis: "object" = None  # torch.float32 [T, 3, NMAPPSIS]: the importance-sampled posteriors (ChunkedFitter with_psis)
     waic: "object" = None  # torch.float32 [T, 7, NMAPWAIC]: the importance-weighted WAIC records (with_waic)
+    auto: "object" = None  # torch.float32 [T, NAUTO]: route, sampled, khat_max, ess_min (fit_auto_chunks)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -225,6 +226,213 @@ def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
                                   _stream_handle(torch, stream)))
     got = (waic,) + tuple(x for x in (pointwise, draws) if x is not None)
     return waic if len(got) == 1 else got
+
+
+def fit_batch_indexed_device(ty, tN, tm, taxon_index, opts: _lib.MdfitOpts, res: FitBatch | None = None,
+                             stream=None) -> FitBatch:
+    """Launch mdfit_fit_batch_indexed on device tensors (asynchronous on
+    `stream`): the sampling call whose row t draws from the streams of the
+    global taxon opts.index_base + taxon_index[t] (int64 [T] on the device, or
+    None: mdfit_fit_batch itself), so that rows idx of a batch fitted with
+    taxon_index = idx are the rows idx of the full call bit for bit."""
+    torch = _torch()
+    lib = _lib.load()
+    T = int(ty.shape[0])
+    for name, t in (("y", ty), ("N", tN)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == (T, _lib.LD)):
+            raise ValueError(f"{name} must be a contiguous cuda int32/uint32 view of shape [T, {_lib.LD}]")
+    if tm is not None and not (tm.is_cuda and tm.is_contiguous() and tm.numel() == T * _lib.NPOS * _lib.NMM):
+        raise ValueError("mm must be a contiguous cuda tensor of T*30*12 uint32")
+    if taxon_index is not None:
+        if not (taxon_index.is_cuda and taxon_index.is_contiguous() and taxon_index.dtype == torch.int64
+                and taxon_index.numel() == T):
+            raise ValueError("taxon_index must be a contiguous cuda int64 tensor of T entries")
+    if res is None:
+        res = alloc_outputs(T, device=ty.device, opts=opts)
+    if res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts):
+        res.workspace = alloc_workspace(T, ty.device, opts)
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) >= T
+            and (res.pred is None or res.pred.is_contiguous())):
+        raise ValueError("res must hold contiguous records of at least T taxa")
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    _lib.check(lib.mdfit_fit_batch_indexed(ptr(ty), ptr(tN), ptr(tm), T, ptr(taxon_index), ctypes.byref(opts),
+                                           ptr(res.out), ptr(res.pred), ptr(res.status), ptr(res.workspace),
+                                           _stream_handle(torch, stream)))
+    return res
+
+
+def auto_route_device(res: FitBatch, psis, waic, route=None, stream=None):
+    """Launch mdfit_auto_route on the records of a finished MAP call and its
+    mdfit_map_psis / mdfit_map_waic records (float64 [T, 3, NMAPPSIS] and [T, 7,
+    NMAPWAIC]; asynchronous on `stream`): writes route int32 [T] (_lib.ROUTE_*)
+    and composes res.out's row of every taxon with route 0 in place.  Returns
+    route."""
+    torch = _torch()
+    lib = _lib.load()
+    T = int(res.out.shape[0])
+    if route is None:
+        route = torch.empty((T,), dtype=torch.int32, device=res.out.device)
+    for name, t, n in (("psis", psis, T * 3 * _lib.NMAPPSIS), ("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
+    if not (route.is_cuda and route.is_contiguous() and route.dtype == torch.int32 and route.numel() == T):
+        raise ValueError("route must be a contiguous cuda int32 tensor of T entries")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and res.status.numel() == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    _lib.check(lib.mdfit_auto_route(ctypes.c_void_p(res.status.data_ptr()), ctypes.c_void_p(psis.data_ptr()),
+                                    ctypes.c_void_p(waic.data_ptr()), T, ctypes.c_void_p(res.out.data_ptr()),
+                                    ctypes.c_void_p(route.data_ptr()), _stream_handle(torch, stream)))
+    return route
+
+
+AUTO_BYTES = _lib.NAUTO * 4  # one taxon's auto block on the way out: f32 (route, sampled, khat_max, ess_min)
+AUTO_STAGES = ("map", "psis", "waic", "route", "gather", "sampler", "scatter")
+
+
+def auto_opts(opts: _lib.MdfitOpts | None):
+    """The two option sets of an auto call, copies of one (None: the defaults):
+    (MAP, NUTS) -- mode differs; max_iter / tol_step, seed / num_warmup /
+    num_samples and index_base are shared."""
+    o = opts if opts is not None else _lib.default_opts()
+    o_map, o_nuts = _lib.MdfitOpts.from_buffer_copy(o), _lib.MdfitOpts.from_buffer_copy(o)
+    o_map.mode, o_nuts.mode = _lib.MODE_MAP, _lib.MODE_NUTS
+    return o_map, o_nuts
+
+
+def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_draws: int = 256,
+                    res: FitBatch | None = None, stream=None, budget_bytes: int | None = None,
+                    sub_chunk_taxa: int = 0, timings: dict | None = None):
+    """The auto inference of a device-resident batch (MDFIT-AUTO v1, DESIGN.md
+    §3.10): the MAP fit, mdfit_map_psis and mdfit_map_waic with psis_draws draws
+    per sub-fit, mdfit_auto_route -- which composes the record of every taxon
+    the importance sampling settles -- and then the sampler over the others
+    alone: idx = nonzero(route & ROUTE_SAMPLE), the rows idx of y, N, mm
+    gathered, mdfit_fit_batch_indexed with taxon_index = idx and the batch's
+    index_base (so a sampled row is the row of the plain NUTS call over the
+    whole batch bit for bit), in sub-chunks sized by plan_chunks' budget for the
+    sampler (budget_bytes, default default_budget; sub_chunk_taxa > 0 caps
+    them) whose workspace is the sub-chunk's, not the batch's, and the records,
+    predictions and status scattered back.  opts: one option set for both fits
+    (auto_opts; its mode is ignored).  An empty subset launches no sampler.
+
+    Taking idx reads the route on the host: the call's one host
+    synchronisation, so it cannot be captured in a graph.  Everything runs on
+    `stream` (default: the current stream).
+
+    Returns (res, route int32 [T], auto float32 [T, NAUTO] = route, sampled 0/1,
+    khat_max, ess_min -- row 6 fields 4, 5 of the waic record).  timings (a
+    dict): filled with the milliseconds of each of AUTO_STAGES, n_sampled and
+    n_sub_chunks (adds a synchronisation at the end)."""
+    torch = _torch()
+    T = int(ty.shape[0])
+    dev = ty.device
+    o_map, o_nuts = auto_opts(opts)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    marks = []
+
+    def mark(name):
+        if timings is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(s)
+            marks.append((name, ev))
+
+    with torch.cuda.stream(s):
+        if res is None:
+            res = alloc_outputs(T, device=dev, opts=o_map)
+        if res.workspace is None or res.workspace.numel() < workspace_bytes(T, o_map):
+            res.workspace = alloc_workspace(T, dev, o_map)
+        mark("start")
+        fit_batch_device(ty, tN, tm, o_map, res, stream=s)
+        mark("map")
+        psis = map_psis_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s)
+        mark("psis")
+        waic = map_waic_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s)
+        mark("waic")
+        route = auto_route_device(res, psis, waic, stream=s)
+        mark("route")
+        idx = torch.nonzero(route & _lib.ROUTE_SAMPLE).reshape(-1)  # (the host synchronisation: its size)
+        n = int(idx.numel())
+        auto = torch.empty((T, _lib.NAUTO), dtype=torch.float32, device=dev)
+        auto[:, 0] = route
+        auto[:, 1] = (route & _lib.ROUTE_SAMPLE) != 0
+        auto[:, 2:4] = waic[:, 6, 4:6]
+        del psis, waic
+        chunks = []
+        t_gather = t_sampler = t_scatter = 0.0
+        if n > 0:
+            budget = budget_bytes if budget_bytes is not None else default_budget(dev)
+            chunks = plan_chunks(n, o_nuts, budget, chunk_taxa=sub_chunk_taxa, n_sets=1, with_mm=tm is not None,
+                                 with_pred=res.pred is not None)
+            cap = max(hi - lo for lo, hi in chunks)
+            sub = alloc_outputs(cap, device=dev, with_pred=res.pred is not None, opts=o_nuts)
+            for lo, hi in chunks:
+                m = hi - lo
+                sel = idx[lo:hi].contiguous()
+                sy, sN = ty.index_select(0, sel), tN.index_select(0, sel)
+                sm = tm.reshape(T, _lib.NPOS, _lib.NMM).index_select(0, sel) if tm is not None else None
+                mark("gather")
+                part = FitBatch(sub.out[:m], sub.pred[:m] if sub.pred is not None else None, sub.status[:m],
+                                sub.workspace)
+                fit_batch_indexed_device(sy, sN, sm, sel, o_nuts, part, stream=s)
+                mark("sampler")
+                res.out.index_copy_(0, sel, part.out)
+                if res.pred is not None:
+                    res.pred.index_copy_(0, sel, part.pred)
+                res.status.index_copy_(0, sel, part.status)
+                mark("scatter")
+        if timings is not None:
+            s.synchronize()
+            for name in AUTO_STAGES:
+                timings[name] = 0.0
+            for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+                timings[name] += e0.elapsed_time(e1)
+            timings["n_sampled"], timings["n_sub_chunks"], timings["n_taxa"] = n, len(chunks), T
+    return res, route, auto
+
+
+def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: int = 256, device="cuda",
+                    dest: FitBatch | None = None, budget_bytes: int | None = None):
+    """fit_auto_device over host counts (uint32 y, N [T, LD], mm [T, 30, 12] or
+    None) chunk by chunk: the chunks of plan_chunks under the device budget
+    (MDFIT_CHUNK_TAXA caps them), each with its global index_base, so any split
+    gives the records of one call bit for bit.  dest (device out [T, NOUT], pred,
+    status, auto f32 [T, NAUTO]): the rows are written in place and dest is
+    returned; None: host arrays (out[T, 25] f64, pred, status, auto) are.  The
+    chunks run one after another -- a chunk's two passes are separated by a host
+    synchronisation -- with no transfer overlap."""
+    torch = _torch()
+    T = int(y.shape[0])
+    dev = torch.device(device)
+    o_map, _ = auto_opts(opts)
+    budget = budget_bytes if budget_bytes is not None else default_budget(dev)
+    # (the MAP pass's buffers, its psis and waic records beside them: two sets' worth is an upper bound)
+    chunks = plan_chunks(T, o_map, budget, with_mm=mm is not None, dest_on_device=dest is not None, with_waic=True)
+    if dest is None:
+        h_out = np.empty((T, H_OUT_COLS), np.float64)
+        h_pred = np.empty((T, _lib.NPRED, _lib.NPOS), np.float32)
+        h_status = np.empty((T,), np.int32)
+        h_auto = np.empty((T, _lib.NAUTO), np.float32)
+    for lo, hi in chunks:
+        ty, tN, tm = to_device_counts(y[lo:hi], N[lo:hi], mm[lo:hi] if mm is not None else None, device=dev)
+        o = _lib.MdfitOpts.from_buffer_copy(o_map)
+        o.index_base = o_map.index_base + lo
+        res = None
+        if dest is not None:
+            res = FitBatch(dest.out[lo:hi], dest.pred[lo:hi] if dest.pred is not None else None, dest.status[lo:hi])
+        res, _route, auto = fit_auto_device(ty, tN, tm, o, psis_draws, res=res, budget_bytes=budget_bytes)
+        if dest is not None:
+            dest.auto[lo:hi].copy_(auto)
+        else:
+            h_out[lo:hi] = res.out[:, :H_OUT_COLS].cpu().numpy()
+            h_pred[lo:hi] = res.pred.cpu().numpy()
+            h_status[lo:hi] = res.status.cpu().numpy()
+            h_auto[lo:hi] = auto.cpu().numpy()
+    if dest is not None:
+        return dest
+    return h_out, h_pred, h_status, h_auto
 
 
 def psis_weights(lw, device="cuda"):

@@ -118,6 +118,12 @@ MAP_WAIC_COLUMNS = [name for name, _, _ in _MAP_WAIC_PICKS]
 # ... then uint32 map_waic_valid (row 6's bit 0: all six rows valid) and
 # map_waic_reliable (its bit 1: valid, and all six khat at or below the threshold)
 MAP_WAIC_UINT_COLUMNS = ["map_waic_valid", "map_waic_reliable"]
+# "auto": the auto block appended after shortname -- uint32
+# auto_route (the mdfit_auto_route bits) and auto_sampled (1: the row is the
+# sampler's), then float32 pareto_k_max and psis_ess_min (row 6 of the waic
+# record: the largest khat and the smallest ess of the six sub-fits)
+AUTO_UINT_COLUMNS = ["auto_route", "auto_sampled"]
+AUTO_COLUMNS = ["pareto_k_max", "psis_ess_min"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -307,7 +313,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
                summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-               waic: bool = False):
+               waic: bool = False, auto: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -322,7 +328,12 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     and the fourth array is the importance-sampled posteriors psis[T, 3, 16]
     f32.  waic (MAP): mdfit_map_waic follows the fit with psis_draws draws per
     sub-fit and the fourth array is the importance-weighted WAIC records
-    waic[T, 7, 8] f32.  At most one of the six."""
+    waic[T, 7, 8] f32.  auto: the auto inference (engine.fit_auto_chunks: the
+    MAP fit, its importance-sampled correction with psis_draws draws per sub-fit
+    and the sampler over the taxa that does not settle; opts carries both fits'
+    options) and the fourth array is the auto block auto[T, 4] f32 = route,
+    sampled, khat_max, ess_min; its chunks run one after another, with no
+    transfer overlap.  At most one of the seven."""
     import torch
 
     from . import engine
@@ -343,6 +354,13 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     # 10k taxa, bench host_to_host) costs no host time, while the host
     # statistics (ingest.noise) take ~1.5 ms of CPU per 10k taxa on the 16-thread
     # share of a multi-file pipeline that is host-bound
+    if auto and (laplace or diag or summary or loo or psis or waic):
+        raise ValueError("auto is the run's only extra block")
+    if auto and not grouped:
+        try:
+            return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev)
+        finally:
+            p.release_pinned()
     if not grouped:
         try:
             return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
@@ -350,14 +368,14 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic)
+        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic, auto)
     finally:
         p.release_pinned()
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
                  summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-                 waic: bool = False):
+                 waic: bool = False, auto: bool = False):
     import torch
 
     from . import engine
@@ -369,8 +387,13 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
     rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                        with_psis=psis, with_waic=waic)
-    if hi > lo:
+                        with_psis=psis, with_waic=waic, with_auto=auto)
+    if hi > lo and auto:  # each rank runs auto on its shard, its rows written in place into the gather buffers
+        engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
+                               device=dev, dest=engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo],
+                                                                rec.status[: hi - lo], auto=rec.auto[: hi - lo]))
+        torch.cuda.synchronize(dev)
+    elif hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
         # records written in place into the gather buffers
         with engine._STAGING_LOCK:
@@ -393,7 +416,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     if rank != 0:
         return None
     return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
-                           with_loo=loo, with_psis=psis, with_waic=waic)
+                           with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto)
 
 
 # --------------------------------------------------------------------------
@@ -450,7 +473,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
-                        psis=None, waic=None) -> pd.DataFrame:
+                        psis=None, waic=None, auto=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -467,7 +490,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     MAP_PSIS_COLUMNS follow as float32, then map_psis_valid and
     map_psis_reliable (uint32).  waic (the importance-weighted WAIC records [T,
     7, 8] of a "map-waic" run): the MAP_WAIC_COLUMNS follow as float32, then
-    map_waic_valid and map_waic_reliable (uint32)."""
+    map_waic_valid and map_waic_reliable (uint32).  auto (the auto block [T, 4]
+    of an "auto" run): auto_route and auto_sampled (uint32), then pareto_k_max
+    and psis_ess_min (float32) follow."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -534,6 +559,13 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["map_waic_valid"] = ((flags & _lib.MAPWAIC_VALID) != 0).astype(np.uint32)
         data["map_waic_reliable"] = ((flags & _lib.MAPWAIC_RELIABLE) != 0).astype(np.uint32)
         columns += MAP_WAIC_COLUMNS + MAP_WAIC_UINT_COLUMNS
+    if auto is not None:
+        ka = np.asarray(auto) if keep is None else np.asarray(auto)[keep]
+        data["auto_route"] = _uint32(np.nan_to_num(ka[:, 0]).astype(np.int64))
+        data["auto_sampled"] = _uint32(np.nan_to_num(ka[:, 1]).astype(np.int64))
+        data["pareto_k_max"] = np.ascontiguousarray(ka[:, 2], dtype=np.float32)
+        data["psis_ess_min"] = np.ascontiguousarray(ka[:, 3], dtype=np.float32)
+        columns += AUTO_UINT_COLUMNS + AUTO_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
@@ -562,7 +594,9 @@ def make_opts(cfg, mcmc_kwargs=None):
     "nuts-loo" (the same call; wants_loo adds the PSIS-LOO model comparison), "map"
     "map-laplace" (the MAP fit; wants_laplace adds the standard errors) or
     "map-psis" (the MAP fit; wants_psis adds the importance-sampled posterior) or
-    "map-waic" (the MAP fit; wants_waic adds the importance-weighted WAIC comparison)."""
+    "map-waic" (the MAP fit; wants_waic adds the importance-weighted WAIC comparison) or
+    "auto" (one option set for the MAP fit and the sampler of engine.fit_auto_device:
+    the sampler's mode and lengths, the MAP fit's defaults)."""
     inference = getattr(cfg, "inference", "nuts")
     if mode_of(inference) == _lib.MODE_MAP:
         return _lib.default_opts(mode=_lib.MODE_MAP)
@@ -575,13 +609,14 @@ def mode_of(inference: str) -> int:
     """The engine mode of an --inference value: "nuts", "nuts-diag",
     "nuts-summary" and "nuts-loo" (the sampler; wants_diag adds mdfit_nuts_diag,
     wants_summary mdfit_nuts_summary, wants_loo mdfit_nuts_loo) or "map" and
-    "map-laplace", "map-psis" and "map-waic"."""
+    "map-laplace", "map-psis" and "map-waic".  "auto" runs both: its option set
+    is the sampler's (engine.auto_opts makes the MAP copy)."""
     if inference in ("map", "map-laplace", "map-psis", "map-waic"):
         return _lib.MODE_MAP
-    if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo"):
+    if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo", "auto"):
         return _lib.MODE_NUTS
     raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'map-waic', 'nuts-diag', "
-                     "'nuts-summary' or 'nuts-loo', "
+                     "'nuts-summary', 'nuts-loo' or 'auto', "
                      f"got {inference!r}")
 
 
@@ -615,8 +650,14 @@ def wants_waic(cfg) -> bool:
     return getattr(cfg, "inference", "nuts") == "map-waic"
 
 
+def wants_auto(cfg) -> bool:
+    """cfg.inference "auto": the MAP fit, its importance-sampled correction and
+    the sampler over the taxa it cannot settle (engine.fit_auto_device)."""
+    return getattr(cfg, "inference", "nuts") == "auto"
+
+
 def psis_draws_of(cfg) -> int:
-    """The draws per sub-fit of a "map-psis" or "map-waic" run (cfg.psis_draws, default 256)."""
+    """The draws per sub-fit of a "map-psis", "map-waic" or "auto" run (cfg.psis_draws, default 256)."""
     return int(getattr(cfg, "psis_draws", 256) or 256)
 
 
@@ -630,10 +671,11 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     p = pack_counts(df_counts, cfg)
     res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
                      summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
-                     psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg))
+                     psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg), auto=wants_auto(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
+    auto = rest[0] if rest and wants_auto(cfg) else None
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
     summ = rest[0] if rest and wants_summary(cfg) else None
@@ -643,7 +685,8 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic),
+    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic,
+                                auto=auto),
             make_df_fit_predictions(p, pred, keep, cfg))
 
 
@@ -740,10 +783,12 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
                      laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
-                     loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg))
+                     loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg),
+                     auto=wants_auto(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
+    auto = rest[0] if rest and wants_auto(cfg) else None
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
     summ = rest[0] if rest and wants_summary(cfg) else None
@@ -758,7 +803,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
         from .counts import _save
 
         df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis,
-                                             waic=waic)
+                                             waic=waic, auto=auto)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())

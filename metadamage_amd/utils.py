@@ -62,9 +62,9 @@ class Config:
     # this engine's addition: "nuts" samples like the reference (fits.py:382-387),
     # "map" is the frequentist MAP fit (BASELINE config 2); "map-laplace",
     # "map-psis", "map-waic", "nuts-diag", "nuts-summary" and "nuts-loo" add their columns
-    # to fit_results; saved in the parquet metadata and part of the cache key
+    # to fit_results; "auto" samples only the taxa the MAP fit's importance sampling cannot settle; saved in the parquet metadata and part of the cache key
     inference: str = "nuts"
-    # the draws per sub-fit of "map-psis" and "map-waic" (25..1024); in the metadata of such a run only
+    # the draws per sub-fit of "map-psis", "map-waic" and "auto" (25..1024); in the metadata of such a run only
     psis_draws: int = 256
     N_cores: int = field(init=False)
 
@@ -131,7 +131,7 @@ class Config:
 
     def to_dict(self):
         d_out = asdict(self)
-        if self.inference not in ("map-psis", "map-waic"):
+        if self.inference not in ("map-psis", "map-waic", "auto"):
             del d_out["psis_draws"]
         for key, val in d_out.items():
             if isinstance(val, Path):
