@@ -560,6 +560,61 @@ int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, cons
                    int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base,
                    double* waic, double* pointwise, double* draws, void* hip_stream);
 
+/* Importance-weighted posterior predictive record: double rec[T][MDFIT_NMAPPRED]:
+ * D_max, D_max_lower_hpdi, D_max_upper_hpdi (job 0), D_max_forward (job 30),
+ * D_max_reverse (job 31), khat of rows 0..2 (PMD-all, PMD-forward,
+ * PMD-reverse), ess = 1 / sum w^2 of rows 0..2, n_distinct of rows 0..2 (the
+ * importance draws the resampling took), the number of jobs made NaN by a
+ * draw that is no count, flags (an integer stored as double: bit 0 all three
+ * rows valid, bit 1 all valid and every khat <= min(1 - 1 / log10 S, 0.7),
+ * bits 2..4 row 0..2 valid). */
+#define MDFIT_NMAPPRED 16
+
+/*
+ * The reference's posterior predictive (fits.py:89-120) of a finished MODE_MAP
+ * call from importance-weighted draws (MDFIT-PPRED v1).  Each
+ * PMD row (stream sub-fit 0 / 2 / 3) is importance-sampled as mdfit_map_psis
+ * does it: the same proposal, Philox stream, target, smoothing and validity
+ * rule, so khat, ess and the valid / reliable bits are mdfit_map_psis's bit
+ * for bit.  The smoothed weights w_s are resampled without a random number:
+ * c_s = c_{s-1} + w_s in ascending s, p_r = (r + 0.5) c_{S-1} / R, s(r) the
+ * least s with c_s > p_r (a draw of weight 0 is never taken).  Draw r of job j
+ * of the sampler's 32 predictive jobs (jobs 0..29: row 0 at column j, N[j];
+ * job 30: row 1 at column 0; job 31: row 2 at column 0 of data_forward, N[0])
+ * is the sampler's predictive Beta-Binomial draw r (counter word 2 = 0xFFFD0000
+ * + r, word 3 = column << 16 counting up) of the row's stream at theta = (q, A,
+ * c, phi) of importance draw s(r); a job's summary is np.median and numpyro's
+ * hpdi(0.68) of count / N.  N = 0, a draw that is no count in [0, N], or an
+ * invalid row give NaN in the job; a taxon with status != MDFIT_OK NaN
+ * everywhere and flags 0.
+ *   y, N, out, status : those of the MODE_MAP call (device; read only)
+ *   num_draws  : S in [25, 1024] (else MDFIT_E_ARG)
+ *   num_pred   : R in [25, 1024] (else MDFIT_E_ARG); the reference draws 1000
+ *   seed, index_base : the Philox streams are keyed by (seed, index_base +
+ *                taxon, sub-fit), as mdfit_map_psis's and the sampler's
+ *   ppred      : float[n_taxa][MDFIT_NPRED][30] = median, lower, upper of
+ *                jobs 0..29, in pred's layout                       (device)
+ *   rec        : double[n_taxa][MDFIT_NMAPPRED]                     (device)
+ *   index      : int32[n_taxa][3][num_pred] = s(r) of each row, -1 in an
+ *                invalid row or a taxon with status != MDFIT_OK; or NULL
+ *                (parity tests)                                     (device)
+ *   counts     : uint32[n_taxa][32][num_pred], the unsorted counts of each
+ *                job, 0xFFFFFFFF for no count or a job not run; or NULL
+ *                (parity tests)                                     (device)
+ * One launch on hip_stream, one wave per taxon; no workspace, no allocation,
+ * no side stream, no host synchronisation, no atomics; capturable in a graph.
+ * n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_pred(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                   int64_t n_taxa, int32_t num_draws, int32_t num_pred, uint64_t seed, int64_t index_base,
+                   float* ppred, double* rec, int32_t* index, uint32_t* counts, void* hip_stream);
+
+/* Test helper: mdfit_map_pred's resampling of given weights w[n_series][S]
+ * (>= 0, not all 0), one wave per series: idx[n_series][R] = s(r) and
+ * n_distinct[n_series] (device pointers).  S, R in [25, 1024]. */
+int mdfit_resample(const double* w, int64_t n_series, int32_t S, int32_t R, int32_t* idx, int32_t* n_distinct,
+                   void* hip_stream);
+
 /*
  * Pointwise beta-binomial log-pmf (numpyro BetaBinomial.log_prob, used by
  * fits.py:59,67 and log_likelihood fits.py:126-133):

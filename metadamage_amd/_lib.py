@@ -34,6 +34,7 @@ NNUTSSUMM = 16
 NNUTSLOO = 8
 NMAPPSIS = 16
 NMAPWAIC = 8
+NMAPPRED = 16
 NLOOROW = 7  # rows of a PSIS-LOO record: the six sub-fits, then the comparisons
 
 # output record field order (enum mdfit_field) == fit_results numeric columns
@@ -106,6 +107,14 @@ AUTO_COMPOSED_FIELDS = ["q_mean", "concentration_mean", "D_max_marginalized_mean
 NAUTO = 4
 AUTO_FIELDS = ["route", "sampled", "khat_max", "ess_min"]
 
+# importance-weighted posterior predictive record (mdfit_map_pred): float64 [T][NMAPPRED]
+MAPPRED_FIELDS = ["D_max", "D_max_lower_hpdi", "D_max_upper_hpdi", "D_max_forward", "D_max_reverse", "khat_all",
+                  "khat_forward", "khat_reverse", "ess_all", "ess_forward", "ess_reverse", "n_distinct_all",
+                  "n_distinct_forward", "n_distinct_reverse", "n_noncount_jobs", "flags"]
+MAPPRED_VALID, MAPPRED_RELIABLE = 1, 2  # flags: bit 0 all rows valid, bit 1 and every khat <= threshold, bits 2..4 row valid
+NPREDJOB = 32  # the sampler's predictive jobs: columns 0..29 of PMD-all, column 0 under PMD-forward and PMD-reverse
+PRED_DRAWS_MIN, PRED_DRAWS_MAX = 25, 1024
+
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
     "mdfit_default_opts",
@@ -124,6 +133,8 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_psis",
     "mdfit_psis_weights",
     "mdfit_map_waic",
+    "mdfit_map_pred",
+    "mdfit_resample",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
     "mdfit_primitive",
@@ -218,6 +229,10 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_map_psis.restype = ctypes.c_int
     lib.mdfit_map_waic.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp, vp]
     lib.mdfit_map_waic.restype = ctypes.c_int
+    lib.mdfit_map_pred.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]
+    lib.mdfit_map_pred.restype = ctypes.c_int
+    lib.mdfit_resample.argtypes = [vp, i64, i32, i32, vp, vp, vp]
+    lib.mdfit_resample.restype = ctypes.c_int
     lib.mdfit_psis_weights.argtypes = [vp, i64, i32, vp, vp, vp]
     lib.mdfit_psis_weights.restype = ctypes.c_int
     lib.mdfit_betabinom_logpmf.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]

@@ -59,9 +59,13 @@ def cli_fit(
                                   "nuts-loo: NUTS with PSIS-LOO model comparison and Pareto-k diagnostics; "
                                   "map-psis: MAP fit with an importance-sampled posterior and its Pareto-k; "
                                   "map-waic: MAP fit with importance-weighted WAIC n_sigma and asymmetry; "
+                                  "map-pred: MAP fit with the importance-weighted posterior predictive D_max, its "
+                                  "68 % interval and fit_predictions columns; "
                                   "auto: MAP fit with its importance-sampled correction, NUTS only for the taxa "
                                   "whose Pareto-k says it cannot be trusted"),
-    psis_draws: int = typer.Option(256, help="map-psis, map-waic, auto: importance draws per sub-fit, 25 to 1024"),
+    psis_draws: int = typer.Option(256, help="map-psis, map-waic, map-pred, auto: importance draws per sub-fit, "
+                                   "25 to 1024"),
+    pred_draws: int = typer.Option(1000, help="map-pred: predictive draws per position, 25 to 1024"),
 ):
     """Fitting Ancient Damage.
 
@@ -83,13 +87,16 @@ def cli_fit(
         "version": "0.0.0",
         "inference": inference,
         "psis_draws": psis_draws,
+        "pred_draws": pred_draws,
     }
-    if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "nuts-diag", "nuts-summary",
-                         "nuts-loo", "auto"):
-        raise typer.BadParameter("--inference must be nuts, map, map-laplace, map-psis, map-waic, nuts-diag, "
-                                 "nuts-summary, nuts-loo or auto")
+    if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "nuts-diag",
+                         "nuts-summary", "nuts-loo", "auto"):
+        raise typer.BadParameter("--inference must be nuts, map, map-laplace, map-psis, map-waic, map-pred, "
+                                 "nuts-diag, nuts-summary, nuts-loo or auto")
     if not 25 <= psis_draws <= 1024:
         raise typer.BadParameter("--psis-draws must be in [25, 1024]")
+    if not 25 <= pred_draws <= 1024:
+        raise typer.BadParameter("--pred-draws must be in [25, 1024]")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

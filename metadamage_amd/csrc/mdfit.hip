@@ -43,6 +43,7 @@
 #include "mdfit_hpdi.h"
 #include "mdfit_host.h"
 #include "mdfit_laplace.h"
+#include "mdfit_mappred.h"
 #include "mdfit_mappsis.h"
 #include "mdfit_mapwaic.h"
 #include "mdfit_model.h"
@@ -2124,6 +2125,45 @@ int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, cons
                      (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
                      seed, index_base, mp::khat_threshold(S), waic, pointwise, draws);
   return check_launch("map_waic_kernel");
+}
+
+int mdfit_map_pred(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                   int32_t num_draws, int32_t num_pred, uint64_t seed, int64_t index_base, float* ppred, double* rec,
+                   int32_t* index, uint32_t* counts, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace mq = mdfit::mappred;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (num_pred < mq::kMinPred || num_pred > mq::kMaxPred)
+    return set_err(MDFIT_E_ARG, "num_pred must be in [25, 1024]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !ppred || !rec) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int S = (int)num_draws, R = (int)num_pred;
+  const int tc = mq::tile_cols(S, R);
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mq::map_pred_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave), mq::lds_bytes(S, R, tc),
+                     (hipStream_t)hip_stream, y, N, out, status, n_taxa, S, R, tc, seed, index_base,
+                     mp::khat_threshold(S), ppred, rec, index, counts);
+  return check_launch("map_pred_kernel");
+}
+
+int mdfit_resample(const double* w, int64_t n_series, int32_t S, int32_t R, int32_t* idx, int32_t* n_distinct,
+                   void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace mq = mdfit::mappred;
+  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
+  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
+  if (R < mq::kMinPred || R > mq::kMaxPred) return set_err(MDFIT_E_ARG, "R must be in [25, 1024]");
+  if (n_series == 0) return 0;
+  if (!w || !idx || !n_distinct) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mq::resample_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
+                     (size_t)S * sizeof(double) + (size_t)R * sizeof(int), (hipStream_t)hip_stream, w, n_series,
+                     (int)S, (int)R, idx, n_distinct);
+  return check_launch("resample_kernel");
 }
 
 int mdfit_auto_route(const int32_t* status, const double* psis, const double* waic, int64_t n_taxa, double* out,

@@ -56,10 +56,19 @@ REC_WAIC = _lib.NWAICROW * _lib.NMAPWAIC * 4
 # with_auto (an "auto" run; never together with any of them): the same for the
 # auto block, one more f32 block [n, NAUTO] = route, sampled, khat_max, ess_min, 16 B per taxon
 REC_AUTO = _lib.NAUTO * 4
+# with_ppred (a "map-pred" run; never together with any of them): the same for the
+# posterior predictive, one more f32 block [n, 106] = ppred [3][30] | rec [NMAPPRED], 424 B per taxon
+REC_PPRED = (_lib.NPRED * _lib.NPOS + _lib.NMAPPRED) * 4
 
 
 def _extra(with_laplace: bool, with_diag: bool, with_summary: bool = False, with_loo: bool = False,
-           with_psis: bool = False, with_waic: bool = False, with_auto: bool = False) -> int:
+           with_psis: bool = False, with_waic: bool = False, with_auto: bool = False,
+           with_ppred: bool = False) -> int:
+    if with_ppred:
+        if with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic or with_auto:
+            raise ValueError("with_ppred, with_auto, with_waic, with_psis, with_loo, with_summary, with_diag and "
+                             "with_laplace are mutually exclusive: one extra block per run")
+        return REC_PPRED
     if with_auto:
         if with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic:
             raise ValueError("with_auto, with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace "
@@ -115,20 +124,23 @@ class Records:
     bytes, `diag` f32[n, 6, 12]; with_summary: n * REC_SUMM bytes, `summ` f32[n,
     6, 16]; with_loo: n * REC_LOO bytes, `loo` f32[n, 7, 8]; with_psis: n *
     REC_PSIS bytes, `psis` f32[n, 3, 16]; with_waic: n * REC_WAIC bytes, `waic`
-    f32[n, 7, 8]; with_auto: n * REC_AUTO bytes, `auto` f32[n, 4].  At most one
-    of the seven."""
+    f32[n, 7, 8]; with_auto: n * REC_AUTO bytes, `auto` f32[n, 4]; with_ppred: n
+    * REC_PPRED bytes, `ppred` f32[n, 106].  At most one of the eight."""
 
     def __init__(self, n: int, device, with_laplace: bool = False, with_diag: bool = False,
                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                 with_waic: bool = False, with_auto: bool = False):
+                 with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False):
         import torch
 
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
         self.buf = torch.empty(n * (REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis,
-                                                       with_waic, with_auto)), dtype=torch.uint8, device=device)
-        self.lap = self.diag = self.summ = self.loo = self.psis = self.waic = self.auto = None
-        if with_auto:
+                                                       with_waic, with_auto, with_ppred)), dtype=torch.uint8,
+                               device=device)
+        self.lap = self.diag = self.summ = self.loo = self.psis = self.waic = self.auto = self.ppred = None
+        if with_ppred:
+            self.pred, self.status, self.ints, self.floats, self.ppred = packed_views(self.buf, n, with_ppred=True)
+        elif with_auto:
             self.pred, self.status, self.ints, self.floats, self.auto = packed_views(self.buf, n, with_auto=True)
         elif with_laplace:
             self.pred, self.status, self.ints, self.floats, self.lap = packed_views(self.buf, n, with_laplace=True)
@@ -153,7 +165,8 @@ class Records:
 
 
 def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False, with_auto: bool = False):
+                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False, with_auto: bool = False,
+                 with_ppred: bool = False):
     """Views (pred[n, 3, 30] f32, status[n] i32, ints[n, 8] f64, floats[n, 17]
     f32) into one uint8 gather buffer of n * REC_BYTES bytes laid out ints |
     floats | pred | status (torch tensor; the f64 block first keeps it 8-byte
@@ -164,8 +177,9 @@ def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = Fals
     REC_LOO more bytes and the fifth view is loo[n, 7, 8] f32; with_psis: n *
     REC_PSIS more bytes and the fifth view is psis[n, 3, 16] f32; with_waic: n *
     REC_WAIC more bytes and the fifth view is waic[n, 7, 8] f32; with_auto: n *
-    REC_AUTO more bytes and the fifth view is auto[n, 4] f32."""
-    _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto)
+    REC_AUTO more bytes and the fifth view is auto[n, 4] f32; with_ppred: n *
+    REC_PPRED more bytes and the fifth view is ppred[n, 106] f32."""
+    _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto, with_ppred)
     o1 = n * REC_INT
     o2 = o1 + n * REC_F32
     o3 = o2 + n * REC_PRED
@@ -173,6 +187,10 @@ def packed_views(buf, n: int, with_laplace: bool = False, with_diag: bool = Fals
     floats = buf[o1:o2].view(dtype=_torch_dtype("float32")).view(n, len(FLOAT_COLS))
     pred = buf[o2:o3].view(dtype=_torch_dtype("float32")).view(n, _lib.NPRED, _lib.NPOS)
     status = buf[o3 : o3 + 4 * n].view(dtype=_torch_dtype("int32"))
+    if with_ppred:
+        o4 = o3 + 4 * n
+        ppred = buf[o4 : o4 + n * REC_PPRED].view(dtype=_torch_dtype("float32")).view(n, REC_PPRED // 4)
+        return pred, status, ints, floats, ppred
     if with_auto:
         o4 = o3 + 4 * n
         auto = buf[o4 : o4 + n * REC_AUTO].view(dtype=_torch_dtype("float32")).view(n, _lib.NAUTO)
@@ -220,8 +238,9 @@ def _torch_dtype(name):
 
 def alloc_records(n: int, device, with_laplace: bool = False, with_diag: bool = False,
                   with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                  with_waic: bool = False, with_auto: bool = False) -> Records:
-    return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto)
+                  with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False) -> Records:
+    return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto,
+                   with_ppred)
 
 
 def gather_records(buf, n_cap: int, rank: int, world: int, group=None, async_op: bool = False):
@@ -328,7 +347,7 @@ def run_distributed(fn, *args, **kwargs):
 
 def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, with_diag: bool = False,
                     with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                    with_waic: bool = False, with_auto: bool = False):
+                    with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  with_laplace: the
     parts carry the Laplace block and a fourth array lap[T, 3, 8] f32 is returned;
@@ -337,12 +356,14 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
     the PSIS-LOO block, returned as loo[T, 7, 8] f32; with_psis: the
     importance-sampled posteriors, returned as psis[T, 3, 16] f32; with_waic: the
     importance-weighted WAIC records, returned as waic[T, 7, 8] f32; with_auto:
-    the auto block, returned as auto[T, 4] f32."""
+    the auto block, returned as auto[T, 4] f32; with_ppred: the posterior
+    predictive block, returned as ppred[T, 106] f32."""
     import torch
 
     outs, preds, sts, laps = [], [], [], []
-    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto)
-    extra = with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic or with_auto
+    rec_bytes = REC_BYTES + _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto,
+                                   with_ppred)
+    extra = with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic or with_auto or with_ppred
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)
@@ -361,7 +382,8 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
         n_cap = part.numel() // rec_bytes
         p, s, ints, floats, *rest = packed_views(part, n_cap, with_laplace=with_laplace, with_diag=with_diag,
                                                  with_summary=with_summary, with_loo=with_loo, with_psis=with_psis,
-                                                 with_waic=with_waic, with_auto=with_auto)
+                                                 with_waic=with_waic, with_auto=with_auto,
+                                                 with_ppred=with_ppred)
         if extra:
             laps.append(rest[0][: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)

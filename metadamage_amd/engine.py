@@ -43,6 +43,7 @@ class FitBatch:
     loo: "object" = None  # torch.float32 [T, 7, NNUTSLOO]: the PSIS-LOO records (ChunkedFitter with_loo)
     psis: "object" = None  # torch.float32 [T, 3, NMAPPSIS]: the importance-sampled posteriors (ChunkedFitter with_psis)
     waic: "object" = None  # torch.float32 [T, 7, NMAPWAIC]: the importance-weighted WAIC records (with_waic)
+    ppred: "object" = None  # torch.float32 [T, PPRED_WORDS]: the posterior predictive block (with_ppred; split_ppred)
     auto: "object" = None  # torch.float32 [T, NAUTO]: route, sampled, khat_max, ess_min (fit_auto_chunks)
 
 
@@ -435,6 +436,67 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
     return h_out, h_pred, h_status, h_auto
 
 
+def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int = 1000, seed: int = 0,
+                    index_base: int = 0, ppred=None, rec=None, index=None, counts=None, stream=None):
+    """Launch mdfit_map_pred on the records of a finished MAP call (asynchronous
+    on `stream`): the reference's posterior predictive from importance-weighted
+    draws (MDFIT-PPRED v1): float32 ppred[T, 3, 30] in pred's layout and float64
+    rec[T, NMAPPRED] (_lib.MAPPRED_FIELDS).  The Philox streams are keyed by
+    (seed, index_base + taxon, sub-fit).  index: None, True (allocated) or an
+    int32 tensor [T, 3, num_pred], the importance draw each predictive draw
+    took; counts: None, True or an int32 tensor [T, 32, num_pred] holding the
+    unsorted counts of each job as uint32 (0xFFFFFFFF: no count or job not run).
+    Returns (ppred, rec[, index][, counts])."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S, R = int(ty.shape[0]), int(num_draws), int(num_pred)
+    if ppred is None:
+        ppred = torch.empty((T, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=ty.device)
+    if rec is None:
+        rec = torch.empty((T, _lib.NMAPPRED), dtype=torch.float64, device=ty.device)
+    if index is True:
+        index = torch.empty((T, 3, R), dtype=torch.int32, device=ty.device)
+    if counts is True:
+        counts = torch.empty((T, _lib.NPREDJOB, R), dtype=torch.int32, device=ty.device)
+    for name, t, n, dt in (("ppred", ppred, T * _lib.NPRED * _lib.NPOS, torch.float32),
+                           ("rec", rec, T * _lib.NMAPPRED, torch.float64),
+                           ("index", index, T * 3 * R, torch.int32),
+                           ("counts", counts, T * _lib.NPREDJOB * R, torch.int32)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of {n} elements")
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    _lib.check(lib.mdfit_map_pred(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
+                                  ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S, R,
+                                  int(seed), int(index_base), ctypes.c_void_p(ppred.data_ptr()),
+                                  ctypes.c_void_p(rec.data_ptr()),
+                                  ctypes.c_void_p(index.data_ptr()) if index is not None else None,
+                                  ctypes.c_void_p(counts.data_ptr()) if counts is not None else None,
+                                  _stream_handle(torch, stream)))
+    return (ppred, rec) + tuple(x for x in (index, counts) if x is not None)
+
+
+def resample(w, num_pred: int, device="cuda"):
+    """(idx[n, R] int32, n_distinct[n] int32) host arrays of the weight series
+    w[n, S] by the device's midpoint systematic resampling (MDFIT-PPRED v1,
+    mdfit_resample; parity tests)."""
+    torch = _torch()
+    lib = _lib.load()
+    w = np.array(w, dtype=np.float64, order="C")
+    n, S = w.shape
+    R = int(num_pred)
+    t = torch.from_numpy(w).to(device)
+    idx = torch.empty((n, R), dtype=torch.int32, device=device)
+    nd = torch.empty(n, dtype=torch.int32, device=device)
+    _lib.check(lib.mdfit_resample(ctypes.c_void_p(t.data_ptr()), n, S, R, ctypes.c_void_p(idx.data_ptr()),
+                                  ctypes.c_void_p(nd.data_ptr()), _stream_handle(torch, None)))
+    torch.cuda.current_stream().synchronize()
+    return idx.cpu().numpy(), nd.cpu().numpy()
+
+
 def psis_weights(lw, device="cuda"):
     """(w[n, S], khat[n]) float64 host arrays of the raw log-weight series
     lw[n, S] by the device's smoothing (MDFIT-PSIS v1, mdfit_psis_weights;
@@ -696,6 +758,32 @@ def _check_waic_mode(with_waic: bool, opts: _lib.MdfitOpts | None, with_laplace:
                          "exclusive: one extra block per run")
 
 
+PRED_DRAWS = 1000  # predictive draws per job of mdfit_map_pred where the caller gives none (the reference's)
+# one taxon's posterior predictive block on the way out, f32: ppred [3][30], then the record [16]
+PPRED_WORDS = _lib.NPRED * _lib.NPOS + _lib.NMAPPRED
+PPRED_BYTES = PPRED_WORDS * 4
+
+
+def split_ppred(block):
+    """(ppred[T, 3, 30], rec[T, NMAPPRED]) views of a posterior predictive block [T, PPRED_WORDS]."""
+    n = _lib.NPRED * _lib.NPOS
+    return block[:, :n].reshape(-1, _lib.NPRED, _lib.NPOS), block[:, n:]
+
+
+def _check_ppred_mode(with_ppred: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
+                      with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
+                      with_psis: bool = False, with_waic: bool = False) -> None:
+    """with_ppred is the MAP mode's (opts None: the default options, MAP) and the
+    run's one optional extra block."""
+    if not with_ppred:
+        return
+    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
+        raise ValueError("with_ppred needs MAP records (opts.mode == MODE_MAP)")
+    if with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic:
+        raise ValueError("with_ppred, with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace are "
+                         "mutually exclusive: one extra block per run")
+
+
 def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
     """with_diag is the sampling mode's (opts None: the default options, MAP)."""
     if with_diag and (opts is None or int(opts.mode) != _lib.MODE_NUTS):
@@ -705,7 +793,7 @@ def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
                  dest_on_device: bool = False, with_laplace: bool = False, with_diag: bool = False,
                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                 with_waic: bool = False) -> int:
+                 with_waic: bool = False, with_ppred: bool = False) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -726,6 +814,9 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     block: ValueError).  with_waic: the importance-weighted WAIC records, 448 B
     as computed (f64) and -- unless they go to the caller's device buffer --
     224 B rounded to f32 (MAP only, and the run's only extra block:
+    ValueError).  with_ppred: the posterior predictive, 360 + 128 B as computed
+    (f32 predictions, f64 record) and -- unless they go to the caller's device
+    buffer -- 424 B as one f32 block (MAP only, and the run's only extra block:
     ValueError)."""
     C = int(C)
     _check_diag_mode(with_diag, opts)
@@ -733,6 +824,7 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
     _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
     _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
+    _check_ppred_mode(with_ppred, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
@@ -748,6 +840,8 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
         b += C * (2 * PSIS_BYTES + (0 if dest_on_device else PSIS_BYTES))
     if with_waic:
         b += C * (2 * WAIC_BYTES + (0 if dest_on_device else WAIC_BYTES))
+    if with_ppred:
+        b += C * (_lib.NPRED * _lib.NPOS * 4 + _lib.NMAPPRED * 8 + (0 if dest_on_device else PPRED_BYTES))
     return b + workspace_bytes(C, opts)
 
 
@@ -755,7 +849,8 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
                 dest_on_device: bool = False, with_laplace: bool = False,
                 with_diag: bool = False, with_summary: bool = False,
-                with_loo: bool = False, with_psis: bool = False, with_waic: bool = False) -> list[tuple[int, int]]:
+                with_loo: bool = False, with_psis: bool = False, with_waic: bool = False,
+                with_ppred: bool = False) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk fit in budget_bytes (None: no memory
     bound), no chunk exceeds the per-call limit (2^25 taxa) or chunk_taxa (> 0;
@@ -768,6 +863,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
     _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
     _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
+    _check_ppred_mode(with_ppred, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -777,7 +873,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
         per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, with_laplace,  # noqa: E731
-                                              with_diag, with_summary, with_loo, with_psis, with_waic)
+                                              with_diag, with_summary, with_loo, with_psis, with_waic, with_ppred)
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
         if per(cap) > budget_bytes:  # largest c with per(c) <= budget (per is monotone in c)
@@ -810,7 +906,8 @@ class _Set:
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
                  with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False):
+                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False,
+                 with_ppred: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -850,6 +947,12 @@ class _Set:
             self.waic64 = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.waic = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32, device=device)
+        self.ppred32 = self.prec64 = self.ppred = None
+        if with_ppred:  # as mdfit_map_pred writes them, and one f32 block for the way out
+            self.ppred32 = torch.empty((C, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=device)
+            self.prec64 = torch.empty((C, _lib.NMAPPRED), dtype=torch.float64, device=device)
+            if not dest_on_device:
+                self.ppred = torch.empty((C, PPRED_WORDS), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -911,17 +1014,26 @@ class ChunkedFitter:
     each chunk's fit on the compute stream in the same way (psis_draws draws
     per sub-fit, opts.seed, the chunk's global taxon index), and its records,
     rounded to f32 there, leave as f32 [T, 7, 8], 224 B per taxon (run's fourth
-    array; dest.waic)."""
+    array; dest.waic).
+
+    with_ppred (MAP only; the run's only extra block): mdfit_map_pred follows
+    each chunk's fit on the compute stream in the same way (psis_draws
+    importance draws per sub-fit, pred_draws predictive draws per job,
+    opts.seed, the chunk's global taxon index); its predictions and its record,
+    rounded to f32 there, leave as one f32 block [T, 106] = ppred [3][30] |
+    rec [16], 424 B per taxon (run's fourth array; dest.ppred; split_ppred)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False,
                  with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
-                 with_psis: bool = False, psis_draws: int = PSIS_DRAWS, with_waic: bool = False):
+                 with_psis: bool = False, psis_draws: int = PSIS_DRAWS, with_waic: bool = False,
+                 with_ppred: bool = False, pred_draws: int = PRED_DRAWS):
         _check_diag_mode(with_diag, opts)
         _check_summary_mode(with_summary, opts, with_laplace, with_diag)
         _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
         _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
         _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
+        _check_ppred_mode(with_ppred, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
         torch = _torch()
         if with_laplace and opts is not None and int(opts.mode) != _lib.MODE_MAP:
             raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
@@ -931,19 +1043,22 @@ class ChunkedFitter:
         self.with_loo = bool(with_loo)
         self.with_psis = bool(with_psis)
         self.with_waic = bool(with_waic)
+        self.with_ppred = bool(with_ppred)
+        self.pred_draws = int(pred_draws)
         self.psis_draws = int(psis_draws)
         self.chunk_cap = int(chunk_cap)
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.with_laplace,
-                          self.with_diag, self.with_summary, self.with_loo, self.with_psis, self.with_waic)
+                          self.with_diag, self.with_summary, self.with_loo, self.with_psis, self.with_waic,
+                          self.with_ppred)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = self.h_lap = None
-        self.h_diag = self.h_summ = self.h_loo = self.h_psis = self.h_waic = None
+        self.h_diag = self.h_summ = self.h_loo = self.h_psis = self.h_waic = self.h_ppred = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -971,6 +1086,8 @@ class ChunkedFitter:
                 self.h_psis = torch.empty((cap, 3, _lib.NMAPPSIS), dtype=torch.float32).pin_memory()
             if self.with_waic:
                 self.h_waic = torch.empty((cap, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32).pin_memory()
+            if self.with_ppred:
+                self.h_ppred = torch.empty((cap, PPRED_WORDS), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -1015,6 +1132,9 @@ class ChunkedFitter:
         _check_waic_mode(self.with_waic, o0)
         if self.with_waic and dest is not None and dest.waic is None:
             raise ValueError("with_waic: dest.waic (float32 [T, 7, NMAPWAIC]) required")
+        _check_ppred_mode(self.with_ppred, o0)
+        if self.with_ppred and dest is not None and dest.ppred is None:
+            raise ValueError("with_ppred: dest.ppred (float32 [T, PPRED_WORDS]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -1099,6 +1219,15 @@ class ChunkedFitter:
                 waic32 = dest.waic[lo:hi] if dest is not None else st.waic[:n]
                 with torch.cuda.stream(comp):
                     waic32.copy_(st.waic64[:n])
+            ppred32 = None
+            if self.with_ppred:  # the records are final: their posterior predictive, one f32 block for the way out
+                map_pred_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, self.pred_draws, int(o.seed),
+                                int(o.index_base), ppred=st.ppred32[:n], rec=st.prec64[:n], stream=comp)
+                ppred32 = dest.ppred[lo:hi] if dest is not None else st.ppred[:n]
+                with torch.cuda.stream(comp):
+                    pp_v, rec_v = split_ppred(ppred32)
+                    pp_v.copy_(st.ppred32[:n])
+                    rec_v.copy_(st.prec64[:n])
             ev_done = torch.cuda.Event()
             ev_done.record(comp)
             done.append(ev_done)
@@ -1121,6 +1250,8 @@ class ChunkedFitter:
                         self.h_psis[lo:hi].copy_(psis32, non_blocking=True)
                     if waic32 is not None:
                         self.h_waic[lo:hi].copy_(waic32, non_blocking=True)
+                    if ppred32 is not None:
+                        self.h_ppred[lo:hi].copy_(ppred32, non_blocking=True)
                 last_d2h = cp
         end = torch.cuda.Event()
         end.record(cp if last_d2h is not None else comp)
@@ -1158,13 +1289,16 @@ class ChunkedFitter:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_psis[:T].numpy()
         if self.with_waic:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_waic[:T].numpy()
+        if self.with_ppred:
+            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_ppred[:T].numpy()
         return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy()
 
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
         (out[T, NOUT], pred, status -- with_laplace also lap, f32 [T, 3, 8],
         with_diag also diag, f32 [T, 6, 12], with_summary also summ, f32 [T, 6, 16], with_loo also loo, f32
-        [T, 7, 8], with_psis also psis, f32 [T, 3, 16], with_waic also waic, f32 [T, 7, 8]: rows written in place),
+        [T, 7, 8], with_psis also psis, f32 [T, 3, 16], with_waic also waic, f32 [T, 7, 8],
+        with_ppred also ppred, f32 [T, 106]: rows written in place),
         ordered on the caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
@@ -1234,7 +1368,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
             dest_on_device: bool = False, budget_bytes: int | None = None,
             with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
             with_loo: bool = False, with_psis: bool = False, psis_draws: int = PSIS_DRAWS,
-            with_waic: bool = False) -> ChunkedFitter:
+            with_waic: bool = False, with_ppred: bool = False, pred_draws: int = PRED_DRAWS) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind and sampler length): the
     multi-file pipeline fits one file after another, and pinned + device
@@ -1252,7 +1386,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     env_chunk = int(os.environ.get("MDFIT_CHUNK_TAXA", "0") or 0)
     key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
            bool(with_laplace), bool(with_diag), bool(with_summary), bool(with_loo),
-           int(psis_draws) if with_psis else 0, int(psis_draws) if with_waic else 0)
+           int(psis_draws) if with_psis else 0, int(psis_draws) if with_waic else 0,
+           (int(psis_draws), int(pred_draws)) if with_ppred else 0)
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1270,11 +1405,12 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
                       with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                      with_loo=with_loo, with_psis=with_psis, with_waic=with_waic)[0]
+                      with_loo=with_loo, with_psis=with_psis, with_waic=with_waic, with_ppred=with_ppred)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
                        with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                       with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws, with_waic=with_waic)
+                       with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws, with_waic=with_waic,
+                       with_ppred=with_ppred, pred_draws=pred_draws)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1284,7 +1420,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, laplace: bool = False, diag: bool = False,
                    summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = PSIS_DRAWS,
-                   waic: bool = False):
+                   waic: bool = False, ppred: bool = False, pred_draws: int = PRED_DRAWS):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
     the PMD sub-fits (_lib.LAPLACE_FIELDS), or, with diag (NUTS only), diag[T, 6,
@@ -1296,7 +1432,10 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     posteriors of the PMD sub-fits from psis_draws draws each
     (_lib.MAPPSIS_FIELDS), or, with waic (MAP only; the only one), waic[T, 7, 8]
     f32, the importance-weighted WAIC records from psis_draws draws per sub-fit
-    (_lib.MAPWAIC_FIELDS) --, chunked
+    (_lib.MAPWAIC_FIELDS), or, with ppred (MAP only; the only one), the block
+    [T, 106] f32 = ppred [3][30] | rec [16] of the posterior predictive from
+    psis_draws importance draws and pred_draws predictive draws (split_ppred,
+    _lib.MAPPRED_FIELDS) --, chunked
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
@@ -1305,14 +1444,14 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace, with_diag=diag,
                      with_summary=summary, with_loo=loo, with_psis=psis, psis_draws=psis_draws,
-                     with_waic=waic)
+                     with_waic=waic, with_ppred=ppred, pred_draws=pred_draws)
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
-        extra = got[3].copy() if laplace or diag or summary or loo or psis or waic else None
+        extra = got[3].copy() if laplace or diag or summary or loo or psis or waic or ppred else None
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
-    if laplace or diag or summary or loo or psis or waic:
+    if laplace or diag or summary or loo or psis or waic or ppred:
         return out, pred, status, extra
     return out, pred, status
 

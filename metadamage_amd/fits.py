@@ -118,6 +118,14 @@ MAP_WAIC_COLUMNS = [name for name, _, _ in _MAP_WAIC_PICKS]
 # ... then uint32 map_waic_valid (row 6's bit 0: all six rows valid) and
 # map_waic_reliable (its bit 1: valid, and all six khat at or below the threshold)
 MAP_WAIC_UINT_COLUMNS = ["map_waic_valid", "map_waic_reliable"]
+# a "map-pred" run (mdfit_map_pred, MDFIT-PPRED v1): the posterior predictive D_max columns from
+# importance-weighted draws, their worst k-hat and least ess / distinct draws over the three PMD rows
+_MAP_PRED_PICKS = [("D_max_predictive", "D_max"), ("D_max_predictive_lower_hpdi", "D_max_lower_hpdi"),
+                   ("D_max_predictive_upper_hpdi", "D_max_upper_hpdi"), ("D_max_predictive_forward", "D_max_forward"),
+                   ("D_max_predictive_reverse", "D_max_reverse")]
+MAP_PRED_COLUMNS = [name for name, _ in _MAP_PRED_PICKS] + ["pareto_k_pred", "pred_ess_min"]
+MAP_PRED_UINT_COLUMNS = ["pred_distinct_min", "map_pred_valid", "map_pred_reliable"]
+MAP_PRED_PREDICTION_COLUMNS = ["median_posterior", "hdpi_lower_posterior", "hdpi_upper_posterior"]
 # "auto": the auto block appended after shortname -- uint32
 # auto_route (the mdfit_auto_route bits) and auto_sampled (1: the row is the
 # sampler's), then float32 pareto_k_max and psis_ess_min (row 6 of the waic
@@ -313,7 +321,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
                summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-               waic: bool = False, auto: bool = False):
+               waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -333,7 +341,10 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     and the sampler over the taxa that does not settle; opts carries both fits'
     options) and the fourth array is the auto block auto[T, 4] f32 = route,
     sampled, khat_max, ess_min; its chunks run one after another, with no
-    transfer overlap.  At most one of the seven."""
+    transfer overlap.  ppred (MAP): mdfit_map_pred follows the fit with
+    psis_draws importance draws per sub-fit and pred_draws predictive draws per
+    job and the fourth array is the posterior predictive block [T, 106] f32 =
+    ppred [3][30] | rec [16] (engine.split_ppred).  At most one of the eight."""
     import torch
 
     from . import engine
@@ -354,7 +365,7 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     # 10k taxa, bench host_to_host) costs no host time, while the host
     # statistics (ingest.noise) take ~1.5 ms of CPU per 10k taxa on the 16-thread
     # share of a multi-file pipeline that is host-bound
-    if auto and (laplace or diag or summary or loo or psis or waic):
+    if auto and (laplace or diag or summary or loo or psis or waic or ppred):
         raise ValueError("auto is the run's only extra block")
     if auto and not grouped:
         try:
@@ -364,18 +375,20 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     if not grouped:
         try:
             return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
-                                         summary=summary, loo=loo, psis=psis, psis_draws=psis_draws, waic=waic)
+                                         summary=summary, loo=loo, psis=psis, psis_draws=psis_draws, waic=waic,
+                                         ppred=ppred, pred_draws=pred_draws)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic, auto)
+        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic, auto,
+                            ppred, pred_draws)
     finally:
         p.release_pinned()
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
                  summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-                 waic: bool = False, auto: bool = False):
+                 waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000):
     import torch
 
     from . import engine
@@ -387,7 +400,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
     rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                        with_psis=psis, with_waic=waic, with_auto=auto)
+                        with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred)
     if hi > lo and auto:  # each rank runs auto on its shard, its rows written in place into the gather buffers
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
                                device=dev, dest=engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo],
@@ -399,7 +412,8 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
                                 with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                                with_psis=psis, psis_draws=psis_draws, with_waic=waic)
+                                with_psis=psis, psis_draws=psis_draws, with_waic=waic, with_ppred=ppred,
+                                pred_draws=pred_draws)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                                                lap=rec.lap[: hi - lo] if laplace else None,
@@ -407,7 +421,8 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
                                                summ=rec.summ[: hi - lo] if summary else None,
                                                loo=rec.loo[: hi - lo] if loo else None,
                                                psis=rec.psis[: hi - lo] if psis else None,
-                                               waic=rec.waic[: hi - lo] if waic else None))
+                                               waic=rec.waic[: hi - lo] if waic else None,
+                                               ppred=rec.ppred[: hi - lo] if ppred else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -416,7 +431,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     if rank != 0:
         return None
     return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
-                           with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto)
+                           with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred)
 
 
 # --------------------------------------------------------------------------
@@ -473,7 +488,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
-                        psis=None, waic=None, auto=None) -> pd.DataFrame:
+                        psis=None, waic=None, auto=None, ppred=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -492,7 +507,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     7, 8] of a "map-waic" run): the MAP_WAIC_COLUMNS follow as float32, then
     map_waic_valid and map_waic_reliable (uint32).  auto (the auto block [T, 4]
     of an "auto" run): auto_route and auto_sampled (uint32), then pareto_k_max
-    and psis_ess_min (float32) follow."""
+    and psis_ess_min (float32) follow.  ppred (the posterior predictive block
+    [T, 106] of a "map-pred" run): the MAP_PRED_COLUMNS follow as float32, then
+    the MAP_PRED_UINT_COLUMNS."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -566,24 +583,45 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["pareto_k_max"] = np.ascontiguousarray(ka[:, 2], dtype=np.float32)
         data["psis_ess_min"] = np.ascontiguousarray(ka[:, 3], dtype=np.float32)
         columns += AUTO_UINT_COLUMNS + AUTO_COLUMNS
+    if ppred is not None:
+        kr = np.asarray(ppred)[:, _lib.NPRED * _lib.NPOS:]
+        kr = kr if keep is None else kr[keep]
+        f = _lib.MAPPRED_FIELDS.index
+        for name, field in _MAP_PRED_PICKS:
+            data[name] = np.ascontiguousarray(kr[:, f(field)], dtype=np.float32)
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)  # (three invalid rows: NaN)
+            data["pareto_k_pred"] = np.nanmax(kr[:, f("khat_all"):f("khat_all") + 3], axis=1).astype(np.float32)
+            data["pred_ess_min"] = np.nanmin(kr[:, f("ess_all"):f("ess_all") + 3], axis=1).astype(np.float32)
+            nd = np.nanmin(kr[:, f("n_distinct_all"):f("n_distinct_all") + 3], axis=1)
+        data["pred_distinct_min"] = _uint32(np.nan_to_num(nd).astype(np.int64))
+        flags = np.nan_to_num(kr[:, f("flags")]).astype(np.int64)
+        data["map_pred_valid"] = ((flags & _lib.MAPPRED_VALID) != 0).astype(np.uint32)
+        data["map_pred_reliable"] = ((flags & _lib.MAPPRED_RELIABLE) != 0).astype(np.uint32)
+        columns += MAP_PRED_COLUMNS + MAP_PRED_UINT_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
-def make_df_fit_predictions(p: Packed, pred, keep, cfg) -> pd.DataFrame:
-    """fits.py:632-665: 30 rows per fitted taxon (z = 1..15, -1..-15)."""
+def make_df_fit_predictions(p: Packed, pred, keep, cfg, ppred=None) -> pd.DataFrame:
+    """fits.py:632-665: 30 rows per fitted taxon (z = 1..15, -1..-15).  ppred
+    (the posterior predictive block [T, 106] of a "map-pred" run): the
+    MAP_PRED_PREDICTION_COLUMNS follow as float32."""
     n = int(keep.sum())
     kp = pred if n == len(keep) else pred[keep]
-    return pd.DataFrame(
-        {
-            "tax_id": _category(p, "tax_id", None if n == len(keep) else keep, _lib.NPOS),
-            "position": np.tile(POSITIONS.astype(np.int8), n),
-            "median": np.ascontiguousarray(kp[:, 0, :], dtype=np.float32).reshape(-1),
-            "hdpi_lower": np.ascontiguousarray(kp[:, 1, :], dtype=np.float32).reshape(-1),
-            "hdpi_upper": np.ascontiguousarray(kp[:, 2, :], dtype=np.float32).reshape(-1),
-            "shortname": _const_category(cfg.shortname, n * _lib.NPOS),
-        },
-        copy=False,
-    )
+    data = {
+        "tax_id": _category(p, "tax_id", None if n == len(keep) else keep, _lib.NPOS),
+        "position": np.tile(POSITIONS.astype(np.int8), n),
+        "median": np.ascontiguousarray(kp[:, 0, :], dtype=np.float32).reshape(-1),
+        "hdpi_lower": np.ascontiguousarray(kp[:, 1, :], dtype=np.float32).reshape(-1),
+        "hdpi_upper": np.ascontiguousarray(kp[:, 2, :], dtype=np.float32).reshape(-1),
+        "shortname": _const_category(cfg.shortname, n * _lib.NPOS),
+    }
+    if ppred is not None:
+        pp = np.asarray(ppred)[:, :_lib.NPRED * _lib.NPOS].reshape(-1, _lib.NPRED, _lib.NPOS)
+        pp = pp if n == len(keep) else pp[keep]
+        for j, name in enumerate(MAP_PRED_PREDICTION_COLUMNS):
+            data[name] = np.ascontiguousarray(pp[:, j, :], dtype=np.float32).reshape(-1)
+    return pd.DataFrame(data, copy=False)
 
 
 def make_opts(cfg, mcmc_kwargs=None):
@@ -595,6 +633,7 @@ def make_opts(cfg, mcmc_kwargs=None):
     "map-laplace" (the MAP fit; wants_laplace adds the standard errors) or
     "map-psis" (the MAP fit; wants_psis adds the importance-sampled posterior) or
     "map-waic" (the MAP fit; wants_waic adds the importance-weighted WAIC comparison) or
+    "map-pred" (the MAP fit; wants_pred adds the importance-weighted posterior predictive) or
     "auto" (one option set for the MAP fit and the sampler of engine.fit_auto_device:
     the sampler's mode and lengths, the MAP fit's defaults)."""
     inference = getattr(cfg, "inference", "nuts")
@@ -609,13 +648,13 @@ def mode_of(inference: str) -> int:
     """The engine mode of an --inference value: "nuts", "nuts-diag",
     "nuts-summary" and "nuts-loo" (the sampler; wants_diag adds mdfit_nuts_diag,
     wants_summary mdfit_nuts_summary, wants_loo mdfit_nuts_loo) or "map" and
-    "map-laplace", "map-psis" and "map-waic".  "auto" runs both: its option set
+    "map-laplace", "map-psis", "map-waic" and "map-pred".  "auto" runs both: its option set
     is the sampler's (engine.auto_opts makes the MAP copy)."""
-    if inference in ("map", "map-laplace", "map-psis", "map-waic"):
+    if inference in ("map", "map-laplace", "map-psis", "map-waic", "map-pred"):
         return _lib.MODE_MAP
     if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo", "auto"):
         return _lib.MODE_NUTS
-    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'map-waic', 'nuts-diag', "
+    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'map-waic', 'map-pred', 'nuts-diag', "
                      "'nuts-summary', 'nuts-loo' or 'auto', "
                      f"got {inference!r}")
 
@@ -650,6 +689,16 @@ def wants_waic(cfg) -> bool:
     return getattr(cfg, "inference", "nuts") == "map-waic"
 
 
+def wants_pred(cfg) -> bool:
+    """cfg.inference "map-pred": the MAP fit followed by mdfit_map_pred."""
+    return getattr(cfg, "inference", "nuts") == "map-pred"
+
+
+def pred_draws_of(cfg) -> int:
+    """The predictive draws per job of a "map-pred" run (cfg.pred_draws, default 1000)."""
+    return int(getattr(cfg, "pred_draws", 1000) or 1000)
+
+
 def wants_auto(cfg) -> bool:
     """cfg.inference "auto": the MAP fit, its importance-sampled correction and
     the sampler over the taxa it cannot settle (engine.fit_auto_device)."""
@@ -657,7 +706,7 @@ def wants_auto(cfg) -> bool:
 
 
 def psis_draws_of(cfg) -> int:
-    """The draws per sub-fit of a "map-psis", "map-waic" or "auto" run (cfg.psis_draws, default 256)."""
+    """The draws per sub-fit of a "map-psis", "map-waic", "map-pred" or "auto" run (cfg.psis_draws, default 256)."""
     return int(getattr(cfg, "psis_draws", 256) or 256)
 
 
@@ -671,7 +720,8 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     p = pack_counts(df_counts, cfg)
     res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
                      summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
-                     psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg), auto=wants_auto(cfg))
+                     psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg), auto=wants_auto(cfg),
+                     ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
@@ -682,12 +732,13 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     loo = rest[0] if rest and wants_loo(cfg) else None
     psis = rest[0] if rest and wants_psis(cfg) else None
     waic = rest[0] if rest and wants_waic(cfg) else None
+    ppred = rest[0] if rest and wants_pred(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
     return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic,
-                                auto=auto),
-            make_df_fit_predictions(p, pred, keep, cfg))
+                                auto=auto, ppred=ppred),
+            make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred))
 
 
 def extract_top_max_fits(df_counts, max_fits):
@@ -734,7 +785,7 @@ def _rank() -> int:
 
 
 CACHE_KEYS = ["min_alignments", "min_y_sum", "substitution_bases_forward", "substitution_bases_reverse",
-              "N_fits", "shortname", "filename", "inference", "psis_draws"]
+              "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws"]
 
 
 def _cache_hit(cfg) -> bool:
@@ -784,7 +835,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
                      laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
                      loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg),
-                     auto=wants_auto(cfg))
+                     auto=wants_auto(cfg), ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
@@ -795,6 +846,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     loo = rest[0] if rest and wants_loo(cfg) else None
     psis = rest[0] if rest and wants_psis(cfg) else None
     waic = rest[0] if rest and wants_waic(cfg) else None
+    ppred = rest[0] if rest and wants_pred(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -803,8 +855,8 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
         from .counts import _save
 
         df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis,
-                                             waic=waic, auto=auto)
-        df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg)
+                                             waic=waic, auto=auto, ppred=ppred)
+        df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
         return df_fit_results, df_fit_predictions

@@ -61,11 +61,13 @@ class Config:
     N_fits: Optional[int] = None
     # this engine's addition: "nuts" samples like the reference (fits.py:382-387),
     # "map" is the frequentist MAP fit (BASELINE config 2); "map-laplace",
-    # "map-psis", "map-waic", "nuts-diag", "nuts-summary" and "nuts-loo" add their columns
+    # "map-psis", "map-waic", "map-pred", "nuts-diag", "nuts-summary" and "nuts-loo" add their columns
     # to fit_results; "auto" samples only the taxa the MAP fit's importance sampling cannot settle; saved in the parquet metadata and part of the cache key
     inference: str = "nuts"
-    # the draws per sub-fit of "map-psis", "map-waic" and "auto" (25..1024); in the metadata of such a run only
+    # the draws per sub-fit of "map-psis", "map-waic", "map-pred" and "auto" (25..1024); in the metadata of such a run only
     psis_draws: int = 256
+    # the predictive draws per job of "map-pred" (25..1024; the reference's 1000); in the metadata of such a run only
+    pred_draws: int = 1000
     N_cores: int = field(init=False)
 
     def __post_init__(self):
@@ -131,8 +133,10 @@ class Config:
 
     def to_dict(self):
         d_out = asdict(self)
-        if self.inference not in ("map-psis", "map-waic", "auto"):
+        if self.inference not in ("map-psis", "map-waic", "map-pred", "auto"):
             del d_out["psis_draws"]
+        if self.inference != "map-pred":
+            del d_out["pred_draws"]
         for key, val in d_out.items():
             if isinstance(val, Path):
                 d_out[key] = str(val)
