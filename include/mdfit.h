@@ -560,6 +560,78 @@ int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, cons
                    int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base,
                    double* waic, double* pointwise, double* draws, void* hip_stream);
 
+/* Adapt record: double adapt[T][3][MDFIT_NMAPADAPT], rows PMD-all, PMD-forward,
+ * PMD-reverse: khat of round 0, ess of round 0, the best round, the rounds
+ * tried (redrawn and smoothed).  NaN in a row that is invalid in round 0 and
+ * for a taxon with status != MDFIT_OK. */
+#define MDFIT_NMAPADAPT 4
+#define MDFIT_ADAPT_MAX_ROUNDS 4
+/* flags bit 6 of a PMD row of the psis and waic records written by the two
+ * entries below: the best round is > 0 (the proposal was refitted). */
+#define MDFIT_FLAG_ADAPTED 64
+
+/*
+ * mdfit_map_psis with moment-matched proposal rounds (MDFIT-ADAPT v1, DESIGN.md
+ * §3.12; importance-weighted moment matching, Paananen et al. 2021).  Round 0
+ * is mdfit_map_psis exactly; a row invalid there stays invalid.  While the best
+ * round's khat is over the threshold of flags bit 1 and fewer than
+ * adapt_rounds rounds have run, the Student-t proposal is refitted to the best
+ * round's smoothed weights w: with rho_j = u_j - K_j c_s the residual of free
+ * coordinate j (K the shift of the centre with a held c, zero when c is free),
+ * the new centre is m_j = sum w rho_j (+ K_j c_s), the new scale the weighted
+ * covariance C of rho -- d_j = sqrt(C_jj) and the upper-triangular factor F of
+ * C_jm / (d_j d_m) = (F F')_jm -- and, with c held on 0, the exponential's new
+ * rate 1 / sum w c_s.  All num_draws draws are redrawn from the same Philox
+ * blocks, weighted and smoothed again; the round becomes the best one when it
+ * is valid and its khat is finite and below the best one's, and ends the loop
+ * otherwise, as do a C_jj that is not > 0, a pivot of the factor <= 1e-8, a
+ * mean held c that is not > 0 and anything non-finite.  The record is that of
+ * the best round, with MDFIT_FLAG_ADAPTED in flags when that is not round 0.
+ * With adapt_rounds = 0 psis and draws are mdfit_map_psis's bit for bit and
+ * adapt reads (khat, ess, 0, 0).
+ *   adapt_rounds : R in [0, MDFIT_ADAPT_MAX_ROUNDS] (else MDFIT_E_ARG)
+ *   adapt      : double[n_taxa][3][MDFIT_NMAPADAPT], or NULL       (device)
+ *   draws      : as mdfit_map_psis's, of the best round.  The constants dropped
+ *                from log g differ from round to round, so raw log-weights
+ *                compare within a round only; the weights are normalised
+ * The other arguments, the launch and its guarantees are mdfit_map_psis's; the
+ * records do not depend on the grid, the chunking or index_base's split.
+ */
+int mdfit_map_psis_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                         int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed,
+                         int64_t index_base, double* psis, double* adapt, double* draws, void* hip_stream);
+
+/*
+ * mdfit_map_waic with the rounds of mdfit_map_psis_adapt on its PMD rows (0, 2,
+ * 3): their khat, ess, n_infeasible, flags and adapt rows are
+ * mdfit_map_psis_adapt's bit for bit, and their WAIC statistics those of the
+ * best round's weights.  The null rows (1, 4, 5) are not adapted: they are
+ * mdfit_map_waic's bit for bit.  With adapt_rounds = 0 waic, pointwise and
+ * draws are mdfit_map_waic's bit for bit.
+ *   adapt      : double[n_taxa][3][MDFIT_NMAPADAPT] (rows PMD-all, PMD-forward,
+ *                PMD-reverse), or NULL                              (device)
+ */
+int mdfit_map_waic_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                         int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed,
+                         int64_t index_base, double* waic, double* adapt, double* pointwise, double* draws,
+                         void* hip_stream);
+
+/*
+ * Test helper: the refit of one round of mdfit_map_psis_adapt (its device
+ * function) on given series, one wave per series: from draws u[n_series][S][4]
+ * = (logit q, logit A, c, log delta), normalised weights w[n_series][S] (a draw
+ * of weight 0 takes no part and may hold anything), the free mask[i] (bit j:
+ * coordinate j free), c_held[i] (non-zero: c is held on 0 and u[2] its
+ * exponential draw) and the shift K[n_series][4], prop[n_series][25] = m[4],
+ * d[4], F[4][4] (row-major, F[j][p], p >= j; a held coordinate: m = 0, d = 1,
+ * the identity's row and column), the exponential's rate (0 with c free); and
+ * ok[i] = 1, or 0 and NaN where the round stops.  S in [25, 1024] (else
+ * MDFIT_E_ARG); n_series at most 2^25.  Device pointers.
+ */
+int mdfit_adapt_proposal(const double* u, const double* w, const int32_t* mask, const int32_t* c_held,
+                         const double* K, int64_t n_series, int32_t S, double* prop, int32_t* ok,
+                         void* hip_stream);
+
 /* Importance-weighted posterior predictive record: double rec[T][MDFIT_NMAPPRED]:
  * D_max, D_max_lower_hpdi, D_max_upper_hpdi (job 0), D_max_forward (job 30),
  * D_max_reverse (job 31), khat of rows 0..2 (PMD-all, PMD-forward,

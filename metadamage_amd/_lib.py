@@ -90,6 +90,15 @@ MAPPSIS_FIELDS = ["q_mean", "A_mean", "c_mean", "phi_mean", "D_max_mean", "q_std
                   "D_max_std", "rho_Ac", "significance", "khat", "ess", "n_infeasible", "flags"]
 MAPPSIS_VALID, MAPPSIS_RELIABLE = 1, 2  # flags: bit 0 valid, bit 1 khat <= threshold, bits 2..5 coordinate free
 
+# adapt record (mdfit_map_psis_adapt, mdfit_map_waic_adapt): float64 [T][3][NMAPADAPT], rows as the psis record's
+NMAPADAPT = 4
+MAPADAPT_FIELDS = ["khat_initial", "ess_initial", "best_round", "rounds_tried"]
+MAPPSIS_ADAPTED = 64  # flags bit 6 of a PMD row of the psis and waic records: the best round is > 0
+ADAPT_MAX_ROUNDS = 4
+# the adapt block that leaves the device (ChunkedFitter psis_adapt): float32 [T][NADAPTOUT]
+NADAPTOUT = 2
+ADAPTOUT_FIELDS = ["khat_initial_max", "best_round_max"]
+
 # importance-weighted WAIC record (mdfit_map_waic): float64 [T][NWAICROW][NMAPWAIC], rows 0..5 in SUBFITS order ...
 NWAICROW = 7
 MAPWAIC_FIELDS = ["elpd_waic", "p_waic", "lppd", "khat", "ess", "n_infeasible", "p_waic_max", "flags"]
@@ -133,6 +142,9 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_psis",
     "mdfit_psis_weights",
     "mdfit_map_waic",
+    "mdfit_map_psis_adapt",
+    "mdfit_map_waic_adapt",
+    "mdfit_adapt_proposal",
     "mdfit_map_pred",
     "mdfit_resample",
     "mdfit_betabinom_logpmf",
@@ -229,6 +241,12 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_map_psis.restype = ctypes.c_int
     lib.mdfit_map_waic.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp, vp]
     lib.mdfit_map_waic.restype = ctypes.c_int
+    lib.mdfit_map_psis_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp]
+    lib.mdfit_map_psis_adapt.restype = ctypes.c_int
+    lib.mdfit_map_waic_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]
+    lib.mdfit_map_waic_adapt.restype = ctypes.c_int
+    lib.mdfit_adapt_proposal.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
+    lib.mdfit_adapt_proposal.restype = ctypes.c_int
     lib.mdfit_map_pred.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]
     lib.mdfit_map_pred.restype = ctypes.c_int
     lib.mdfit_resample.argtypes = [vp, i64, i32, i32, vp, vp, vp]

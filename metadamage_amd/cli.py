@@ -66,6 +66,8 @@ def cli_fit(
     psis_draws: int = typer.Option(256, help="map-psis, map-waic, map-pred, auto: importance draws per sub-fit, "
                                    "25 to 1024"),
     pred_draws: int = typer.Option(1000, help="map-pred: predictive draws per position, 25 to 1024"),
+    psis_adapt: int = typer.Option(0, help="map-psis, map-waic, auto: at most this many moment-matched proposal "
+                                   "rounds for a sub-fit whose Pareto-k is over the threshold, 0 to 4"),
 ):
     """Fitting Ancient Damage.
 
@@ -88,6 +90,7 @@ def cli_fit(
         "inference": inference,
         "psis_draws": psis_draws,
         "pred_draws": pred_draws,
+        "psis_adapt": psis_adapt,
     }
     if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "nuts-diag",
                          "nuts-summary", "nuts-loo", "auto"):
@@ -97,6 +100,10 @@ def cli_fit(
         raise typer.BadParameter("--psis-draws must be in [25, 1024]")
     if not 25 <= pred_draws <= 1024:
         raise typer.BadParameter("--pred-draws must be in [25, 1024]")
+    if not 0 <= psis_adapt <= 4:
+        raise typer.BadParameter("--psis-adapt must be in [0, 4]")
+    if psis_adapt and inference not in ("map-psis", "map-waic", "auto"):
+        raise typer.BadParameter("--psis-adapt goes with --inference map-psis, map-waic or auto")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

@@ -2102,10 +2102,30 @@ int mdfit_map_psis(const uint32_t* y, const uint32_t* N, const double* out, cons
   if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
   const int S = (int)num_draws;
   mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mp::map_psis_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+  hipLaunchKernelGGL(mp::map_psis_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
                      (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), psis, draws);
+                     seed, index_base, mp::khat_threshold(S), psis, draws, 0, (double*)nullptr);
   return check_launch("map_psis_kernel");
+}
+
+int mdfit_map_psis_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                         int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
+                         double* psis, double* adapt, double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
+    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !psis) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mp::map_psis_kernel<true>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), psis, draws, (int)adapt_rounds, adapt);
+  return check_launch("map_psis_kernel<adapt>");
 }
 
 int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
@@ -2121,10 +2141,46 @@ int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, cons
   if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
   const int S = (int)num_draws;
   mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mw::map_waic_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+  hipLaunchKernelGGL(mw::map_waic_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
                      (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), waic, pointwise, draws);
+                     seed, index_base, mp::khat_threshold(S), waic, pointwise, draws, 0, (double*)nullptr);
   return check_launch("map_waic_kernel");
+}
+
+int mdfit_map_waic_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                         int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
+                         double* waic, double* adapt, double* pointwise, double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace mw = mdfit::mapwaic;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
+    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !waic) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mw::map_waic_kernel<true>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), waic, pointwise, draws, (int)adapt_rounds, adapt);
+  return check_launch("map_waic_kernel<adapt>");
+}
+
+int mdfit_adapt_proposal(const double* u, const double* w, const int32_t* mask, const int32_t* c_held, const double* K,
+                         int64_t n_series, int32_t S, double* prop, int32_t* ok, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
+  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
+  if (n_series == 0) return 0;
+  if (!u || !w || !mask || !c_held || !K || !prop || !ok) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mdfit::mapadapt::adapt_proposal_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
+                     (size_t)S * sizeof(double), (hipStream_t)hip_stream, u, w, mask, c_held, K, n_series, (int)S, prop,
+                     ok);
+  return check_launch("adapt_proposal_kernel");
 }
 
 int mdfit_map_pred(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,

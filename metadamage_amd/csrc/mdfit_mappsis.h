@@ -442,6 +442,10 @@ __device__ __forceinline__ void scaled_factor(const double H[10], unsigned free_
   }
 }
 
+}  // namespace mdfit::mappsis
+#include "mdfit_mapadapt.h"  // (the refit of a round: needs psis_draw and the proposal's layout above)
+namespace mdfit::mappsis {
+
 // the kernel's draws for psis_estimates: regenerated from the stream
 struct StreamDraws {
   const double* P;
@@ -465,12 +469,25 @@ struct StreamDraws {
 // phase 4 psis_estimates with the draws regenerated from the stream.
 // Dynamic LDS: work_len(S) doubles (22,016 B at S = 1024, 6,656 B at S = 256);
 // static: 1,280 B.  Reads y, N, out and status only.
+//
+// kAdapt (mdfit_map_psis_adapt, MDFIT-ADAPT v1): phases 2-3
+// run once per round.  A row whose khat is over tau gets its proposal refitted
+// to the weighted draws (mdfit_mapadapt.h), in place in s_par[s] with the best
+// round's 32 words kept one per lane in a register, and is drawn and smoothed
+// again from the same stream; a round that lowers khat becomes the best one,
+// any other ends the loop: the best proposal is put back and phases 2-3 run
+// once more on it, which brings its weights back into the work buffer bit for
+// bit (no second copy of the weights and no further LDS: the blocks per CU are
+// the plain kernel's).  adapt_rounds = 0 is the plain kernel's arithmetic.
+// adapt: [T][3][4], optional.
+template <bool kAdapt>
 __global__ __launch_bounds__(64) void map_psis_kernel(const uint32_t* __restrict__ gy,
                                                       const uint32_t* __restrict__ gN,
                                                       const double* __restrict__ out,
                                                       const int32_t* __restrict__ status, int64_t n_taxa, int S,
                                                       uint64_t seed, int64_t index_base, double tau,
-                                                      double* __restrict__ psis, double* __restrict__ draws) {
+                                                      double* __restrict__ psis, double* __restrict__ draws,
+                                                      int adapt_rounds, double* __restrict__ adapt) {
   extern __shared__ double s_w[];
   __shared__ double s_y[kLD], s_N[kLD];
   __shared__ double s_par[3][kNPar];
@@ -485,6 +502,8 @@ __global__ __launch_bounds__(64) void map_psis_kernel(const uint32_t* __restrict
     if (lane < 3) invalid_row(psis + (t * 3 + lane) * MDFIT_NMAPPSIS, 0u);
     if (draws != nullptr)
       for (int64_t i = lane; i < (int64_t)3 * S * 6; i += 64) draws[t * 3 * S * 6 + i] = NAN;
+    if constexpr (kAdapt)
+      if (adapt != nullptr && lane < 12) adapt[t * 12 + lane] = NAN;
     return;
   }
   if (lane < kLD) {
@@ -569,6 +588,8 @@ __global__ __launch_bounds__(64) void map_psis_kernel(const uint32_t* __restrict
       if (lane == 0) invalid_row(rec, mask);
       if (dr != nullptr)
         for (int i = lane; i < S * 6; i += 64) dr[i] = NAN;
+      if constexpr (kAdapt)
+        if (adapt != nullptr && lane < 4) adapt[(t * 3 + s) * 4 + lane] = NAN;
       continue;
     }
     Stream st;
@@ -577,38 +598,82 @@ __global__ __launch_bounds__(64) void map_psis_kernel(const uint32_t* __restrict
     st.c0 = (uint32_t)gtaxon;
     st.c1 = (uint32_t)(gtaxon >> 32) + ((uint32_t)(s == 0 ? 0 : s + 1) << 24);  // the chain's sub-fit index: 0, 2, 3
     const int lo = s == 2 ? kNHalf : 0, hi = s == 1 ? kNHalf : kNPos;
-    // ---- phase 2: lanes over draws ----
-    for (int i = lane; i < S; i += 64) {
-      const DrawU r = psis_draw(P, st, i);
-      const ThetaD th = psis_theta(r);
-      double lw = -INFINITY;
-      if (th.feasible) {
-        const double ph = th.delta + 2.0;
-        double ll = 0.0;
+    // the rounds of MDFIT-ADAPT v1 (one pass without kAdapt): a round's proposal is written over the best one
+    // in s_par[s], which lane j < 32 keeps word j of in `keep` and puts back when the round is dropped
+    double khat, n_inf;
+    bool okw;
+    double k0 = NAN, ess0 = NAN, k_best = NAN, keep = 0.0;
+    int best = 0, tried = 0;
+    bool rerun = false;
+    for (int rnd = 0;;) {
+      // ---- phase 2: lanes over draws ----
+      for (int i = lane; i < S; i += 64) {
+        const DrawU r = psis_draw(P, st, i);
+        const ThetaD th = psis_theta(r);
+        double lw = -INFINITY;
+        if (th.feasible) {
+          const double ph = th.delta + 2.0;
+          double ll = 0.0;
 #pragma unroll 1
-        for (int col = lo; col < hi; ++col) {
-          const int kk = col < kNHalf ? col : col - kNHalf;
-          const double D = fma(th.A, powk(th.omq, kk), th.c);
-          ll += bb_logpmf(s_y[col], s_N[col], D, ph);
+          for (int col = lo; col < hi; ++col) {
+            const int kk = col < kNHalf ? col : col - kNHalf;
+            const double D = fma(th.A, powk(th.omq, kk), th.c);
+            ll += bb_logpmf(s_y[col], s_N[col], D, ph);
+          }
+          lw = (ll + th.lj) - r.lg;
         }
-        lw = (ll + th.lj) - r.lg;
+        s_w[i] = lw;
+        if (dr != nullptr) {
+          dr[i * 6 + 0] = r.u0;
+          dr[i * 6 + 1] = r.u1;
+          dr[i * 6 + 2] = r.u2;
+          dr[i * 6 + 3] = r.u3;
+          dr[i * 6 + 4] = lw;
+        }
       }
-      s_w[i] = lw;
-      if (dr != nullptr) {
-        dr[i * 6 + 0] = r.u0;
-        dr[i * 6 + 1] = r.u1;
-        dr[i * 6 + 2] = r.u2;
-        dr[i * 6 + 3] = r.u3;
-        dr[i * 6 + 4] = lw;
+      // ---- phase 3: the smoothed weights; phase 4: the estimates ----
+      okw = psis_weights(w, s_w, S, khat, n_inf);
+      if constexpr (!kAdapt) {
+        break;
+      } else {
+        if (rerun) break;  // (the best round's weights are back in s_w, khat and n_inf its own)
+        if (rnd == 0) {
+          if (!okw) break;
+          k0 = khat;
+          ess0 = mapadapt::weights_ess(w, s_w, S);
+        } else {
+          tried = rnd;
+          if (!(okw && isfinite(khat) && khat < k_best)) {  // 6. the round is dropped: the best one once more
+            if (lane < kNPar) s_par[s][lane] = keep;
+            __syncthreads();
+            rerun = true;
+            continue;
+          }
+          best = rnd;
+        }
+        k_best = khat;
+        if (rnd == adapt_rounds || k_best <= tau) break;              // 1. the stop test
+        if (lane < kNPar) keep = s_par[s][lane];
+        if (!mapadapt::next_proposal(s_w, S, s_par[s], st)) break;  // 2-4. the refitted proposal, in place
+        ++rnd;
       }
     }
-    // ---- phase 3: the smoothed weights; phase 4: the estimates ----
-    double khat, n_inf;
-    const bool okw = psis_weights(w, s_w, S, khat, n_inf);
     if (okw) {
       psis_estimates(w, s_w, S, StreamDraws{P, st}, khat, n_inf, tau, mask, rec);
     } else if (lane == 0) {
       invalid_row(rec, mask);
+    }
+    if constexpr (kAdapt) {
+      if (lane == 0) {
+        if (okw && best > 0) rec[kFlags] += (double)mapadapt::kAdaptedBit;
+        if (adapt != nullptr) {
+          double* ar = adapt + (t * 3 + s) * 4;
+          ar[mapadapt::kKhat0] = k0;
+          ar[mapadapt::kEss0] = ess0;
+          ar[mapadapt::kBestRound] = okw ? (double)best : NAN;
+          ar[mapadapt::kRoundsTried] = okw ? (double)tried : NAN;
+        }
+      }
     }
     if (dr != nullptr)
       for (int i = lane; i < S; i += 64) dr[i * 6 + 5] = okw ? s_w[i] : NAN;

@@ -359,13 +359,20 @@ __device__ __forceinline__ void proposals(const uint32_t* __restrict__ gy, const
 // then waic_row.  Row 6 is nutsloo::n_sigma on the waic_i columns, as
 // nuts_loo_kernel's.  Dynamic LDS: lds_len(S) doubles (22,016 B at S = 1024,
 // 11,048 B at S = 256); static: 4,448 B.  Reads y, N, out and status only.
+//
+// kAdapt (mdfit_map_waic_adapt, MDFIT-ADAPT v1): the PMD rows'
+// phases 2-3 run in map_psis_kernel<true>'s rounds, statement for statement, so
+// their khat, ess, n_infeasible, flags and adapt record are its bits; the null
+// rows take one pass.  The shift s_l0 is the log-pmf at the best round's centre.
+template <bool kAdapt>
 __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict__ gy,
                                                       const uint32_t* __restrict__ gN,
                                                       const double* __restrict__ out,
                                                       const int32_t* __restrict__ status, int64_t n_taxa, int S,
                                                       uint64_t seed, int64_t index_base, double tau,
                                                       double* __restrict__ waic, double* __restrict__ pointwise,
-                                                      double* __restrict__ draws) {
+                                                      double* __restrict__ draws, int adapt_rounds,
+                                                      double* __restrict__ adapt) {
   extern __shared__ double s_w[];
   __shared__ double s_y[kLD], s_N[kLD];
   __shared__ double s_par[MDFIT_NSUBFIT][kNPar];
@@ -384,6 +391,8 @@ __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict
       for (int i = lane; i < MDFIT_NSUBFIT * kMaxPts * 2; i += 64) pw[i] = NAN;
     if (dr0 != nullptr)
       for (int64_t i = lane; i < (int64_t)MDFIT_NSUBFIT * S * 6; i += 64) dr0[i] = NAN;
+    if constexpr (kAdapt)
+      if (adapt != nullptr && lane < 12) adapt[t * 12 + lane] = NAN;
     return;
   }
   if (lane < kLD) {
@@ -417,63 +426,105 @@ __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict
       st.k1 = (uint32_t)(seed >> 32);
       st.c0 = (uint32_t)gtaxon;
       st.c1 = (uint32_t)(gtaxon >> 32) + ((uint32_t)s << 24);  // the chain's sub-fit index
-      // ---- phase 2: lanes over draws ----
-      for (int i = lane; i < S; i += 64) {
-        const DrawU r = mappsis::psis_draw(P, st, i);
-        double lw = -INFINITY;
-        if (pmd) {
-          const ThetaD th = mappsis::psis_theta(r);
-          if (th.feasible) {
+      // the rounds of MDFIT-ADAPT v1 for a PMD row (one pass otherwise): a round's proposal is written over the
+      // best one in s_par[s], which lane j < 32 keeps word j of in `keep` and puts back when the round is dropped
+      double khat, n_inf;
+      double k0 = NAN, ess0 = NAN, k_best = NAN, keep = 0.0;
+      int best = 0, tried = 0;
+      bool rerun = false;
+      for (int rnd = 0;;) {
+        // ---- phase 2: lanes over draws ----
+        for (int i = lane; i < S; i += 64) {
+          const DrawU r = mappsis::psis_draw(P, st, i);
+          double lw = -INFINITY;
+          if (pmd) {
+            const ThetaD th = mappsis::psis_theta(r);
+            if (th.feasible) {
+              const double ph = th.delta + 2.0;
+              double ll = 0.0;
+#pragma unroll 1
+              for (int col = lo; col < hi; ++col) {
+                const int kk = col < kNHalf ? col : col - kNHalf;
+                const double D = fma(th.A, powk(th.omq, kk), th.c);
+                ll += bb_logpmf(s_y[col], s_N[col], D, ph);
+              }
+              lw = (ll + th.lj) - r.lg;
+            }
+          } else {
+            const ThetaD th = null_theta(r);
             const double ph = th.delta + 2.0;
             double ll = 0.0;
 #pragma unroll 1
-            for (int col = lo; col < hi; ++col) {
-              const int kk = col < kNHalf ? col : col - kNHalf;
-              const double D = fma(th.A, powk(th.omq, kk), th.c);
-              ll += bb_logpmf(s_y[col], s_N[col], D, ph);
-            }
+            for (int col = lo; col < hi; ++col) ll += bb_logpmf(s_y[col], s_N[col], th.q, ph);
             lw = (ll + th.lj) - r.lg;
           }
+          s_w[i] = lw;
+          if (dr != nullptr) {
+            dr[i * 6 + 0] = r.u0;
+            dr[i * 6 + 1] = r.u1;
+            dr[i * 6 + 2] = r.u2;
+            dr[i * 6 + 3] = r.u3;
+            dr[i * 6 + 4] = lw;
+          }
+        }
+        // the shift of the second moments: the log-pmf at the mode (lanes over points)
+        if (lane < n) {
+          DrawU m;
+          m.u0 = P[kPU + 0];
+          m.u1 = P[kPU + 1];
+          m.u2 = P[kPU + 2];
+          m.u3 = P[kPU + 3];
+          m.lg = 0.0;
+          const DrawPt d = draw_point(pmd, m);
+          const int col = lo + lane;
+          const int kk = col < kNHalf ? col : col - kNHalf;
+          const double l = bb_logpmf(s_y[col], s_N[col], fma(d.A, powk(d.w, kk), d.c), d.ph);
+          s_l0[lane] = isfinite(l) ? l : 0.0;
+        }
+        // ---- phase 3: the smoothed weights ----
+        ok = mappsis::psis_weights(w, s_w, S, khat, n_inf);
+        if constexpr (!kAdapt) {
+          break;
         } else {
-          const ThetaD th = null_theta(r);
-          const double ph = th.delta + 2.0;
-          double ll = 0.0;
-#pragma unroll 1
-          for (int col = lo; col < hi; ++col) ll += bb_logpmf(s_y[col], s_N[col], th.q, ph);
-          lw = (ll + th.lj) - r.lg;
-        }
-        s_w[i] = lw;
-        if (dr != nullptr) {
-          dr[i * 6 + 0] = r.u0;
-          dr[i * 6 + 1] = r.u1;
-          dr[i * 6 + 2] = r.u2;
-          dr[i * 6 + 3] = r.u3;
-          dr[i * 6 + 4] = lw;
+          if (!pmd || rerun) break;  // (rerun: the best round's weights are back in s_w, khat and n_inf its own)
+          if (rnd == 0) {
+            if (!ok) break;
+            k0 = khat;
+            ess0 = mapadapt::weights_ess(w, s_w, S);
+          } else {
+            tried = rnd;
+            if (!(ok && isfinite(khat) && khat < k_best)) {  // 6. the round is dropped: the best one once more
+              if (lane < kNPar) s_par[s][lane] = keep;
+              __syncthreads();
+              rerun = true;
+              continue;
+            }
+            best = rnd;
+          }
+          k_best = khat;
+          if (rnd == adapt_rounds || k_best <= tau) break;              // 1. the stop test
+          if (lane < kNPar) keep = s_par[s][lane];
+          if (!mapadapt::next_proposal(s_w, S, s_par[s], st)) break;  // 2-4. the refitted proposal, in place
+          ++rnd;
         }
       }
-      // the shift of the second moments: the log-pmf at the mode (lanes over points)
-      if (lane < n) {
-        DrawU m;
-        m.u0 = P[kPU + 0];
-        m.u1 = P[kPU + 1];
-        m.u2 = P[kPU + 2];
-        m.u3 = P[kPU + 3];
-        m.lg = 0.0;
-        const DrawPt d = draw_point(pmd, m);
-        const int col = lo + lane;
-        const int kk = col < kNHalf ? col : col - kNHalf;
-        const double l = bb_logpmf(s_y[col], s_N[col], fma(d.A, powk(d.w, kk), d.c), d.ph);
-        s_l0[lane] = isfinite(l) ? l : 0.0;
+      if constexpr (kAdapt) {
+        if (pmd && adapt != nullptr && lane == 0) {
+          double* ar = adapt + (t * 3 + (s == 0 ? 0 : s - 1)) * 4;
+          ar[mapadapt::kKhat0] = k0;
+          ar[mapadapt::kEss0] = ess0;
+          ar[mapadapt::kBestRound] = ok ? (double)best : NAN;
+          ar[mapadapt::kRoundsTried] = ok ? (double)tried : NAN;
+        }
       }
-      // ---- phase 3: the smoothed weights ----
-      double khat, n_inf;
-      ok = mappsis::psis_weights(w, s_w, S, khat, n_inf);
       if (dr != nullptr)
         for (int i = lane; i < S; i += 64) dr[i * 6 + 5] = ok ? s_w[i] : NAN;
       if (ok) {
         // ---- phase 4: the pointwise statistics, the row ----
         waic_points(w, s_w, S, n, StreamSource{P, st, pmd, lo, s_y, s_N}, s_l0, tile, s_acc, s_pt[0], s_pt[1]);
         const double ess = waic_row(w, s_pt[0], s_pt[1], n, s_w, S, khat, n_inf, tau, mask, rec + s * MDFIT_NMAPWAIC);
+        if constexpr (kAdapt)
+          if (best > 0 && lane == 0) rec[s * MDFIT_NMAPWAIC + kFlags] += (double)mapadapt::kAdaptedBit;
         kmax = fmax(kmax, khat);
         emin = fmin(emin, ess);
         all_rel = all_rel && khat <= tau;
@@ -486,6 +537,8 @@ __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict
     } else if (dr != nullptr) {
       for (int i = lane; i < S * 6; i += 64) dr[i] = NAN;
     }
+    if constexpr (kAdapt)
+      if (!ok && pmd && adapt != nullptr && lane < 4) adapt[(t * 3 + (s == 0 ? 0 : s - 1)) * 4 + lane] = NAN;
     if (!ok) {
       all_ok = false;
       if (lane == 0) invalid_row(rec + s * MDFIT_NMAPWAIC, mask);

@@ -45,6 +45,7 @@ class FitBatch:
     waic: "object" = None  # torch.float32 [T, 7, NMAPWAIC]: the importance-weighted WAIC records (with_waic)
     ppred: "object" = None  # torch.float32 [T, PPRED_WORDS]: the posterior predictive block (with_ppred; split_ppred)
     auto: "object" = None  # torch.float32 [T, NAUTO]: route, sampled, khat_max, ess_min (fit_auto_chunks)
+    adapt: "object" = None  # torch.float32 [T, NADAPTOUT]: largest round-0 khat, largest best round (psis_adapt > 0)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -158,22 +159,32 @@ def map_laplace_device(ty, tN, res: FitBatch, lap=None, gh=None, stream=None, u=
 
 
 def map_psis_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, psis=None,
-                    draws=None, stream=None):
+                    draws=None, stream=None, adapt_rounds: int = 0, adapt=None):
     """Launch mdfit_map_psis on the records of a finished MAP call (asynchronous
     on `stream`): the importance-sampled posterior of the three PMD sub-fits
     (MDFIT-PSIS v1), float64 psis[T, 3, NMAPPSIS] (_lib.MAPPSIS_FIELDS).  The
     Philox streams are keyed by (seed, index_base + taxon, sub-fit).  draws:
     None, True (allocated) or a float64 tensor [T, 3, num_draws, 6] = u[4], the
     raw log-weight, the weight.  Returns psis, or (psis, draws) when draws is
-    asked for."""
+    asked for.
+
+    adapt_rounds > 0, or adapt given (True: allocated, or a float64 tensor [T, 3,
+    NMAPADAPT]): mdfit_map_psis_adapt (MDFIT-ADAPT v1) with at most adapt_rounds
+    moment-matched proposal rounds per row; the adapt block (_lib.MAPADAPT_FIELDS)
+    is then the last element of the returned tuple, and draws are the best
+    round's."""
     torch = _torch()
     lib = _lib.load()
-    T, S = int(ty.shape[0]), int(num_draws)
+    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
+    use_adapt = R != 0 or adapt is not None
+    if use_adapt and (adapt is None or adapt is True):
+        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
     if psis is None:
         psis = torch.empty((T, 3, _lib.NMAPPSIS), dtype=torch.float64, device=ty.device)
     if draws is True:
         draws = torch.empty((T, 3, S, 6), dtype=torch.float64, device=ty.device)
-    for name, t, n in (("psis", psis, T * 3 * _lib.NMAPPSIS), ("draws", draws, T * 3 * S * 6)):
+    for name, t, n in (("psis", psis, T * 3 * _lib.NMAPPSIS), ("draws", draws, T * 3 * S * 6),
+                       ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
         if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
             raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
     for name, a in (("y", ty), ("N", tN)):
@@ -181,6 +192,13 @@ def map_psis_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
             raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
     if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
         raise ValueError("res must hold the contiguous records of these T taxa")
+    if use_adapt:
+        _lib.check(lib.mdfit_map_psis_adapt(
+            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
+            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(seed), int(index_base),
+            ctypes.c_void_p(psis.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
+            ctypes.c_void_p(draws.data_ptr()) if draws is not None else None, _stream_handle(torch, stream)))
+        return (psis, adapt) if draws is None else (psis, draws, adapt)
     _lib.check(lib.mdfit_map_psis(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
                                   ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S,
                                   int(seed), int(index_base), ctypes.c_void_p(psis.data_ptr()),
@@ -190,7 +208,7 @@ def map_psis_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
 
 
 def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, waic=None,
-                    pointwise=None, draws=None, stream=None):
+                    pointwise=None, draws=None, stream=None, adapt_rounds: int = 0, adapt=None):
     """Launch mdfit_map_waic on the records of a finished MAP call (asynchronous
     on `stream`): the importance-weighted WAIC of the six sub-fits and the
     reference's comparisons on it (MDFIT-WAIC v1), float64 waic[T, 7, NMAPWAIC]
@@ -199,10 +217,17 @@ def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
     True (allocated) or a float64 tensor [T, 6, 30, 2] = (lppd_i, p_i); draws:
     None, True or a float64 tensor [T, 6, num_draws, 6] = u[4], the raw
     log-weight, the weight.  Returns waic, or the tuple (waic[, pointwise][,
-    draws]) of what was asked for."""
+    draws]) of what was asked for.
+
+    adapt_rounds > 0, or adapt given (True, or a float64 tensor [T, 3,
+    NMAPADAPT]): mdfit_map_waic_adapt, the PMD rows with mdfit_map_psis_adapt's
+    rounds; the adapt block is then the last element of the returned tuple."""
     torch = _torch()
     lib = _lib.load()
-    T, S = int(ty.shape[0]), int(num_draws)
+    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
+    use_adapt = R != 0 or adapt is not None
+    if use_adapt and (adapt is None or adapt is True):
+        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
     if waic is None:
         waic = torch.empty((T, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=ty.device)
     if pointwise is True:
@@ -211,7 +236,7 @@ def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
         draws = torch.empty((T, _lib.NSUBFIT, S, 6), dtype=torch.float64, device=ty.device)
     for name, t, n in (("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC),
                        ("pointwise", pointwise, T * _lib.NSUBFIT * _lib.NPOS * 2),
-                       ("draws", draws, T * _lib.NSUBFIT * S * 6)):
+                       ("draws", draws, T * _lib.NSUBFIT * S * 6), ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
         if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
             raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
     for name, a in (("y", ty), ("N", tN)):
@@ -219,6 +244,14 @@ def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
             raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
     if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
         raise ValueError("res must hold the contiguous records of these T taxa")
+    if use_adapt:
+        _lib.check(lib.mdfit_map_waic_adapt(
+            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
+            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(seed), int(index_base),
+            ctypes.c_void_p(waic.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
+            ctypes.c_void_p(pointwise.data_ptr()) if pointwise is not None else None,
+            ctypes.c_void_p(draws.data_ptr()) if draws is not None else None, _stream_handle(torch, stream)))
+        return (waic,) + tuple(x for x in (pointwise, draws) if x is not None) + (adapt,)
     _lib.check(lib.mdfit_map_waic(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
                                   ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S,
                                   int(seed), int(index_base), ctypes.c_void_p(waic.data_ptr()),
@@ -303,9 +336,23 @@ def auto_opts(opts: _lib.MdfitOpts | None):
     return o_map, o_nuts
 
 
+def adapt_summary(adapt, out=None):
+    """The adapt block that leaves the device, float32 [T, NADAPTOUT], from the
+    adapt record float64 [T, 3, NMAPADAPT], reduced on the device: the largest
+    round-0 khat and the largest best round over the taxon's valid PMD rows (NaN
+    when it has none)."""
+    torch = _torch()
+    neg = torch.nan_to_num(adapt[:, :, [0, 2]], nan=-float("inf")).amax(dim=1)
+    neg = torch.where(torch.isneginf(neg), torch.full_like(neg, float("nan")), neg)
+    if out is None:
+        return neg.to(torch.float32)
+    out.copy_(neg)
+    return out
+
+
 def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_draws: int = 256,
                     res: FitBatch | None = None, stream=None, budget_bytes: int | None = None,
-                    sub_chunk_taxa: int = 0, timings: dict | None = None):
+                    sub_chunk_taxa: int = 0, timings: dict | None = None, psis_adapt: int = 0):
     """The auto inference of a device-resident batch (MDFIT-AUTO v1, DESIGN.md
     §3.10): the MAP fit, mdfit_map_psis and mdfit_map_waic with psis_draws draws
     per sub-fit, mdfit_auto_route -- which composes the record of every taxon
@@ -324,7 +371,10 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
     `stream` (default: the current stream).
 
     Returns (res, route int32 [T], auto float32 [T, NAUTO] = route, sampled 0/1,
-    khat_max, ess_min -- row 6 fields 4, 5 of the waic record).  timings (a
+    khat_max, ess_min -- row 6 fields 4, 5 of the waic record).  psis_adapt > 0:
+    both launches run at most that many moment-matched proposal rounds per PMD
+    row (MDFIT-ADAPT v1; the routing rule is untouched) and res.adapt is the
+    float32 [T, NADAPTOUT] block of adapt_summary.  timings (a
     dict): filled with the milliseconds of each of AUTO_STAGES, n_sampled and
     n_sub_chunks (adds a synchronisation at the end)."""
     torch = _torch()
@@ -348,10 +398,20 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
         mark("start")
         fit_batch_device(ty, tN, tm, o_map, res, stream=s)
         mark("map")
-        psis = map_psis_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s)
-        mark("psis")
-        waic = map_waic_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s)
-        mark("waic")
+        if int(psis_adapt) > 0:  # (MDFIT-ADAPT v1 in both launches: their PMD rows agree bit for bit)
+            psis, ad = map_psis_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s,
+                                       adapt_rounds=psis_adapt)
+            mark("psis")
+            waic, _ = map_waic_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s,
+                                      adapt_rounds=psis_adapt, adapt=ad)
+            mark("waic")
+            res.adapt = adapt_summary(ad)
+            del ad
+        else:
+            psis = map_psis_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s)
+            mark("psis")
+            waic = map_waic_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s)
+            mark("waic")
         route = auto_route_device(res, psis, waic, stream=s)
         mark("route")
         idx = torch.nonzero(route & _lib.ROUTE_SAMPLE).reshape(-1)  # (the host synchronisation: its size)
@@ -395,7 +455,7 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
 
 
 def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: int = 256, device="cuda",
-                    dest: FitBatch | None = None, budget_bytes: int | None = None):
+                    dest: FitBatch | None = None, budget_bytes: int | None = None, psis_adapt: int = 0):
     """fit_auto_device over host counts (uint32 y, N [T, LD], mm [T, 30, 12] or
     None) chunk by chunk: the chunks of plan_chunks under the device budget
     (MDFIT_CHUNK_TAXA caps them), each with its global index_base, so any split
@@ -403,7 +463,9 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
     status, auto f32 [T, NAUTO]): the rows are written in place and dest is
     returned; None: host arrays (out[T, 25] f64, pred, status, auto) are.  The
     chunks run one after another -- a chunk's two passes are separated by a host
-    synchronisation -- with no transfer overlap."""
+    synchronisation -- with no transfer overlap.  psis_adapt > 0: passed to
+    fit_auto_device; dest.adapt (f32 [T, NADAPTOUT]) is written too, or a fifth
+    host array returned."""
     torch = _torch()
     T = int(y.shape[0])
     dev = torch.device(device)
@@ -416,6 +478,7 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
         h_pred = np.empty((T, _lib.NPRED, _lib.NPOS), np.float32)
         h_status = np.empty((T,), np.int32)
         h_auto = np.empty((T, _lib.NAUTO), np.float32)
+        h_adapt = np.empty((T, _lib.NADAPTOUT), np.float32)
     for lo, hi in chunks:
         ty, tN, tm = to_device_counts(y[lo:hi], N[lo:hi], mm[lo:hi] if mm is not None else None, device=dev)
         o = _lib.MdfitOpts.from_buffer_copy(o_map)
@@ -423,16 +486,23 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
         res = None
         if dest is not None:
             res = FitBatch(dest.out[lo:hi], dest.pred[lo:hi] if dest.pred is not None else None, dest.status[lo:hi])
-        res, _route, auto = fit_auto_device(ty, tN, tm, o, psis_draws, res=res, budget_bytes=budget_bytes)
+        res, _route, auto = fit_auto_device(ty, tN, tm, o, psis_draws, res=res, budget_bytes=budget_bytes,
+                                            psis_adapt=psis_adapt)
         if dest is not None:
             dest.auto[lo:hi].copy_(auto)
+            if int(psis_adapt) > 0:
+                dest.adapt[lo:hi].copy_(res.adapt)
         else:
+            if int(psis_adapt) > 0:
+                h_adapt[lo:hi] = res.adapt.cpu().numpy()
             h_out[lo:hi] = res.out[:, :H_OUT_COLS].cpu().numpy()
             h_pred[lo:hi] = res.pred.cpu().numpy()
             h_status[lo:hi] = res.status.cpu().numpy()
             h_auto[lo:hi] = auto.cpu().numpy()
     if dest is not None:
         return dest
+    if int(psis_adapt) > 0:
+        return h_out, h_pred, h_status, h_auto, h_adapt
     return h_out, h_pred, h_status, h_auto
 
 
@@ -512,6 +582,30 @@ def psis_weights(lw, device="cuda"):
                                       ctypes.c_void_p(khat.data_ptr()), _stream_handle(torch, None)))
     torch.cuda.current_stream().synchronize()
     return w.cpu().numpy(), khat.cpu().numpy()
+
+
+def adapt_proposal(u, w, mask, c_held, K, device="cuda"):
+    """The refit of one round of MDFIT-ADAPT v1 by the device's function
+    (mdfit_adapt_proposal; a test helper): draws u[n, S, 4], normalised weights
+    w[n, S], free mask[n], c_held[n], shift K[n, 4] -> (m[n, 4], d[n, 4], F[n, 4,
+    4], gc[n], ok[n]); NaN where ok is 0."""
+    torch = _torch()
+    lib = _lib.load()
+    tu = torch.as_tensor(np.ascontiguousarray(u, dtype=np.float64), device=device)
+    tw = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64), device=device)
+    n, S = int(tw.shape[0]), int(tw.shape[1])
+    tm = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.int32), device=device)
+    tc = torch.as_tensor(np.ascontiguousarray(c_held, dtype=np.int32), device=device)
+    tK = torch.as_tensor(np.ascontiguousarray(K, dtype=np.float64), device=device)
+    prop = torch.empty((n, 25), dtype=torch.float64, device=device)
+    ok = torch.empty(n, dtype=torch.int32, device=device)
+    _lib.check(lib.mdfit_adapt_proposal(ctypes.c_void_p(tu.data_ptr()), ctypes.c_void_p(tw.data_ptr()),
+                                        ctypes.c_void_p(tm.data_ptr()), ctypes.c_void_p(tc.data_ptr()),
+                                        ctypes.c_void_p(tK.data_ptr()), n, S, ctypes.c_void_p(prop.data_ptr()),
+                                        ctypes.c_void_p(ok.data_ptr()), _stream_handle(torch)))
+    torch.cuda.synchronize()
+    p = prop.cpu().numpy()
+    return p[:, 0:4], p[:, 4:8], p[:, 8:24].reshape(n, 4, 4), p[:, 24], ok.cpu().numpy()
 
 
 def nuts_diag_device(res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, diag=None, stream=None):
@@ -784,6 +878,17 @@ def _check_ppred_mode(with_ppred: bool, opts: _lib.MdfitOpts | None, with_laplac
                          "mutually exclusive: one extra block per run")
 
 
+def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
+    """psis_adapt (MDFIT-ADAPT v1's round cap) is 0 .. ADAPT_MAX_ROUNDS and, when
+    not 0, goes with an importance-sampled block (with_psis, with_waic) or auto."""
+    R = int(psis_adapt)
+    if not 0 <= R <= _lib.ADAPT_MAX_ROUNDS:
+        raise ValueError(f"psis_adapt must be in [0, {_lib.ADAPT_MAX_ROUNDS}]")
+    if R > 0 and not importance_sampled:
+        raise ValueError("psis_adapt needs with_psis, with_waic or the auto inference")
+    return R
+
+
 def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
     """with_diag is the sampling mode's (opts None: the default options, MAP)."""
     if with_diag and (opts is None or int(opts.mode) != _lib.MODE_NUTS):
@@ -907,7 +1012,7 @@ class _Set:
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
                  with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
                  with_loo: bool = False, with_psis: bool = False, with_waic: bool = False,
-                 with_ppred: bool = False):
+                 with_ppred: bool = False, with_adapt: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -947,6 +1052,11 @@ class _Set:
             self.waic64 = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.waic = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32, device=device)
+        self.adapt64 = self.adapt = None
+        if with_adapt:  # as the adapt entries write it, and reduced to f32 [C, 2] for the way out
+            self.adapt64 = torch.empty((C, 3, _lib.NMAPADAPT), dtype=torch.float64, device=device)
+            if not dest_on_device:
+                self.adapt = torch.empty((C, _lib.NADAPTOUT), dtype=torch.float32, device=device)
         self.ppred32 = self.prec64 = self.ppred = None
         if with_ppred:  # as mdfit_map_pred writes them, and one f32 block for the way out
             self.ppred32 = torch.empty((C, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=device)
@@ -1021,13 +1131,20 @@ class ChunkedFitter:
     importance draws per sub-fit, pred_draws predictive draws per job,
     opts.seed, the chunk's global taxon index); its predictions and its record,
     rounded to f32 there, leave as one f32 block [T, 106] = ppred [3][30] |
-    rec [16], 424 B per taxon (run's fourth array; dest.ppred; split_ppred)."""
+    rec [16], 424 B per taxon (run's fourth array; dest.ppred; split_ppred).
+
+    psis_adapt = R > 0 (with_psis or with_waic): the chunk's launch is
+    mdfit_map_psis_adapt / mdfit_map_waic_adapt with at most R moment-matched
+    proposal rounds per PMD row (MDFIT-ADAPT v1), and one more f32 block [T, 2] =
+    (largest round-0 khat over the PMD rows, largest best round), reduced on the
+    device (adapt_summary), leaves beside the psis or waic block (run's fifth
+    array; dest.adapt)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False,
                  with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
                  with_psis: bool = False, psis_draws: int = PSIS_DRAWS, with_waic: bool = False,
-                 with_ppred: bool = False, pred_draws: int = PRED_DRAWS):
+                 with_ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0):
         _check_diag_mode(with_diag, opts)
         _check_summary_mode(with_summary, opts, with_laplace, with_diag)
         _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
@@ -1044,6 +1161,7 @@ class ChunkedFitter:
         self.with_psis = bool(with_psis)
         self.with_waic = bool(with_waic)
         self.with_ppred = bool(with_ppred)
+        self.psis_adapt = _check_psis_adapt(psis_adapt, with_psis or with_waic)
         self.pred_draws = int(pred_draws)
         self.psis_draws = int(psis_draws)
         self.chunk_cap = int(chunk_cap)
@@ -1051,14 +1169,14 @@ class ChunkedFitter:
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.with_laplace,
                           self.with_diag, self.with_summary, self.with_loo, self.with_psis, self.with_waic,
-                          self.with_ppred)
+                          self.with_ppred, self.psis_adapt > 0)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = self.h_lap = None
-        self.h_diag = self.h_summ = self.h_loo = self.h_psis = self.h_waic = self.h_ppred = None
+        self.h_diag = self.h_summ = self.h_loo = self.h_psis = self.h_waic = self.h_ppred = self.h_adapt = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -1088,6 +1206,8 @@ class ChunkedFitter:
                 self.h_waic = torch.empty((cap, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32).pin_memory()
             if self.with_ppred:
                 self.h_ppred = torch.empty((cap, PPRED_WORDS), dtype=torch.float32).pin_memory()
+            if self.psis_adapt > 0:
+                self.h_adapt = torch.empty((cap, _lib.NADAPTOUT), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -1135,6 +1255,8 @@ class ChunkedFitter:
         _check_ppred_mode(self.with_ppred, o0)
         if self.with_ppred and dest is not None and dest.ppred is None:
             raise ValueError("with_ppred: dest.ppred (float32 [T, PPRED_WORDS]) required")
+        if self.psis_adapt > 0 and dest is not None and dest.adapt is None:
+            raise ValueError("psis_adapt: dest.adapt (float32 [T, NADAPTOUT]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -1205,20 +1327,27 @@ class ChunkedFitter:
                 loo32 = dest.loo[lo:hi] if dest is not None else st.loo[:n]
                 with torch.cuda.stream(comp):
                     loo32.copy_(st.loo64[:n])
-            psis32 = None
+            psis32 = adapt32 = None
+            ad_kw = {}
+            if self.psis_adapt > 0:
+                ad_kw = {"adapt_rounds": self.psis_adapt, "adapt": st.adapt64[:n]}
             if self.with_psis:  # the records are final: their posteriors, rounded to f32 in place
                 map_psis_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
-                                psis=st.psis64[:n], stream=comp)
+                                psis=st.psis64[:n], stream=comp, **ad_kw)
                 psis32 = dest.psis[lo:hi] if dest is not None else st.psis[:n]
                 with torch.cuda.stream(comp):
                     psis32.copy_(st.psis64[:n])
             waic32 = None
             if self.with_waic:  # the records are final: their WAIC comparisons, rounded to f32 in place
                 map_waic_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
-                                waic=st.waic64[:n], stream=comp)
+                                waic=st.waic64[:n], stream=comp, **ad_kw)
                 waic32 = dest.waic[lo:hi] if dest is not None else st.waic[:n]
                 with torch.cuda.stream(comp):
                     waic32.copy_(st.waic64[:n])
+            if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
+                adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
+                with torch.cuda.stream(comp):
+                    adapt_summary(st.adapt64[:n], out=adapt32)
             ppred32 = None
             if self.with_ppred:  # the records are final: their posterior predictive, one f32 block for the way out
                 map_pred_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, self.pred_draws, int(o.seed),
@@ -1252,6 +1381,8 @@ class ChunkedFitter:
                         self.h_waic[lo:hi].copy_(waic32, non_blocking=True)
                     if ppred32 is not None:
                         self.h_ppred[lo:hi].copy_(ppred32, non_blocking=True)
+                    if adapt32 is not None:
+                        self.h_adapt[lo:hi].copy_(adapt32, non_blocking=True)
                 last_d2h = cp
         end = torch.cuda.Event()
         end.record(cp if last_d2h is not None else comp)
@@ -1285,6 +1416,10 @@ class ChunkedFitter:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_summ[:T].numpy()
         if self.with_loo:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_loo[:T].numpy()
+        if self.psis_adapt > 0:  # (a fifth array beside the psis or waic block)
+            block = self.h_psis if self.with_psis else self.h_waic
+            return (self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), block[:T].numpy(),
+                    self.h_adapt[:T].numpy())
         if self.with_psis:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_psis[:T].numpy()
         if self.with_waic:
@@ -1368,7 +1503,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
             dest_on_device: bool = False, budget_bytes: int | None = None,
             with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
             with_loo: bool = False, with_psis: bool = False, psis_draws: int = PSIS_DRAWS,
-            with_waic: bool = False, with_ppred: bool = False, pred_draws: int = PRED_DRAWS) -> ChunkedFitter:
+            with_waic: bool = False, with_ppred: bool = False, pred_draws: int = PRED_DRAWS,
+            psis_adapt: int = 0) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind and sampler length): the
     multi-file pipeline fits one file after another, and pinned + device
@@ -1388,6 +1524,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
            bool(with_laplace), bool(with_diag), bool(with_summary), bool(with_loo),
            int(psis_draws) if with_psis else 0, int(psis_draws) if with_waic else 0,
            (int(psis_draws), int(pred_draws)) if with_ppred else 0)
+    if int(psis_adapt) > 0:  # (the keys of the runs without it are unchanged)
+        key = key + (int(psis_adapt),)
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1410,7 +1548,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
                        with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
                        with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws, with_waic=with_waic,
-                       with_ppred=with_ppred, pred_draws=pred_draws)
+                       with_ppred=with_ppred, pred_draws=pred_draws, psis_adapt=psis_adapt)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1420,7 +1558,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, laplace: bool = False, diag: bool = False,
                    summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = PSIS_DRAWS,
-                   waic: bool = False, ppred: bool = False, pred_draws: int = PRED_DRAWS):
+                   waic: bool = False, ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
     the PMD sub-fits (_lib.LAPLACE_FIELDS), or, with diag (NUTS only), diag[T, 6,
@@ -1439,18 +1577,23 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
-    PinnedPack (copied to the device from there)."""
+    PinnedPack (copied to the device from there).  psis_adapt > 0 (with psis or
+    waic): the launch adapts its proposals (ChunkedFitter psis_adapt) and a fifth
+    array adapt[T, 2] f32 (_lib.ADAPTOUT_FIELDS) is returned."""
     T = int(y.shape[0])
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace, with_diag=diag,
                      with_summary=summary, with_loo=loo, with_psis=psis, psis_draws=psis_draws,
-                     with_waic=waic, with_ppred=ppred, pred_draws=pred_draws)
+                     with_waic=waic, with_ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt)
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
         extra = got[3].copy() if laplace or diag or summary or loo or psis or waic or ppred else None
+        adapt = got[4].copy() if int(psis_adapt) > 0 else None
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
+    if adapt is not None:
+        return out, pred, status, extra, adapt
     if laplace or diag or summary or loo or psis or waic or ppred:
         return out, pred, status, extra
     return out, pred, status

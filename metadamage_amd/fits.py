@@ -132,6 +132,9 @@ MAP_PRED_PREDICTION_COLUMNS = ["median_posterior", "hdpi_lower_posterior", "hdpi
 # record: the largest khat and the smallest ess of the six sub-fits)
 AUTO_UINT_COLUMNS = ["auto_route", "auto_sampled"]
 AUTO_COLUMNS = ["pareto_k_max", "psis_ess_min"]
+# psis_adapt > 0 ("map-psis", "map-waic", "auto"): the last two columns -- the largest round-0 Pareto-k over the PMD
+# rows (float32) and the largest best round of MDFIT-ADAPT v1 (uint32)
+ADAPT_COLUMNS = ["pareto_k_initial", "psis_adapt_rounds"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
                      "N_sum_total", "y_sum_forward", "y_sum_reverse", "y_sum_total"}
 
@@ -321,7 +324,8 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
                summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-               waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000):
+               waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
+               psis_adapt: int = 0):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -344,7 +348,10 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     transfer overlap.  ppred (MAP): mdfit_map_pred follows the fit with
     psis_draws importance draws per sub-fit and pred_draws predictive draws per
     job and the fourth array is the posterior predictive block [T, 106] f32 =
-    ppred [3][30] | rec [16] (engine.split_ppred).  At most one of the eight."""
+    ppred [3][30] | rec [16] (engine.split_ppred).  At most one of the eight.
+    psis_adapt > 0 (with psis, waic or auto): the importance sampling adapts its
+    proposals in at most that many rounds (MDFIT-ADAPT v1) and a fifth array
+    adapt[T, 2] f32 = (largest round-0 khat, largest best round) is returned."""
     import torch
 
     from . import engine
@@ -367,28 +374,30 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     # share of a multi-file pipeline that is host-bound
     if auto and (laplace or diag or summary or loo or psis or waic or ppred):
         raise ValueError("auto is the run's only extra block")
+    psis_adapt = engine._check_psis_adapt(psis_adapt, psis or waic or auto)
     if auto and not grouped:
         try:
-            return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev)
+            return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt)
         finally:
             p.release_pinned()
     if not grouped:
         try:
             return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
                                          summary=summary, loo=loo, psis=psis, psis_draws=psis_draws, waic=waic,
-                                         ppred=ppred, pred_draws=pred_draws)
+                                         ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
         return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic, auto,
-                            ppred, pred_draws)
+                            ppred, pred_draws, psis_adapt)
     finally:
         p.release_pinned()
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
                  summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-                 waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000):
+                 waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
+                 psis_adapt: int = 0):
     import torch
 
     from . import engine
@@ -400,11 +409,13 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
     rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                        with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred)
+                        with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred, with_adapt=psis_adapt > 0)
+    adapt = rec.adapt[: hi - lo] if psis_adapt > 0 else None
     if hi > lo and auto:  # each rank runs auto on its shard, its rows written in place into the gather buffers
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
                                device=dev, dest=engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo],
-                                                                rec.status[: hi - lo], auto=rec.auto[: hi - lo]))
+                                                                rec.status[: hi - lo], auto=rec.auto[: hi - lo],
+                                                                adapt=adapt), psis_adapt=psis_adapt)
         torch.cuda.synchronize(dev)
     elif hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
@@ -413,7 +424,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
                                 with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
                                 with_psis=psis, psis_draws=psis_draws, with_waic=waic, with_ppred=ppred,
-                                pred_draws=pred_draws)
+                                pred_draws=pred_draws, psis_adapt=psis_adapt)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                                                lap=rec.lap[: hi - lo] if laplace else None,
@@ -422,7 +433,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
                                                loo=rec.loo[: hi - lo] if loo else None,
                                                psis=rec.psis[: hi - lo] if psis else None,
                                                waic=rec.waic[: hi - lo] if waic else None,
-                                               ppred=rec.ppred[: hi - lo] if ppred else None))
+                                               ppred=rec.ppred[: hi - lo] if ppred else None, adapt=adapt))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -431,7 +442,8 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     if rank != 0:
         return None
     return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
-                           with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred)
+                           with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred,
+                           with_adapt=psis_adapt > 0)
 
 
 # --------------------------------------------------------------------------
@@ -488,7 +500,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
-                        psis=None, waic=None, auto=None, ppred=None) -> pd.DataFrame:
+                        psis=None, waic=None, auto=None, ppred=None, adapt=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -509,7 +521,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     of an "auto" run): auto_route and auto_sampled (uint32), then pareto_k_max
     and psis_ess_min (float32) follow.  ppred (the posterior predictive block
     [T, 106] of a "map-pred" run): the MAP_PRED_COLUMNS follow as float32, then
-    the MAP_PRED_UINT_COLUMNS."""
+    the MAP_PRED_UINT_COLUMNS.  adapt (the adapt block [T, 2] of a run with
+    psis_adapt > 0): pareto_k_initial (float32) and psis_adapt_rounds (uint32)
+    are the last two columns."""
     n = int(keep.sum())
     keep = None if n == len(keep) else keep  # (every taxon kept: no row selection)
     data = {
@@ -599,6 +613,11 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["map_pred_valid"] = ((flags & _lib.MAPPRED_VALID) != 0).astype(np.uint32)
         data["map_pred_reliable"] = ((flags & _lib.MAPPRED_RELIABLE) != 0).astype(np.uint32)
         columns += MAP_PRED_COLUMNS + MAP_PRED_UINT_COLUMNS
+    if adapt is not None:
+        kd = np.asarray(adapt) if keep is None else np.asarray(adapt)[keep]
+        data["pareto_k_initial"] = np.ascontiguousarray(kd[:, 0], dtype=np.float32)
+        data["psis_adapt_rounds"] = _uint32(np.nan_to_num(kd[:, 1]).astype(np.int64))
+        columns += ADAPT_COLUMNS
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
@@ -705,6 +724,11 @@ def wants_auto(cfg) -> bool:
     return getattr(cfg, "inference", "nuts") == "auto"
 
 
+def psis_adapt_of(cfg) -> int:
+    """The moment-matched proposal rounds of a "map-psis", "map-waic" or "auto" run (cfg.psis_adapt, default 0)."""
+    return int(getattr(cfg, "psis_adapt", 0) or 0)
+
+
 def psis_draws_of(cfg) -> int:
     """The draws per sub-fit of a "map-psis", "map-waic", "map-pred" or "auto" run (cfg.psis_draws, default 256)."""
     return int(getattr(cfg, "psis_draws", 256) or 256)
@@ -721,10 +745,11 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
                      summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
                      psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg), auto=wants_auto(cfg),
-                     ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg))
+                     ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg), psis_adapt=psis_adapt_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
+    adapt = rest[1] if psis_adapt_of(cfg) > 0 else None
     auto = rest[0] if rest and wants_auto(cfg) else None
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
@@ -737,7 +762,7 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
     return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic,
-                                auto=auto, ppred=ppred),
+                                auto=auto, ppred=ppred, adapt=adapt),
             make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred))
 
 
@@ -785,7 +810,7 @@ def _rank() -> int:
 
 
 CACHE_KEYS = ["min_alignments", "min_y_sum", "substitution_bases_forward", "substitution_bases_reverse",
-              "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws"]
+              "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws", "psis_adapt"]
 
 
 def _cache_hit(cfg) -> bool:
@@ -835,10 +860,12 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
                      laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
                      loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg),
-                     auto=wants_auto(cfg), ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg))
+                     auto=wants_auto(cfg), ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg),
+                     psis_adapt=psis_adapt_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
+    adapt = rest[1] if psis_adapt_of(cfg) > 0 else None
     auto = rest[0] if rest and wants_auto(cfg) else None
     lap = rest[0] if rest and wants_laplace(cfg) else None
     diag = rest[0] if rest and wants_diag(cfg) else None
@@ -855,7 +882,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
         from .counts import _save
 
         df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis,
-                                             waic=waic, auto=auto, ppred=ppred)
+                                             waic=waic, auto=auto, ppred=ppred, adapt=adapt)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())

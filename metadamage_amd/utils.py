@@ -68,6 +68,9 @@ class Config:
     psis_draws: int = 256
     # the predictive draws per job of "map-pred" (25..1024; the reference's 1000); in the metadata of such a run only
     pred_draws: int = 1000
+    # moment-matched proposal rounds of "map-psis", "map-waic" and "auto" (0..4; MDFIT-ADAPT v1); in the metadata and
+    # the cache key of a run with a non-zero value only
+    psis_adapt: int = 0
     N_cores: int = field(init=False)
 
     def __post_init__(self):
@@ -137,6 +140,8 @@ class Config:
             del d_out["psis_draws"]
         if self.inference != "map-pred":
             del d_out["pred_draws"]
+        if not self.psis_adapt:
+            del d_out["psis_adapt"]
         for key, val in d_out.items():
             if isinstance(val, Path):
                 d_out[key] = str(val)
