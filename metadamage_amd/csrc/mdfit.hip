@@ -533,35 +533,37 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
       // lg3(phi) from a pad: lane 15's point b (all-position: both halves;
       // pair: the reverse half), lane 7's point b (pair: the forward half);
       // for model_null also lg3(a), lg3(b) (point_accum: null_row)
+      // (lg3 with flog's tail kept, kPos off: the same bits, and this layout
+      // stays at 28 B of scratch; without the tail it needs 36)
       const bool src15 = whole || h == 1;
       auto pad3 = [&](const LG3& v) -> LG3 { return src15 ? rowb3<15>(v) : rowb3<7>(v); };
       const PointArgs gb = point_args(pb, th);
-      const LG3 t3b = lg3<true>(pb.N + th.phi);
+      const LG3 t3b = lg3<true, false, false>(pb.N + th.phi);
       const LG3 t6 = pad3(t3b);
-      const LG3 tb1 = lg3<true>(pb.y + gb.a);
-      const LG3 tb2 = lg3<true>(pb.N - pb.y + gb.b);
+      const LG3 tb1 = lg3<true, false, false>(pb.y + gb.a);
+      const LG3 tb2 = lg3<true, false, false>(pb.N - pb.y + gb.b);
       LG3 tb4, tb5;
       if (null_wave) {
         tb4 = pad3(tb1);
         tb5 = pad3(tb2);
       } else {
-        tb4 = lg3<true>(gb.a);
-        tb5 = lg3<true>(gb.b);
+        tb4 = lg3<true, false, false>(gb.a);
+        tb5 = lg3<true, false, false>(gb.b);
       }
       double accb[kNAcc];
 #pragma unroll
       for (int j = 0; j < kNAcc; ++j) accb[j] = 0.0;
       point_finish(pb, th, gb, tb1, tb2, t3b, tb4, tb5, t6, accb, accf);
       const PointArgs ga = point_args(pa, th);
-      const LG3 ta3 = lg3<true>(pa.N + th.phi);
-      const LG3 ta1 = lg3<true>(pa.y + ga.a);
-      const LG3 ta2 = lg3<true>(pa.N - pa.y + ga.b);
+      const LG3 ta3 = lg3<true, false, false>(pa.N + th.phi);
+      const LG3 ta1 = lg3<true, false, false>(pa.y + ga.a);
+      const LG3 ta2 = lg3<true, false, false>(pa.N - pa.y + ga.b);
       // (null: a, b are the half's; an all-position fit: point a is z = +k,
       // point b z = -k, the same a, b; a pair: the point's own)
       LG3 ta4 = tb4, ta5 = tb5;
       if (!null_wave && !whole_wave) {
-        ta4 = lg3<true>(ga.a);
-        ta5 = lg3<true>(ga.b);
+        ta4 = lg3<true, false, false>(ga.a);
+        ta5 = lg3<true, false, false>(ga.b);
       }
       point_finish(pa, th, ga, ta1, ta2, ta3, ta4, ta5, t6, acc, accf);
 #pragma unroll

@@ -242,7 +242,10 @@ __device__ __forceinline__ double point_finish(const PointData& pd, const Theta&
   mag += fabs(t3.l) + fabs(t6.l);
   double ell = (la + lb) - lS;  // exact 0 when N = 0
   if (accf) {
-    const double r1 = lrise(pd.y, a), r2 = lrise(pd.N - pd.y, b), r3 = lrise(pd.N, phi);
+    // lnGamma(a), lnGamma(b), lnGamma(phi) are t4.l, t5.l, t6.l (pad-lane and
+    // xrow variants included: bitwise lg3 of the same argument)
+    const double r1 = lrise_lg(pd.y, a, t4.l), r2 = lrise_lg(pd.N - pd.y, b, t5.l),
+                 r3 = lrise_lg(pd.N, phi, t6.l);
     ell = (r1 + r2) - r3;
     mag = (fabs(r1) + fabs(r2)) + fabs(r3);
   }

@@ -52,7 +52,12 @@ __device__ __forceinline__ double rcp1(double x) {
 // [sqrt(1/2), sqrt(2)), log(1+f) = f - hfsq + s (hfsq + R(s^2)), s = f/(2+f),
 // R a degree-7 minimax polynomial in s^2 -- Cody & Waite / the fdlibm scheme).
 // 0 -> -inf, +inf -> +inf, negative / NaN -> NaN.
-__device__ __forceinline__ double flog(double x) {
+//
+// flog_pos: the reduction and the polynomial alone, for an argument that is
+// finite and > 0 by construction (subnormals included) -- flog's bits there,
+// without its special-case tail (a branch region per inlined instance).  NOT
+// defined for 0, +inf, negative or NaN arguments.
+__device__ __forceinline__ double flog_pos(double x) {
 #pragma clang fp contract(off)  // (every fusion explicit: the same bits in every inlined instance)
   constexpr double kLn2Hi = 6.93147180369123816490e-01;  // high 32 bits of ln 2
   constexpr double kLn2Lo = 1.90821492927058770002e-10;  // ln 2 - kLn2Hi
@@ -73,7 +78,11 @@ __device__ __forceinline__ double flog(double x) {
                               3.999999999940941908e-01), t2);
   const double hfsq = 0.5 * f * f;
   const double de = (double)e;
-  const double r = fma(de, kLn2Hi, -((hfsq - fma(s, hfsq + R, de * kLn2Lo)) - f));
+  return fma(de, kLn2Hi, -((hfsq - fma(s, hfsq + R, de * kLn2Lo)) - f));
+}
+__device__ __forceinline__ double flog(double x) {
+#pragma clang fp contract(off)
+  const double r = flog_pos(x);
   const bool normal = x > 0.0 && x < INFINITY;
   return normal ? r : (x == 0.0 ? -INFINITY : (x == INFINITY ? x : NAN));
 }
@@ -215,16 +224,22 @@ struct LG3 {
 // potential and WAIC (MDFIT_TLOG_NUTS: C3 6.6 -> 6.1 s); the MAP fit, HPDI and
 // record kernels keep the accurate form (the table log in the fit kernel was
 // within +-1 % at C2 and 125k and spilled its PPL 2 layout: DESIGN.md §9).
-template <bool kTri = true, bool kTab = false>
+// kPos: x >= +0 (every caller's: counts plus a, b, phi > 0), so xs >= 10 and
+// the shift product is in [0, 3.4e11): the accurate form's logs by flog_pos,
+// without flog's special-case branch region; flog's bits.  Off only where the
+// leaner code costs a kernel registers (fit_kernel<2>: DESIGN.md §4 K1).
+template <bool kTri = true, bool kTab = false, bool kPos = true>
 __device__ __forceinline__ LG3 lg3(double x) {
 #pragma clang fp contract(off)  // (every fusion explicit: the same bits in every inlined instance)
   constexpr double kHalfLog2Pi = 0.91893853320467274178;  // 0.5 ln(2 pi)
-  double P = 1.0, dP = 0.0, d2P = 0.0;
+  // the recursion starts from its j = 0 step's result (P, P', P'') = (x, 1, 0):
+  // from (1, 0, 0) that step multiplies by one and adds zero (x >= +0)
+  double P = x, dP = 1.0, d2P = 0.0;
   double xs = x;
   const bool shift = x < 10.0;
   if (shift) {
 #pragma unroll
-    for (int j = 0; j < 10; ++j) {
+    for (int j = 1; j < 10; ++j) {
       const double t = x + (double)j;
       if (kTri) d2P = fma(d2P, t, 2.0 * dP);
       dP = fma(dP, t, P);
@@ -234,7 +249,8 @@ __device__ __forceinline__ LG3 lg3(double x) {
   }
   const double r = kTab ? rcp1(xs) : rcp(xs);
   const double r2 = r * r;
-  const double lx = kTab ? flog_t(xs) : flog(xs);
+  // xs >= 10 for every x >= 0: no special case to resolve (kPos)
+  const double lx = kTab ? flog_t(xs) : (kPos ? flog_pos(xs) : flog(xs));
   // lnGamma(xs) ~ (xs - 1/2) ln xs - xs + ln(2 pi)/2 + r (1/12 - r2 (1/360 - ...))
   double sl = fma(r2, -1.0 / 156.0, 691.0 / 360360.0);
   sl = fma(r2, -sl, 1.0 / 1188.0);
@@ -265,7 +281,8 @@ __device__ __forceinline__ LG3 lg3(double x) {
   if (shift) {
     const double iP = kTab ? rcp1(P) : rcp(P);
     const double s1 = dP * iP;          // sum 1/(x+j)
-    L -= kTab ? flog_t<true>(P) : flog(P);
+    // P in [0, 3.4e11), 0 only at x = 0: flog(P) by one select (kPos)
+    L -= kTab ? flog_t<true>(P) : (kPos ? (P == 0.0 ? -INFINITY : flog_pos(P)) : flog(P));
     Ps -= s1;
     if (kTri) Q += fma(s1, s1, -(d2P * iP));  // sum 1/(x+j)^2
   }
@@ -316,6 +333,15 @@ __device__ __forceinline__ double lgdiff(double z, double h) {
 __device__ __forceinline__ double lrise(double n, double s) {
   if (n == 0.0) return 0.0;
   return s <= n + 1.0 ? lgdiff(n + 1.0, s - 1.0) - lgam(s) : lgdiff(s, n) - lgam(n + 1.0);
+}
+// lrise(n, s) for a caller that already holds lgs = lnGamma(s) as lg3 returns
+// it (lg3's l is the same bits for either kTri): the branch s <= n + 1 -- every
+// point of a deep taxon, y and N far above a, b and phi -- subtracts lgs
+// instead of evaluating lgam(s) again; the other branch and n == 0 as lrise.
+__device__ __forceinline__ double lrise_lg(double n, double s, double lgs) {
+#pragma clang fp contract(off)
+  if (n == 0.0) return 0.0;
+  return s <= n + 1.0 ? lgdiff(n + 1.0, s - 1.0) - lgs : lgdiff(s, n) - lgam(n + 1.0);
 }
 
 // Full beta-binomial log-pmf (numpyro BetaBinomial.log_prob with log C(N,y),
