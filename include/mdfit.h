@@ -239,6 +239,40 @@ int mdfit_fit_batch_indexed(const uint32_t* y, const uint32_t* N, const uint32_t
 int mdfit_auto_route(const int32_t* status, const double* psis, const double* waic, int64_t n_taxa,
                      double* out, int32_t* route, void* hip_stream);
 
+/* Route bit of mdfit_auto_route_pred beside the four above; the taxon goes to
+ * the sampler iff route & MDFIT_ROUTE_SAMPLE_PRED is non-zero. */
+#define MDFIT_ROUTE_PRED 16        /* the pred record lacks flags bit 1, or counts a job made NaN by a draw that is no count */
+#define MDFIT_ROUTE_SAMPLE_PRED 23 /* MDFIT_ROUTE_SAMPLE | MDFIT_ROUTE_PRED */
+
+/*
+ * mdfit_auto_route with the importance-weighted posterior predictive
+ * (MDFIT-AUTO v1.1).  route[t] is mdfit_auto_route's, plus
+ * MDFIT_ROUTE_PRED when flags of prec[t] lacks bit 1 or its n_noncount field is
+ * not 0 (a NaN counts as not 0); a taxon with MDFIT_INVALID gets
+ * MDFIT_ROUTE_INVALID alone.
+ *   status, psis, waic : as mdfit_auto_route's
+ *   prec, ppred : the records double[n_taxa][MDFIT_NMAPPRED] and float[n_taxa]
+ *                [MDFIT_NPRED][30] of mdfit_map_pred_adapt (or mdfit_map_pred)
+ *                from the same num_draws, adapt_rounds, seed and index_base as
+ *                psis and waic (device; read only)
+ *   out        : for a taxon with route 0 the nine columns of mdfit_auto_route
+ *                and D_max, D_max_lower_hpdi, D_max_upper_hpdi, D_max_forward,
+ *                D_max_reverse <- prec fields 0..4, copied exactly; every other
+ *                field, and every field of a taxon with route != 0, is left as
+ *                the MAP call wrote it                               (device)
+ *   pred       : the MAP call's float[n_taxa][MDFIT_NPRED][30], or NULL; for a
+ *                taxon with route 0 its 90 floats <- ppred's         (device)
+ *   route      : int32_t[n_taxa]                                     (device)
+ * By the bit-for-bit identity of khat and the valid / reliable bits of the pred
+ * and psis records of one call, the flags half of MDFIT_ROUTE_PRED is never set
+ * without MDFIT_ROUTE_PSIS; the rule checks it regardless.  One launch on
+ * hip_stream, one thread per taxon; no workspace, no atomics, no host
+ * synchronisation.  n_taxa: at most 2^25 per call.
+ */
+int mdfit_auto_route_pred(const int32_t* status, const double* psis, const double* waic, const double* prec,
+                          const float* ppred, int64_t n_taxa, double* out, float* pred, int32_t* route,
+                          void* hip_stream);
+
 /*
  * Noise columns of records fitted with mm = NULL (both modes): the three
  * normalized_noise columns of out[n_taxa][MDFIT_NOUT] from the mismatch counts
@@ -680,6 +714,28 @@ int mdfit_adapt_proposal(const double* u, const double* w, const int32_t* mask, 
 int mdfit_map_pred(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
                    int64_t n_taxa, int32_t num_draws, int32_t num_pred, uint64_t seed, int64_t index_base,
                    float* ppred, double* rec, int32_t* index, uint32_t* counts, void* hip_stream);
+
+/*
+ * mdfit_map_pred with the moment-matched proposal rounds of
+ * mdfit_map_psis_adapt on each PMD row (MDFIT-AUTO v1.1): per
+ * row, khat, ess and the valid / reliable bits of rec are mdfit_map_psis_adapt's
+ * bit for bit for the same num_draws, adapt_rounds, seed and index_base, and so
+ * is adapt; the resampling, the regenerated theta and the predictive draws are
+ * those of the best round's proposal and weights.  flags of rec gains
+ * MDFIT_FLAG_ADAPTED (64) when some valid row's best round is > 0.  With
+ * adapt_rounds = 0, ppred, rec, index and counts are mdfit_map_pred's bit for
+ * bit and adapt reads (khat, ess, 0, 0).
+ *   adapt_rounds : R in [0, MDFIT_ADAPT_MAX_ROUNDS] (else MDFIT_E_ARG)
+ *   adapt      : double[n_taxa][3][MDFIT_NMAPADAPT], or NULL       (device)
+ * The other arguments, the launch and its guarantees are mdfit_map_pred's: one
+ * wave per taxon, no workspace, no atomics, no side stream, capturable in a
+ * graph; the records do not depend on the grid, the chunking or index_base's
+ * split.
+ */
+int mdfit_map_pred_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                         int64_t n_taxa, int32_t num_draws, int32_t num_pred, int32_t adapt_rounds,
+                         uint64_t seed, int64_t index_base, float* ppred, double* rec, double* adapt,
+                         int32_t* index, uint32_t* counts, void* hip_stream);
 
 /* Test helper: mdfit_map_pred's resampling of given weights w[n_series][S]
  * (>= 0, not all 0), one wave per series: idx[n_series][R] = s(r) and

@@ -112,6 +112,13 @@ ROUTE_WAIC, ROUTE_PSIS, ROUTE_STATUS, ROUTE_INVALID, ROUTE_SAMPLE = 1, 2, 4, 8, 
 # the nine result columns mdfit_auto_route composes for a taxon with route 0
 AUTO_COMPOSED_FIELDS = ["q_mean", "concentration_mean", "D_max_marginalized_mean", "q_mean_forward",
                         "q_mean_reverse", "n_sigma", "n_sigma_forward", "n_sigma_reverse", "asymmetry"]
+# mdfit_auto_route_pred: one more cause, and the sampled set's mask with it
+ROUTE_PRED, ROUTE_SAMPLE_PRED = 16, 23
+# the five predictive columns mdfit_auto_route_pred composes beside the nine above
+AUTO_PRED_COMPOSED_FIELDS = ["D_max", "D_max_lower_hpdi", "D_max_upper_hpdi", "D_max_forward", "D_max_reverse"]
+# the auto-pred block that leaves the device (engine.fit_auto_device auto_pred): float32 [T][NAUTOPRED]
+NAUTOPRED = 2
+AUTOPRED_FIELDS = ["pred_ess_min", "pred_distinct_min"]
 # the auto block that leaves the device (engine.fit_auto_device): float32 [T][NAUTO]
 NAUTO = 4
 AUTO_FIELDS = ["route", "sampled", "khat_max", "ess_min"]
@@ -130,6 +137,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_fit_batch",
     "mdfit_fit_batch_indexed",
     "mdfit_auto_route",
+    "mdfit_auto_route_pred",
     "mdfit_workspace_bytes",
     "mdfit_noise",
     "mdfit_map_laplace",
@@ -146,6 +154,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_waic_adapt",
     "mdfit_adapt_proposal",
     "mdfit_map_pred",
+    "mdfit_map_pred_adapt",
     "mdfit_resample",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
@@ -249,6 +258,12 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_adapt_proposal.restype = ctypes.c_int
     lib.mdfit_map_pred.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]
     lib.mdfit_map_pred.restype = ctypes.c_int
+    if hasattr(lib, "mdfit_map_pred_adapt"):  # (absent from the parent builds loaded by tools/ for A/B)
+        lib.mdfit_map_pred_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp,
+                                             vp, vp]
+        lib.mdfit_map_pred_adapt.restype = ctypes.c_int
+        lib.mdfit_auto_route_pred.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+        lib.mdfit_auto_route_pred.restype = ctypes.c_int
     lib.mdfit_resample.argtypes = [vp, i64, i32, i32, vp, vp, vp]
     lib.mdfit_resample.restype = ctypes.c_int
     lib.mdfit_psis_weights.argtypes = [vp, i64, i32, vp, vp, vp]

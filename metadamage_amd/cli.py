@@ -65,9 +65,12 @@ def cli_fit(
                                   "whose Pareto-k says it cannot be trusted"),
     psis_draws: int = typer.Option(256, help="map-psis, map-waic, map-pred, auto: importance draws per sub-fit, "
                                    "25 to 1024"),
-    pred_draws: int = typer.Option(1000, help="map-pred: predictive draws per position, 25 to 1024"),
+    pred_draws: int = typer.Option(1000, help="map-pred, auto with --auto-pred: predictive draws per position, 25 to 1024"),
     psis_adapt: int = typer.Option(0, help="map-psis, map-waic, auto: at most this many moment-matched proposal "
                                    "rounds for a sub-fit whose Pareto-k is over the threshold, 0 to 4"),
+    auto_pred: bool = typer.Option(False, "--auto-pred", help="auto: D_max, its 68 % interval and the fit_predictions "
+                                   "rows of a taxon that is not sampled from the importance-weighted posterior "
+                                   "predictive (--pred-draws draws per position)"),
 ):
     """Fitting Ancient Damage.
 
@@ -91,6 +94,7 @@ def cli_fit(
         "psis_draws": psis_draws,
         "pred_draws": pred_draws,
         "psis_adapt": psis_adapt,
+        "auto_pred": auto_pred,
     }
     if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "nuts-diag",
                          "nuts-summary", "nuts-loo", "auto"):
@@ -104,6 +108,8 @@ def cli_fit(
         raise typer.BadParameter("--psis-adapt must be in [0, 4]")
     if psis_adapt and inference not in ("map-psis", "map-waic", "auto"):
         raise typer.BadParameter("--psis-adapt goes with --inference map-psis, map-waic or auto")
+    if auto_pred and inference != "auto":
+        raise typer.BadParameter("--auto-pred goes with --inference auto")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

@@ -1586,6 +1586,19 @@ __global__ __launch_bounds__(256) void auto_route_kernel(const int32_t* __restri
   if (t < n_taxa) autoroute::route_one(t, status, psis, waic, out, route);
 }
 
+// MDFIT-AUTO v1.1 (mdfit_auto_route_pred): v1's rule with the pred record's
+// bit, and the 14 columns and 90 prediction floats of csrc/mdfit_auto.h
+__global__ __launch_bounds__(256) void auto_route_pred_kernel(const int32_t* __restrict__ status,
+                                                              const double* __restrict__ psis,
+                                                              const double* __restrict__ waic,
+                                                              const double* __restrict__ prec,
+                                                              const float* __restrict__ ppred, int64_t n_taxa,
+                                                              double* __restrict__ out, float* __restrict__ pred,
+                                                              int32_t* __restrict__ route) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n_taxa) autoroute::route_pred_one(t, status, psis, waic, prec, ppred, out, pred, route);
+}
+
 }  // namespace mdfit
 
 // ===========================================================================
@@ -2201,10 +2214,31 @@ int mdfit_map_pred(const uint32_t* y, const uint32_t* N, const double* out, cons
   const int S = (int)num_draws, R = (int)num_pred;
   const int tc = mq::tile_cols(S, R);
   mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mq::map_pred_kernel, dim3((unsigned)n_taxa), dim3(mdfit::kWave), mq::lds_bytes(S, R, tc),
+  hipLaunchKernelGGL(mq::map_pred_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave), mq::lds_bytes(S, R, tc),
                      (hipStream_t)hip_stream, y, N, out, status, n_taxa, S, R, tc, seed, index_base,
-                     mp::khat_threshold(S), ppred, rec, index, counts);
+                     mp::khat_threshold(S), ppred, rec, index, counts, 0, (double*)nullptr);
   return check_launch("map_pred_kernel");
+}
+
+int mdfit_map_pred_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                         int64_t n_taxa, int32_t num_draws, int32_t num_pred, int32_t adapt_rounds, uint64_t seed,
+                         int64_t index_base, float* ppred, double* rec, double* adapt, int32_t* index,
+                         uint32_t* counts, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace mq = mdfit::mappred;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (num_pred < mq::kMinPred || num_pred > mq::kMaxPred)
+    return set_err(MDFIT_E_ARG, "num_pred must be in [25, 1024]");
+  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
+    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !ppred || !rec) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  return mq::launch_adapt(y, N, out, status, n_taxa, (int)num_draws, (int)num_pred, (int)adapt_rounds, seed,
+                          index_base, ppred, rec, adapt, index, counts, (hipStream_t)hip_stream);
 }
 
 int mdfit_resample(const double* w, int64_t n_series, int32_t S, int32_t R, int32_t* idx, int32_t* n_distinct,
@@ -2233,6 +2267,19 @@ int mdfit_auto_route(const int32_t* status, const double* psis, const double* wa
   hipLaunchKernelGGL(mdfit::auto_route_kernel, dim3((unsigned)((n_taxa + 255) / 256)), dim3(256), 0,
                      (hipStream_t)hip_stream, status, psis, waic, n_taxa, out, route);
   return check_launch("auto_route_kernel");
+}
+
+int mdfit_auto_route_pred(const int32_t* status, const double* psis, const double* waic, const double* prec,
+                          const float* ppred, int64_t n_taxa, double* out, float* pred, int32_t* route,
+                          void* hip_stream) {
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (n_taxa == 0) return 0;
+  if (!status || !psis || !waic || !prec || !ppred || !out || !route)
+    return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  hipLaunchKernelGGL(mdfit::auto_route_pred_kernel, dim3((unsigned)((n_taxa + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, status, psis, waic, prec, ppred, n_taxa, out, pred, route);
+  return check_launch("auto_route_pred_kernel");
 }
 
 int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w, double* khat, void* hip_stream) {

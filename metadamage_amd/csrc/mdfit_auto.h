@@ -6,6 +6,9 @@
 // record -- and the composition copies nine fields; neither does any
 // arithmetic, so the device kernel (mdfit.hip: one thread per taxon) and a plain
 // C++ program (tests/auto_host_main.cpp, g++) give the same bits.
+// MDFIT-AUTO v1.1 (mdfit_auto_route_pred) below them: the rule
+// with the pred record's bit and the composition with the predictive columns
+// and prediction floats (tests/auto_pred_host_main.cpp).
 #pragma once
 
 #include <cstdint>
@@ -70,6 +73,50 @@ MDFIT_AUTO_FN void route_one(int64_t t, const int32_t* status, const double* psi
   const int r = route_of(status[t], p, w);
   route[t] = r;
   if (r == 0) compose(out + t * MDFIT_NOUT, p, w);
+}
+
+// ---- MDFIT-AUTO v1.1 (mdfit_auto_route_pred): the rule also
+// reads the flags and n_noncount of the taxon's mdfit_map_pred_adapt record, and
+// a settled taxon's five predictive columns and 90 prediction floats take the
+// importance-weighted posterior predictive.  Still no arithmetic.
+constexpr int kPredUnreliable = 16;  // the pred record lacks bit 1, or counts a job made NaN by a draw that is no count
+constexpr int kSamplePredMask = kSampleMask | kPredUnreliable;
+constexpr int kPredFlags = MDFIT_NMAPPRED - 1, kPredNNonCount = MDFIT_NMAPPRED - 2;
+constexpr int kNPredFloats = MDFIT_NPRED * 30;
+
+// route of one taxon: route_of and the pred record's bit (prec its [MDFIT_NMAPPRED])
+MDFIT_AUTO_FN int route_pred_of(int32_t status, const double* psis, const double* waic, const double* prec) {
+  if (status == MDFIT_INVALID) return kInvalid;
+  int r = route_of(status, psis, waic);
+  if ((flag_bits(prec[kPredFlags]) & 2u) == 0u || prec[kPredNNonCount] != 0.0) r |= kPredUnreliable;
+  return r;
+}
+
+// the record of a taxon with route 0: compose()'s nine columns, the five
+// predictive columns <- prec[0..4] and, with pred non-NULL, its 90 floats <- ppred's
+MDFIT_AUTO_FN void compose_pred(double* rec, float* pred, const double* psis, const double* waic, const double* prec,
+                                const float* ppred) {
+  compose(rec, psis, waic);
+  rec[MDFIT_F_D_MAX] = prec[0];
+  rec[MDFIT_F_D_MAX_LOWER_HPDI] = prec[1];
+  rec[MDFIT_F_D_MAX_UPPER_HPDI] = prec[2];
+  rec[MDFIT_F_D_MAX_FORWARD] = prec[3];
+  rec[MDFIT_F_D_MAX_REVERSE] = prec[4];
+  if (pred != nullptr)
+    for (int x = 0; x < kNPredFloats; ++x) pred[x] = ppred[x];
+}
+
+// one taxon of mdfit_auto_route_pred
+MDFIT_AUTO_FN void route_pred_one(int64_t t, const int32_t* status, const double* psis, const double* waic,
+                                  const double* prec, const float* ppred, double* out, float* pred, int32_t* route) {
+  const double* p = psis + t * (3 * MDFIT_NMAPPSIS);
+  const double* w = waic + t * (7 * MDFIT_NMAPWAIC);
+  const double* q = prec + t * MDFIT_NMAPPRED;
+  const int r = route_pred_of(status[t], p, w, q);
+  route[t] = r;
+  if (r == 0)
+    compose_pred(out + t * MDFIT_NOUT, pred != nullptr ? pred + t * kNPredFloats : nullptr, p, w, q,
+                 ppred + t * kNPredFloats);
 }
 
 }  // namespace mdfit::autoroute

@@ -1,5 +1,6 @@
 // mdfit_host.h — host-side helpers shared by the translation units of
-// libmdfit.so (mdfit.hip: C-ABI + MAP kernels, mdfit_nuts.hip: sampling mode).
+// libmdfit.so (mdfit.hip: C-ABI + MAP kernels, mdfit_nuts.hip: sampling mode,
+// mdfit_mappred_adapt.hip: the adapting predictive kernel).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,6 +64,14 @@ namespace mdfit::host {
 // (mdfit_poison_lds) -- called before each LDS-using kernel of a call
 void debug_poison(hipStream_t s);
 }  // namespace mdfit::host
+
+namespace mdfit::mappred {
+// mdfit_map_pred_adapt's launch (mdfit_mappred_adapt.hip: map_pred_kernel<true>
+// in a unit of its own flags); the arguments are checked by the caller
+int launch_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa, int S,
+                 int R, int adapt_rounds, uint64_t seed, int64_t index_base, float* ppred, double* rec, double* adapt,
+                 int32_t* index, uint32_t* counts, hipStream_t s);
+}  // namespace mdfit::mappred
 
 namespace mdfit::nuts {
 // sampling mode (mdfit_nuts.hip): workspace = 256 B of queue counters, then

@@ -165,6 +165,7 @@ namespace mdfit {
 // objective_group<kAll> does), row 2 the forward fit (diag sub-fit 2), row 3
 // the reverse fit (diag sub-fit 3); lane 15 of every row is the pad that holds
 // lg3(phi) (point_accum<true>).  60 of the 64 lanes hold a point.
+#ifndef MDFIT_NO_HELPER_KERNELS  // (a second unit of libmdfit.so includes this header for the templates alone)
 __global__ __launch_bounds__(64) void laplace_kernel(const uint32_t* __restrict__ gy,
                                                      const uint32_t* __restrict__ gN,
                                                      const double* __restrict__ out,
@@ -254,6 +255,7 @@ __global__ __launch_bounds__(64) void laplace_kernel(const uint32_t* __restrict_
     }
   }
 }
+#endif  // MDFIT_NO_HELPER_KERNELS
 
 }  // namespace mdfit
 #endif  // __HIPCC__

@@ -209,6 +209,7 @@ __device__ __forceinline__ bool next_proposal(const double* wt, int S, double* P
 }
 
 // mdfit_adapt_proposal: one wave per series
+#ifndef MDFIT_NO_HELPER_KERNELS  // (a second unit of libmdfit.so includes this header for the templates alone)
 __global__ __launch_bounds__(64) void adapt_proposal_kernel(const double* __restrict__ u, const double* __restrict__ wt,
                                                             const int32_t* __restrict__ mask,
                                                             const int32_t* __restrict__ cheld,
@@ -233,6 +234,7 @@ __global__ __launch_bounds__(64) void adapt_proposal_kernel(const double* __rest
     okp[row] = ok ? 1 : 0;
   }
 }
+#endif  // MDFIT_NO_HELPER_KERNELS
 
 }  // namespace mdfit::mapadapt
 #endif  // __HIPCC__

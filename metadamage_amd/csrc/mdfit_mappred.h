@@ -7,6 +7,9 @@
 // and draw r of each of the sampler's 32 predictive jobs is the oracle's
 // predictive_obs on theta of importance draw s(r), in the sampler's predictive
 // Philox domain.  Median and numpyro's hpdi(0.68) of count / N follow.
+// mdfit_map_pred_adapt (MDFIT-AUTO v1.1) is the same kernel
+// with mdfit_mapadapt.h's proposal rounds around the importance sampling of a
+// row (map_pred_kernel<true>, built in mdfit_mappred_adapt.hip).
 //
 // The resampling (resample), the u32 sort (sort_counts) and the median / HPDI
 // (median_hpdi_counts) are written once over a `lanes` policy, as
@@ -315,6 +318,16 @@ __device__ __forceinline__ int64_t predictive_count(Stream st, int r, int col, i
 // one column of rows 1 and 2, the counts into the tile behind the index;
 // phase 6 -- sort_counts and median_hpdi_counts per column.  Dynamic LDS:
 // lds_bytes(S, R, tc); static: 2,400 B.  Reads y, N, out and status only.
+//
+// kAdapt (mdfit_map_pred_adapt, MDFIT-AUTO v1.1): per row,
+// phases 2-3 run in map_psis_kernel<true>'s rounds, statement for statement, on
+// s_par[slot] (the by-slot layout map_waic_kernel<true> adapts in), so khat,
+// ess, the valid / reliable bits and the adapt record are mdfit_map_psis_adapt's
+// bits.  After the loop the best round's proposal is in s_par[slot] and its
+// weights are in the work buffer: phases 4-6 run unchanged and draw from the
+// best proposal.  The refit reads the weights s_w[0..S) and the proposal alone,
+// so no LDS is added.  adapt: [T][3][4], optional.
+template <bool kAdapt>
 __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict__ gy,
                                                       const uint32_t* __restrict__ gN,
                                                       const double* __restrict__ out,
@@ -322,7 +335,8 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
                                                       int R, int tc, uint64_t seed, int64_t index_base, double tau,
                                                       float* __restrict__ ppred, double* __restrict__ rec_out,
                                                       int32_t* __restrict__ index_tap,
-                                                      uint32_t* __restrict__ counts_tap) {
+                                                      uint32_t* __restrict__ counts_tap, int adapt_rounds,
+                                                      double* __restrict__ adapt) {
   extern __shared__ double s_w[];
   __shared__ double s_y[kLD], s_N[kLD];
   __shared__ double s_par[4][kNPar];   // by diagnostic slot: 0, 2, 3 (1, the null fit's, unused)
@@ -345,6 +359,8 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
     if (lane < MDFIT_NMAPPRED) rec[lane] = lane == kFlags ? 0.0 : NAN;
     if (pp != nullptr)
       for (int x = lane; x < MDFIT_NPRED * kNPos; x += 64) pp[x] = NAN;
+    if constexpr (kAdapt)
+      if (adapt != nullptr && lane < 12) adapt[t * 12 + lane] = NAN;
     return;
   }
   if (lane < kLD) {
@@ -362,6 +378,7 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
   int* s_idx = reinterpret_cast<int*>(s_w + S);
   uint32_t* s_c = reinterpret_cast<uint32_t*>(s_idx + R);
   double n_noncount = 0.0;
+  bool adapted = false;  // (kAdapt: some valid row's best round is > 0; wave-uniform)
 #pragma unroll 1
   for (int row = 0; row < 3; ++row) {
     const int slot = row == 0 ? 0 : row + 1;  // the chain's sub-fit index: 0, 2, 3
@@ -375,27 +392,68 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
       st.c0 = (uint32_t)gtaxon;
       st.c1 = (uint32_t)(gtaxon >> 32) + ((uint32_t)slot << 24);
       const int lo = row == 2 ? kNHalf : 0, hi = row == 1 ? kNHalf : kNPos;
-      // ---- phase 2: lanes over draws ----
-      for (int i = lane; i < S; i += 64) {
-        const DrawU r = mappsis::psis_draw(P, st, i);
-        const ThetaD th = mappsis::psis_theta(r);
-        double lw = -INFINITY;
-        if (th.feasible) {
-          const double ph = th.delta + 2.0;
-          double ll = 0.0;
-#pragma unroll 1
-          for (int col = lo; col < hi; ++col) {
-            const int kk = col < kNHalf ? col : col - kNHalf;
-            const double D = fma(th.A, powk(th.omq, kk), th.c);
-            ll += bb_logpmf(s_y[col], s_N[col], D, ph);
-          }
-          lw = (ll + th.lj) - r.lg;
-        }
-        s_w[i] = lw;
-      }
-      // ---- phase 3: the smoothed weights, their ess ----
+      // the rounds of MDFIT-ADAPT v1 (one pass without kAdapt): a round's proposal is written over the best one
+      // in s_par[slot], which lane j < 32 keeps word j of in `keep` and puts back when the round is dropped
       double n_inf;
-      ok = mappsis::psis_weights(w, s_w, S, khat, n_inf);
+      double k0 = NAN, ess0 = NAN, k_best = NAN, keep = 0.0;
+      int best = 0, tried = 0;
+      bool rerun = false;
+      for (int rnd = 0;;) {
+        // ---- phase 2: lanes over draws ----
+        for (int i = lane; i < S; i += 64) {
+          const DrawU r = mappsis::psis_draw(P, st, i);
+          const ThetaD th = mappsis::psis_theta(r);
+          double lw = -INFINITY;
+          if (th.feasible) {
+            const double ph = th.delta + 2.0;
+            double ll = 0.0;
+#pragma unroll 1
+            for (int col = lo; col < hi; ++col) {
+              const int kk = col < kNHalf ? col : col - kNHalf;
+              const double D = fma(th.A, powk(th.omq, kk), th.c);
+              ll += bb_logpmf(s_y[col], s_N[col], D, ph);
+            }
+            lw = (ll + th.lj) - r.lg;
+          }
+          s_w[i] = lw;
+        }
+        // ---- phase 3: the smoothed weights, their ess ----
+        ok = mappsis::psis_weights(w, s_w, S, khat, n_inf);
+        if constexpr (!kAdapt) {
+          break;
+        } else {
+          if (rerun) break;  // (the best round's weights are back in s_w, khat its own)
+          if (rnd == 0) {
+            if (!ok) break;
+            k0 = khat;
+            ess0 = mapadapt::weights_ess(w, s_w, S);
+          } else {
+            tried = rnd;
+            if (!(ok && isfinite(khat) && khat < k_best)) {  // 6. the round is dropped: the best one once more
+              if (lane < kNPar) s_par[slot][lane] = keep;
+              __syncthreads();
+              rerun = true;
+              continue;
+            }
+            best = rnd;
+          }
+          k_best = khat;
+          if (rnd == adapt_rounds || k_best <= tau) break;                // 1. the stop test
+          if (lane < kNPar) keep = s_par[slot][lane];
+          if (!mapadapt::next_proposal(s_w, S, s_par[slot], st)) break;  // 2-4. the refitted proposal, in place
+          ++rnd;
+        }
+      }
+      if constexpr (kAdapt) {
+        adapted = adapted || (ok && best > 0);
+        if (adapt != nullptr && lane == 0) {
+          double* ar = adapt + (t * 3 + row) * 4;
+          ar[mapadapt::kKhat0] = k0;
+          ar[mapadapt::kEss0] = ess0;
+          ar[mapadapt::kBestRound] = ok ? (double)best : NAN;
+          ar[mapadapt::kRoundsTried] = ok ? (double)tried : NAN;
+        }
+      }
       if (ok) {
         double s2 = 0.0;
         for (int i = lane; i < S; i += 64) {
@@ -455,6 +513,8 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
         }
       }
     }
+    if constexpr (kAdapt)
+      if (P[kPValid] == 0.0 && adapt != nullptr && lane < 4) adapt[(t * 3 + row) * 4 + lane] = NAN;
     if (lane == 0) {
       s_row[row][0] = khat;
       s_row[row][1] = ess;
@@ -485,10 +545,13 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
     }
     rec[kNNonCount] = n_noncount;
     rec[kFlags] = (double)(fl | (all_ok ? kValidBit : 0u) | (all_ok && all_rel ? kReliableBit : 0u));
+    if constexpr (kAdapt)
+      if (adapted) rec[kFlags] += (double)mapadapt::kAdaptedBit;
   }
 }
 
 // mdfit_resample: one wave per series w[row][0..S)
+#ifndef MDFIT_NO_HELPER_KERNELS  // (a second unit of libmdfit.so includes this header for the templates alone)
 __global__ __launch_bounds__(64) void resample_kernel(const double* __restrict__ wt, int64_t n_series, int S, int R,
                                                       int32_t* __restrict__ idx, int32_t* __restrict__ n_distinct) {
   extern __shared__ double s_w[];
@@ -500,6 +563,7 @@ __global__ __launch_bounds__(64) void resample_kernel(const double* __restrict__
   for (int x = threadIdx.x; x < R; x += 64) idx[row * (int64_t)R + x] = s_idx[x];
   if (threadIdx.x == 0) n_distinct[row] = (int32_t)nd;
 }
+#endif  // MDFIT_NO_HELPER_KERNELS
 
 }  // namespace mdfit::mappred
 #endif  // __HIPCC__

@@ -682,6 +682,7 @@ __global__ __launch_bounds__(64) void map_psis_kernel(const uint32_t* __restrict
 }
 
 // mdfit_psis_weights: one wave per series lw[row][0..S)
+#ifndef MDFIT_NO_HELPER_KERNELS  // (a second unit of libmdfit.so includes this header for the templates alone)
 __global__ __launch_bounds__(64) void psis_weights_kernel(const double* __restrict__ lw, int64_t n_series, int S,
                                                           double* __restrict__ wout, double* __restrict__ khat) {
   extern __shared__ double s_w[];
@@ -693,6 +694,7 @@ __global__ __launch_bounds__(64) void psis_weights_kernel(const double* __restri
   for (int x = threadIdx.x; x < S; x += 64) wout[row * (int64_t)S + x] = ok ? s_w[x] : NAN;
   if (threadIdx.x == 0) khat[row] = ok ? k : NAN;
 }
+#endif  // MDFIT_NO_HELPER_KERNELS
 
 }  // namespace mdfit::mappsis
 #endif  // __HIPCC__

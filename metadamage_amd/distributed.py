@@ -59,14 +59,25 @@ REC_AUTO = _lib.NAUTO * 4
 # with_ppred (a "map-pred" run; never together with any of them): the same for the
 # posterior predictive, one more f32 block [n, 106] = ppred [3][30] | rec [NMAPPRED], 424 B per taxon
 REC_PPRED = (_lib.NPRED * _lib.NPOS + _lib.NMAPPRED) * 4
-# psis_adapt > 0 (with the psis, waic or auto block): one more f32 block [n, 2] behind it, 8 B per taxon
+# psis_adapt > 0 (with the psis, waic or auto block: with_adapt; with the ppred block: with_ppred_adapt): one more f32
+# block [n, 2] behind it, 8 B per taxon
 REC_ADAPT = _lib.NADAPTOUT * 4
+# auto_pred (with the auto block): one more f32 block [n, NAUTOPRED] = pred_ess_min, pred_distinct_min behind the
+# auto block and before the adapt block, 8 B per taxon
+REC_AUTO_PRED = _lib.NAUTOPRED * 4
 
 
-def _check_adapt(with_adapt: bool, with_psis: bool, with_waic: bool, with_auto: bool) -> int:
+def _check_adapt(with_adapt: bool, with_psis: bool, with_waic: bool, with_auto: bool, with_ppred: bool = False,
+                 with_auto_pred: bool = False, with_ppred_adapt: bool = False) -> int:
+    """The bytes per taxon behind the run's extra block: the auto-pred block, then the adapt block (with_adapt
+    beside the psis, waic or auto block; with_ppred_adapt, its own switch, beside the ppred block)."""
     if with_adapt and not (with_psis or with_waic or with_auto):
         raise ValueError("with_adapt goes with with_psis, with_waic or with_auto")
-    return REC_ADAPT if with_adapt else 0
+    if with_ppred_adapt and not with_ppred:
+        raise ValueError("with_ppred_adapt goes with with_ppred")
+    if with_auto_pred and not with_auto:
+        raise ValueError("with_auto_pred goes with with_auto")
+    return (REC_AUTO_PRED if with_auto_pred else 0) + (REC_ADAPT if with_adapt or with_ppred_adapt else 0)
 
 
 def _extra(with_laplace: bool, with_diag: bool, with_summary: bool = False, with_loo: bool = False,
@@ -138,18 +149,21 @@ class Records:
     def __init__(self, n: int, device, with_laplace: bool = False, with_diag: bool = False,
                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
                  with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False,
-                 with_adapt: bool = False):
+                 with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False):
         import torch
 
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
         extra = _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto, with_ppred)
-        self.buf = torch.empty(n * (REC_BYTES + extra + _check_adapt(with_adapt, with_psis, with_waic, with_auto)),
-                               dtype=torch.uint8, device=device)
+        tail = _check_adapt(with_adapt, with_psis, with_waic, with_auto, with_ppred, with_auto_pred, with_ppred_adapt)
+        self.buf = torch.empty(n * (REC_BYTES + extra + tail), dtype=torch.uint8, device=device)
         self.lap = self.diag = self.summ = self.loo = self.psis = self.waic = self.auto = self.ppred = None
-        self.adapt = None
-        if with_adapt:  # (behind the run's extra block; the views below stop before it)
-            o5 = n * (REC_BYTES + extra)
+        self.adapt = self.auto_pred = None
+        o5 = n * (REC_BYTES + extra)  # (behind the run's extra block; the views below stop before it)
+        if with_auto_pred:
+            self.auto_pred = self.buf[o5 : o5 + n * REC_AUTO_PRED].view(dtype=torch.float32).view(n, _lib.NAUTOPRED)
+            o5 += n * REC_AUTO_PRED
+        if with_adapt or with_ppred_adapt:
             self.adapt = self.buf[o5 : o5 + n * REC_ADAPT].view(dtype=torch.float32).view(n, _lib.NADAPTOUT)
         if with_ppred:
             self.pred, self.status, self.ints, self.floats, self.ppred = packed_views(self.buf, n, with_ppred=True)
@@ -252,11 +266,13 @@ def _torch_dtype(name):
 def alloc_records(n: int, device, with_laplace: bool = False, with_diag: bool = False,
                   with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
                   with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False,
-                  with_adapt: bool = False) -> Records:
-    """with_adapt (psis_adapt > 0, beside with_psis, with_waic or with_auto): the
-    buffer is n * REC_ADAPT bytes longer, `adapt` f32[n, 2] behind the extra block."""
+                  with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False) -> Records:
+    """with_adapt (psis_adapt > 0, beside with_psis, with_waic or with_auto), or
+    with_ppred_adapt (the same beside with_ppred): the buffer is n * REC_ADAPT
+    bytes longer, `adapt` f32[n, 2] behind the extra block.  with_auto_pred (beside with_auto): n * REC_AUTO_PRED bytes
+    longer, `auto_pred` f32[n, 2] behind the auto block and before `adapt`."""
     return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto,
-                   with_ppred, with_adapt)
+                   with_ppred, with_adapt, with_auto_pred, with_ppred_adapt)
 
 
 def gather_records(buf, n_cap: int, rank: int, world: int, group=None, async_op: bool = False):
@@ -364,7 +380,7 @@ def run_distributed(fn, *args, **kwargs):
 def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, with_diag: bool = False,
                     with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
                     with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False,
-                    with_adapt: bool = False):
+                    with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  with_laplace: the
     parts carry the Laplace block and a fourth array lap[T, 3, 8] f32 is returned;
@@ -375,13 +391,17 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
     importance-weighted WAIC records, returned as waic[T, 7, 8] f32; with_auto:
     the auto block, returned as auto[T, 4] f32; with_ppred: the posterior
     predictive block, returned as ppred[T, 106] f32.  with_adapt (beside
-    with_psis, with_waic or with_auto): the parts carry the adapt block behind
-    it, returned last as adapt[T, 2] f32."""
+    with_psis, with_waic or with_auto; with_ppred_adapt beside with_ppred): the
+    parts carry the adapt block behind it, returned last as adapt[T, 2] f32.  with_auto_pred (beside
+    with_auto): the parts carry the auto-pred block behind the auto block,
+    returned behind auto[T, 4] as auto_pred[T, 2] f32."""
     import torch
 
-    outs, preds, sts, laps, adapts = [], [], [], [], []
+    outs, preds, sts, laps, adapts, apreds = [], [], [], [], [], []
     rec_extra = _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto, with_ppred)
-    rec_bytes = REC_BYTES + rec_extra + _check_adapt(with_adapt, with_psis, with_waic, with_auto)
+    rec_bytes = REC_BYTES + rec_extra + _check_adapt(with_adapt, with_psis, with_waic, with_auto, with_ppred,
+                                                     with_auto_pred, with_ppred_adapt)
+    with_adapt = with_adapt or with_ppred_adapt
     extra = with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic or with_auto or with_ppred
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
@@ -405,8 +425,12 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
                                                  with_ppred=with_ppred)
         if extra:
             laps.append(rest[0][: hi - lo].numpy())
+        o5 = n_cap * (REC_BYTES + rec_extra)
+        if with_auto_pred:
+            ap = part[o5 : o5 + n_cap * REC_AUTO_PRED].view(dtype=_torch_dtype("float32")).view(n_cap, _lib.NAUTOPRED)
+            apreds.append(ap[: hi - lo].numpy())
+            o5 += n_cap * REC_AUTO_PRED
         if with_adapt:
-            o5 = n_cap * (REC_BYTES + rec_extra)
             ad = part[o5 : o5 + n_cap * REC_ADAPT].view(dtype=_torch_dtype("float32")).view(n_cap, _lib.NADAPTOUT)
             adapts.append(ad[: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)
@@ -415,9 +439,10 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
         outs.append(o)
         preds.append(p[: hi - lo].numpy())
         sts.append(s[: hi - lo].numpy())
-    if with_adapt:
-        return (np.concatenate(outs), np.concatenate(preds), np.concatenate(sts), np.concatenate(laps),
-                np.concatenate(adapts))
+    if with_adapt or with_auto_pred:
+        return ((np.concatenate(outs), np.concatenate(preds), np.concatenate(sts), np.concatenate(laps))
+                + ((np.concatenate(apreds),) if with_auto_pred else ())
+                + ((np.concatenate(adapts),) if with_adapt else ()))
     if extra:
         return np.concatenate(outs), np.concatenate(preds), np.concatenate(sts), np.concatenate(laps)
     return np.concatenate(outs), np.concatenate(preds), np.concatenate(sts)

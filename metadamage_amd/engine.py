@@ -46,6 +46,7 @@ class FitBatch:
     ppred: "object" = None  # torch.float32 [T, PPRED_WORDS]: the posterior predictive block (with_ppred; split_ppred)
     auto: "object" = None  # torch.float32 [T, NAUTO]: route, sampled, khat_max, ess_min (fit_auto_chunks)
     adapt: "object" = None  # torch.float32 [T, NADAPTOUT]: largest round-0 khat, largest best round (psis_adapt > 0)
+    auto_pred: "object" = None  # torch.float32 [T, NAUTOPRED]: pred_ess_min, pred_distinct_min (auto with auto_pred)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -322,8 +323,41 @@ def auto_route_device(res: FitBatch, psis, waic, route=None, stream=None):
     return route
 
 
+def auto_route_pred_device(res: FitBatch, psis, waic, prec, ppred, route=None, stream=None):
+    """Launch mdfit_auto_route_pred (MDFIT-AUTO v1.1): auto_route_device with the
+    records of mdfit_map_pred_adapt -- prec float64 [T, NMAPPRED], ppred float32
+    [T, 3, 30] -- in the rule (_lib.ROUTE_PRED) and the composition: a taxon with
+    route 0 also gets its five predictive columns from prec and, where res.pred
+    is not None, its 90 prediction floats from ppred.  Returns route."""
+    torch = _torch()
+    lib = _lib.load()
+    T = int(res.out.shape[0])
+    if route is None:
+        route = torch.empty((T,), dtype=torch.int32, device=res.out.device)
+    for name, t, n, dt in (("psis", psis, T * 3 * _lib.NMAPPSIS, torch.float64),
+                           ("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC, torch.float64),
+                           ("prec", prec, T * _lib.NMAPPRED, torch.float64),
+                           ("ppred", ppred, T * _lib.NPRED * _lib.NPOS, torch.float32)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of {n} elements")
+    if not (route.is_cuda and route.is_contiguous() and route.dtype == torch.int32 and route.numel() == T):
+        raise ValueError("route must be a contiguous cuda int32 tensor of T entries")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and res.status.numel() == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    if res.pred is not None and not (res.pred.is_contiguous() and res.pred.dtype == torch.float32
+                                     and res.pred.numel() == T * _lib.NPRED * _lib.NPOS):
+        raise ValueError("res.pred must be a contiguous float32 tensor [T, 3, 30]")
+    _lib.check(lib.mdfit_auto_route_pred(
+        ctypes.c_void_p(res.status.data_ptr()), ctypes.c_void_p(psis.data_ptr()), ctypes.c_void_p(waic.data_ptr()),
+        ctypes.c_void_p(prec.data_ptr()), ctypes.c_void_p(ppred.data_ptr()), T, ctypes.c_void_p(res.out.data_ptr()),
+        ctypes.c_void_p(res.pred.data_ptr()) if res.pred is not None else None, ctypes.c_void_p(route.data_ptr()),
+        _stream_handle(torch, stream)))
+    return route
+
+
 AUTO_BYTES = _lib.NAUTO * 4  # one taxon's auto block on the way out: f32 (route, sampled, khat_max, ess_min)
 AUTO_STAGES = ("map", "psis", "waic", "route", "gather", "sampler", "scatter")
+AUTO_PRED_BYTES = _lib.NAUTOPRED * 4  # one taxon's auto-pred block on the way out: f32 (pred_ess_min, pred_distinct_min)
 
 
 def auto_opts(opts: _lib.MdfitOpts | None):
@@ -352,7 +386,8 @@ def adapt_summary(adapt, out=None):
 
 def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_draws: int = 256,
                     res: FitBatch | None = None, stream=None, budget_bytes: int | None = None,
-                    sub_chunk_taxa: int = 0, timings: dict | None = None, psis_adapt: int = 0):
+                    sub_chunk_taxa: int = 0, timings: dict | None = None, psis_adapt: int = 0,
+                    auto_pred: bool = False, pred_draws: int | None = None):
     """The auto inference of a device-resident batch (MDFIT-AUTO v1, DESIGN.md
     §3.10): the MAP fit, mdfit_map_psis and mdfit_map_waic with psis_draws draws
     per sub-fit, mdfit_auto_route -- which composes the record of every taxon
@@ -376,10 +411,23 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
     row (MDFIT-ADAPT v1; the routing rule is untouched) and res.adapt is the
     float32 [T, NADAPTOUT] block of adapt_summary.  timings (a
     dict): filled with the milliseconds of each of AUTO_STAGES, n_sampled and
-    n_sub_chunks (adds a synchronisation at the end)."""
+    n_sub_chunks (adds a synchronisation at the end).
+
+    auto_pred (MDFIT-AUTO v1.1): after the waic launch,
+    mdfit_map_pred_adapt on the whole batch with psis_draws, psis_adapt, the
+    call's seed and index_base and pred_draws predictive draws per job (default
+    PRED_DRAWS); mdfit_auto_route_pred in place of mdfit_auto_route, so a settled
+    taxon's five predictive columns and res.pred (which must exist) are the
+    importance-weighted posterior predictive, and idx = nonzero(route &
+    ROUTE_SAMPLE_PRED).  res.auto_pred is the float32 [T, NAUTOPRED] block
+    (pred_ess_min, pred_distinct_min over the three rows; NaN for a sampled
+    taxon), and timings gains "pred".  False: nothing of this is launched."""
     torch = _torch()
     T = int(ty.shape[0])
     dev = ty.device
+    auto_pred = bool(auto_pred)
+    n_pred = int(pred_draws) if pred_draws is not None else PRED_DRAWS
+    sample_mask = _lib.ROUTE_SAMPLE_PRED if auto_pred else _lib.ROUTE_SAMPLE
     o_map, o_nuts = auto_opts(opts)
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     marks = []
@@ -395,6 +443,8 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
             res = alloc_outputs(T, device=dev, opts=o_map)
         if res.workspace is None or res.workspace.numel() < workspace_bytes(T, o_map):
             res.workspace = alloc_workspace(T, dev, o_map)
+        if auto_pred and res.pred is None:
+            raise ValueError("auto_pred composes the prediction rows: res.pred must exist")
         mark("start")
         fit_batch_device(ty, tN, tm, o_map, res, stream=s)
         mark("map")
@@ -412,14 +462,26 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
             mark("psis")
             waic = map_waic_device(ty, tN, res, psis_draws, int(o_map.seed), int(o_map.index_base), stream=s)
             mark("waic")
-        route = auto_route_device(res, psis, waic, stream=s)
+        if auto_pred:
+            got = map_pred_device(ty, tN, res, psis_draws, n_pred, int(o_map.seed), int(o_map.index_base), stream=s,
+                                  adapt_rounds=int(psis_adapt))
+            ppred, prec = got[0], got[1]
+            mark("pred")
+            route = auto_route_pred_device(res, psis, waic, prec, ppred, stream=s)
+        else:
+            route = auto_route_device(res, psis, waic, stream=s)
         mark("route")
-        idx = torch.nonzero(route & _lib.ROUTE_SAMPLE).reshape(-1)  # (the host synchronisation: its size)
+        idx = torch.nonzero(route & sample_mask).reshape(-1)  # (the host synchronisation: its size)
         n = int(idx.numel())
         auto = torch.empty((T, _lib.NAUTO), dtype=torch.float32, device=dev)
         auto[:, 0] = route
-        auto[:, 1] = (route & _lib.ROUTE_SAMPLE) != 0
+        auto[:, 1] = (route & sample_mask) != 0
         auto[:, 2:4] = waic[:, 6, 4:6]
+        if auto_pred:
+            ap = torch.stack((prec[:, 8:11].amin(dim=1), prec[:, 11:14].amin(dim=1)), dim=1)
+            ap[(route & sample_mask) != 0] = float("nan")
+            res.auto_pred = ap.to(torch.float32)
+            del ppred, prec, got, ap
         del psis, waic
         chunks = []
         t_gather = t_sampler = t_scatter = 0.0
@@ -446,7 +508,7 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
                 mark("scatter")
         if timings is not None:
             s.synchronize()
-            for name in AUTO_STAGES:
+            for name in AUTO_STAGES + (("pred",) if auto_pred else ()):
                 timings[name] = 0.0
             for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
                 timings[name] += e0.elapsed_time(e1)
@@ -455,7 +517,8 @@ def fit_auto_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, psis_dr
 
 
 def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: int = 256, device="cuda",
-                    dest: FitBatch | None = None, budget_bytes: int | None = None, psis_adapt: int = 0):
+                    dest: FitBatch | None = None, budget_bytes: int | None = None, psis_adapt: int = 0,
+                    auto_pred: bool = False, pred_draws: int | None = None):
     """fit_auto_device over host counts (uint32 y, N [T, LD], mm [T, 30, 12] or
     None) chunk by chunk: the chunks of plan_chunks under the device budget
     (MDFIT_CHUNK_TAXA caps them), each with its global index_base, so any split
@@ -464,8 +527,10 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
     returned; None: host arrays (out[T, 25] f64, pred, status, auto) are.  The
     chunks run one after another -- a chunk's two passes are separated by a host
     synchronisation -- with no transfer overlap.  psis_adapt > 0: passed to
-    fit_auto_device; dest.adapt (f32 [T, NADAPTOUT]) is written too, or a fifth
-    host array returned."""
+    fit_auto_device; dest.adapt (f32 [T, NADAPTOUT]) is written too, or one more
+    host array returned, last.  auto_pred (with pred_draws): passed to
+    fit_auto_device; dest.auto_pred (f32 [T, NAUTOPRED]) is written too, or one
+    more host array returned behind auto and before adapt."""
     torch = _torch()
     T = int(y.shape[0])
     dev = torch.device(device)
@@ -479,6 +544,7 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
         h_status = np.empty((T,), np.int32)
         h_auto = np.empty((T, _lib.NAUTO), np.float32)
         h_adapt = np.empty((T, _lib.NADAPTOUT), np.float32)
+        h_auto_pred = np.empty((T, _lib.NAUTOPRED), np.float32)
     for lo, hi in chunks:
         ty, tN, tm = to_device_counts(y[lo:hi], N[lo:hi], mm[lo:hi] if mm is not None else None, device=dev)
         o = _lib.MdfitOpts.from_buffer_copy(o_map)
@@ -487,27 +553,35 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
         if dest is not None:
             res = FitBatch(dest.out[lo:hi], dest.pred[lo:hi] if dest.pred is not None else None, dest.status[lo:hi])
         res, _route, auto = fit_auto_device(ty, tN, tm, o, psis_draws, res=res, budget_bytes=budget_bytes,
-                                            psis_adapt=psis_adapt)
+                                            psis_adapt=psis_adapt, auto_pred=auto_pred, pred_draws=pred_draws)
         if dest is not None:
             dest.auto[lo:hi].copy_(auto)
+            if auto_pred:
+                dest.auto_pred[lo:hi].copy_(res.auto_pred)
             if int(psis_adapt) > 0:
                 dest.adapt[lo:hi].copy_(res.adapt)
         else:
             if int(psis_adapt) > 0:
                 h_adapt[lo:hi] = res.adapt.cpu().numpy()
+            if auto_pred:
+                h_auto_pred[lo:hi] = res.auto_pred.cpu().numpy()
             h_out[lo:hi] = res.out[:, :H_OUT_COLS].cpu().numpy()
             h_pred[lo:hi] = res.pred.cpu().numpy()
             h_status[lo:hi] = res.status.cpu().numpy()
             h_auto[lo:hi] = auto.cpu().numpy()
     if dest is not None:
         return dest
+    got = (h_out, h_pred, h_status, h_auto)
+    if auto_pred:
+        got += (h_auto_pred,)
     if int(psis_adapt) > 0:
-        return h_out, h_pred, h_status, h_auto, h_adapt
-    return h_out, h_pred, h_status, h_auto
+        got += (h_adapt,)
+    return got
 
 
 def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int = 1000, seed: int = 0,
-                    index_base: int = 0, ppred=None, rec=None, index=None, counts=None, stream=None):
+                    index_base: int = 0, ppred=None, rec=None, index=None, counts=None, stream=None,
+                    adapt_rounds: int = 0, adapt=None):
     """Launch mdfit_map_pred on the records of a finished MAP call (asynchronous
     on `stream`): the reference's posterior predictive from importance-weighted
     draws (MDFIT-PPRED v1): float32 ppred[T, 3, 30] in pred's layout and float64
@@ -516,10 +590,18 @@ def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int =
     int32 tensor [T, 3, num_pred], the importance draw each predictive draw
     took; counts: None, True or an int32 tensor [T, 32, num_pred] holding the
     unsorted counts of each job as uint32 (0xFFFFFFFF: no count or job not run).
-    Returns (ppred, rec[, index][, counts])."""
+    Returns (ppred, rec[, index][, counts]).
+
+    adapt_rounds > 0, or adapt given (True, or a float64 tensor [T, 3,
+    NMAPADAPT]): mdfit_map_pred_adapt (MDFIT-AUTO v1.1), each row with
+    mdfit_map_psis_adapt's rounds and the predictive drawn from the best round;
+    the adapt block is then the last element of the returned tuple."""
     torch = _torch()
     lib = _lib.load()
     T, S, R = int(ty.shape[0]), int(num_draws), int(num_pred)
+    use_adapt = int(adapt_rounds) != 0 or adapt is not None
+    if use_adapt and (adapt is None or adapt is True):
+        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
     if ppred is None:
         ppred = torch.empty((T, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=ty.device)
     if rec is None:
@@ -531,7 +613,8 @@ def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int =
     for name, t, n, dt in (("ppred", ppred, T * _lib.NPRED * _lib.NPOS, torch.float32),
                            ("rec", rec, T * _lib.NMAPPRED, torch.float64),
                            ("index", index, T * 3 * R, torch.int32),
-                           ("counts", counts, T * _lib.NPREDJOB * R, torch.int32)):
+                           ("counts", counts, T * _lib.NPREDJOB * R, torch.int32),
+                           ("adapt", adapt, T * 3 * _lib.NMAPADAPT, torch.float64)):
         if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
             raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of {n} elements")
     for name, a in (("y", ty), ("N", tN)):
@@ -539,6 +622,14 @@ def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int =
             raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
     if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
         raise ValueError("res must hold the contiguous records of these T taxa")
+    if use_adapt:
+        _lib.check(lib.mdfit_map_pred_adapt(
+            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
+            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(adapt_rounds), int(seed), int(index_base),
+            ctypes.c_void_p(ppred.data_ptr()), ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
+            ctypes.c_void_p(index.data_ptr()) if index is not None else None,
+            ctypes.c_void_p(counts.data_ptr()) if counts is not None else None, _stream_handle(torch, stream)))
+        return (ppred, rec) + tuple(x for x in (index, counts) if x is not None) + (adapt,)
     _lib.check(lib.mdfit_map_pred(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
                                   ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S, R,
                                   int(seed), int(index_base), ctypes.c_void_p(ppred.data_ptr()),
@@ -880,12 +971,13 @@ def _check_ppred_mode(with_ppred: bool, opts: _lib.MdfitOpts | None, with_laplac
 
 def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
     """psis_adapt (MDFIT-ADAPT v1's round cap) is 0 .. ADAPT_MAX_ROUNDS and, when
-    not 0, goes with an importance-sampled block (with_psis, with_waic) or auto."""
+    not 0, goes with an importance-sampled block (with_psis, with_waic,
+    with_ppred) or auto."""
     R = int(psis_adapt)
     if not 0 <= R <= _lib.ADAPT_MAX_ROUNDS:
         raise ValueError(f"psis_adapt must be in [0, {_lib.ADAPT_MAX_ROUNDS}]")
     if R > 0 and not importance_sampled:
-        raise ValueError("psis_adapt needs with_psis, with_waic or the auto inference")
+        raise ValueError("psis_adapt needs with_psis, with_waic, with_ppred or the auto inference")
     return R
 
 
@@ -1133,11 +1225,11 @@ class ChunkedFitter:
     rounded to f32 there, leave as one f32 block [T, 106] = ppred [3][30] |
     rec [16], 424 B per taxon (run's fourth array; dest.ppred; split_ppred).
 
-    psis_adapt = R > 0 (with_psis or with_waic): the chunk's launch is
-    mdfit_map_psis_adapt / mdfit_map_waic_adapt with at most R moment-matched
+    psis_adapt = R > 0 (with_psis, with_waic or with_ppred): the chunk's launch is
+    mdfit_map_psis_adapt / mdfit_map_waic_adapt / mdfit_map_pred_adapt with at most R moment-matched
     proposal rounds per PMD row (MDFIT-ADAPT v1), and one more f32 block [T, 2] =
     (largest round-0 khat over the PMD rows, largest best round), reduced on the
-    device (adapt_summary), leaves beside the psis or waic block (run's fifth
+    device (adapt_summary), leaves behind the psis, waic or ppred block (run's fifth
     array; dest.adapt)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
@@ -1161,7 +1253,7 @@ class ChunkedFitter:
         self.with_psis = bool(with_psis)
         self.with_waic = bool(with_waic)
         self.with_ppred = bool(with_ppred)
-        self.psis_adapt = _check_psis_adapt(psis_adapt, with_psis or with_waic)
+        self.psis_adapt = _check_psis_adapt(psis_adapt, with_psis or with_waic or with_ppred)
         self.pred_draws = int(pred_draws)
         self.psis_draws = int(psis_draws)
         self.chunk_cap = int(chunk_cap)
@@ -1344,19 +1436,19 @@ class ChunkedFitter:
                 waic32 = dest.waic[lo:hi] if dest is not None else st.waic[:n]
                 with torch.cuda.stream(comp):
                     waic32.copy_(st.waic64[:n])
-            if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
-                adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
-                with torch.cuda.stream(comp):
-                    adapt_summary(st.adapt64[:n], out=adapt32)
             ppred32 = None
             if self.with_ppred:  # the records are final: their posterior predictive, one f32 block for the way out
                 map_pred_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, self.pred_draws, int(o.seed),
-                                int(o.index_base), ppred=st.ppred32[:n], rec=st.prec64[:n], stream=comp)
+                                int(o.index_base), ppred=st.ppred32[:n], rec=st.prec64[:n], stream=comp, **ad_kw)
                 ppred32 = dest.ppred[lo:hi] if dest is not None else st.ppred[:n]
                 with torch.cuda.stream(comp):
                     pp_v, rec_v = split_ppred(ppred32)
                     pp_v.copy_(st.ppred32[:n])
                     rec_v.copy_(st.prec64[:n])
+            if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
+                adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
+                with torch.cuda.stream(comp):
+                    adapt_summary(st.adapt64[:n], out=adapt32)
             ev_done = torch.cuda.Event()
             ev_done.record(comp)
             done.append(ev_done)
@@ -1416,8 +1508,8 @@ class ChunkedFitter:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_summ[:T].numpy()
         if self.with_loo:
             return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_loo[:T].numpy()
-        if self.psis_adapt > 0:  # (a fifth array beside the psis or waic block)
-            block = self.h_psis if self.with_psis else self.h_waic
+        if self.psis_adapt > 0:  # (a fifth array beside the psis, waic or ppred block)
+            block = self.h_psis if self.with_psis else (self.h_waic if self.with_waic else self.h_ppred)
             return (self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), block[:T].numpy(),
                     self.h_adapt[:T].numpy())
         if self.with_psis:
@@ -1577,8 +1669,8 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
-    PinnedPack (copied to the device from there).  psis_adapt > 0 (with psis or
-    waic): the launch adapts its proposals (ChunkedFitter psis_adapt) and a fifth
+    PinnedPack (copied to the device from there).  psis_adapt > 0 (with psis,
+    waic or ppred): the launch adapts its proposals (ChunkedFitter psis_adapt) and a fifth
     array adapt[T, 2] f32 (_lib.ADAPTOUT_FIELDS) is returned."""
     T = int(y.shape[0])
     with _STAGING_LOCK:

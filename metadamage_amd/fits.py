@@ -132,7 +132,11 @@ MAP_PRED_PREDICTION_COLUMNS = ["median_posterior", "hdpi_lower_posterior", "hdpi
 # record: the largest khat and the smallest ess of the six sub-fits)
 AUTO_UINT_COLUMNS = ["auto_route", "auto_sampled"]
 AUTO_COLUMNS = ["pareto_k_max", "psis_ess_min"]
-# psis_adapt > 0 ("map-psis", "map-waic", "auto"): the last two columns -- the largest round-0 Pareto-k over the PMD
+# "auto" with auto_pred (MDFIT-AUTO v1.1): behind them pred_ess_min (float32) and pred_distinct_min
+# (uint32, 0 where the taxon is sampled), the least ess and distinct importance draws over the three PMD rows of the
+# predictive the settled taxon's D_max columns and prediction rows come from
+AUTO_PRED_COLUMNS = ["pred_ess_min", "pred_distinct_min"]
+# psis_adapt > 0 ("map-psis", "map-waic", "map-pred", "auto"): the last two columns -- the largest round-0 Pareto-k over the PMD
 # rows (float32) and the largest best round of MDFIT-ADAPT v1 (uint32)
 ADAPT_COLUMNS = ["pareto_k_initial", "psis_adapt_rounds"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
@@ -325,7 +329,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
                summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
                waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
-               psis_adapt: int = 0):
+               psis_adapt: int = 0, auto_pred: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -349,9 +353,13 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     psis_draws importance draws per sub-fit and pred_draws predictive draws per
     job and the fourth array is the posterior predictive block [T, 106] f32 =
     ppred [3][30] | rec [16] (engine.split_ppred).  At most one of the eight.
-    psis_adapt > 0 (with psis, waic or auto): the importance sampling adapts its
-    proposals in at most that many rounds (MDFIT-ADAPT v1) and a fifth array
-    adapt[T, 2] f32 = (largest round-0 khat, largest best round) is returned."""
+    psis_adapt > 0 (with psis, waic, ppred or auto): the importance sampling
+    adapts its proposals in at most that many rounds (MDFIT-ADAPT v1) and one
+    more array adapt[T, 2] f32 = (largest round-0 khat, largest best round) is
+    returned, last.  auto_pred (with auto; MDFIT-AUTO v1.1): a settled taxon's
+    predictive columns and prediction rows are the importance-weighted posterior
+    predictive from pred_draws draws per job, and auto_pred[T, 2] f32 =
+    (pred_ess_min, pred_distinct_min) is returned behind the auto block."""
     import torch
 
     from . import engine
@@ -374,10 +382,13 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     # share of a multi-file pipeline that is host-bound
     if auto and (laplace or diag or summary or loo or psis or waic or ppred):
         raise ValueError("auto is the run's only extra block")
-    psis_adapt = engine._check_psis_adapt(psis_adapt, psis or waic or auto)
+    psis_adapt = engine._check_psis_adapt(psis_adapt, psis or waic or auto or ppred)
+    if auto_pred and not auto:
+        raise ValueError("auto_pred goes with the auto inference")
     if auto and not grouped:
         try:
-            return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt)
+            return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt,
+                                          auto_pred=auto_pred, pred_draws=pred_draws)
         finally:
             p.release_pinned()
     if not grouped:
@@ -389,7 +400,7 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
         return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic, auto,
-                            ppred, pred_draws, psis_adapt)
+                            ppred, pred_draws, psis_adapt, auto_pred)
     finally:
         p.release_pinned()
 
@@ -397,7 +408,7 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
                  summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
                  waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
-                 psis_adapt: int = 0):
+                 psis_adapt: int = 0, auto_pred: bool = False):
     import torch
 
     from . import engine
@@ -409,13 +420,18 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
     rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                        with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred, with_adapt=psis_adapt > 0)
+                        with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred,
+                        with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
+                        with_auto_pred=auto_pred)
     adapt = rec.adapt[: hi - lo] if psis_adapt > 0 else None
     if hi > lo and auto:  # each rank runs auto on its shard, its rows written in place into the gather buffers
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
                                device=dev, dest=engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo],
                                                                 rec.status[: hi - lo], auto=rec.auto[: hi - lo],
-                                                                adapt=adapt), psis_adapt=psis_adapt)
+                                                                adapt=adapt,
+                                                                auto_pred=rec.auto_pred[: hi - lo] if auto_pred
+                                                                else None),
+                               psis_adapt=psis_adapt, auto_pred=auto_pred, pred_draws=pred_draws)
         torch.cuda.synchronize(dev)
     elif hi > lo:
         # the shard through the bounded-memory chunked dispatch, each chunk's
@@ -443,7 +459,8 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         return None
     return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
                            with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred,
-                           with_adapt=psis_adapt > 0)
+                           with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
+                           with_auto_pred=auto_pred)
 
 
 # --------------------------------------------------------------------------
@@ -500,7 +517,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
-                        psis=None, waic=None, auto=None, ppred=None, adapt=None) -> pd.DataFrame:
+                        psis=None, waic=None, auto=None, ppred=None, adapt=None, auto_pred=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -521,7 +538,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     of an "auto" run): auto_route and auto_sampled (uint32), then pareto_k_max
     and psis_ess_min (float32) follow.  ppred (the posterior predictive block
     [T, 106] of a "map-pred" run): the MAP_PRED_COLUMNS follow as float32, then
-    the MAP_PRED_UINT_COLUMNS.  adapt (the adapt block [T, 2] of a run with
+    the MAP_PRED_UINT_COLUMNS.  auto_pred (the auto-pred block [T, 2] of an
+    "auto" run with auto_pred): pred_ess_min (float32) and pred_distinct_min
+    (uint32) follow the auto columns.  adapt (the adapt block [T, 2] of a run with
     psis_adapt > 0): pareto_k_initial (float32) and psis_adapt_rounds (uint32)
     are the last two columns."""
     n = int(keep.sum())
@@ -597,6 +616,11 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["pareto_k_max"] = np.ascontiguousarray(ka[:, 2], dtype=np.float32)
         data["psis_ess_min"] = np.ascontiguousarray(ka[:, 3], dtype=np.float32)
         columns += AUTO_UINT_COLUMNS + AUTO_COLUMNS
+    if auto_pred is not None:
+        kq = np.asarray(auto_pred) if keep is None else np.asarray(auto_pred)[keep]
+        data["pred_ess_min"] = np.ascontiguousarray(kq[:, 0], dtype=np.float32)
+        data["pred_distinct_min"] = _uint32(np.nan_to_num(kq[:, 1]).astype(np.int64))
+        columns += AUTO_PRED_COLUMNS
     if ppred is not None:
         kr = np.asarray(ppred)[:, _lib.NPRED * _lib.NPOS:]
         kr = kr if keep is None else kr[keep]
@@ -725,8 +749,27 @@ def wants_auto(cfg) -> bool:
 
 
 def psis_adapt_of(cfg) -> int:
-    """The moment-matched proposal rounds of a "map-psis", "map-waic" or "auto" run (cfg.psis_adapt, default 0)."""
+    """The moment-matched proposal rounds of a "map-psis", "map-waic", "map-pred" or "auto" run (cfg.psis_adapt,
+    default 0)."""
     return int(getattr(cfg, "psis_adapt", 0) or 0)
+
+
+def auto_pred_of(cfg) -> bool:
+    """cfg.auto_pred (default False): an "auto" run composes the importance-weighted posterior predictive
+    (MDFIT-AUTO v1.1); with any other inference a ValueError naming the option."""
+    on = bool(getattr(cfg, "auto_pred", False))
+    if on and not wants_auto(cfg):
+        raise ValueError("auto_pred goes with inference 'auto'")
+    return on
+
+
+def _split_rest(cfg, rest):
+    """The optional arrays behind (out, pred, status) of fit_packed: (the run's extra block or None, auto_pred or
+    None, adapt or None) -- the auto-pred block follows the extra block, the adapt block is last."""
+    rest = list(rest)
+    adapt = rest.pop() if psis_adapt_of(cfg) > 0 else None
+    auto_pred = rest.pop() if auto_pred_of(cfg) else None
+    return (rest[0] if rest else None), auto_pred, adapt
 
 
 def psis_draws_of(cfg) -> int:
@@ -745,24 +788,25 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
                      summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
                      psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg), auto=wants_auto(cfg),
-                     ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg), psis_adapt=psis_adapt_of(cfg))
+                     ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg), psis_adapt=psis_adapt_of(cfg),
+                     auto_pred=auto_pred_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
-    adapt = rest[1] if psis_adapt_of(cfg) > 0 else None
-    auto = rest[0] if rest and wants_auto(cfg) else None
-    lap = rest[0] if rest and wants_laplace(cfg) else None
-    diag = rest[0] if rest and wants_diag(cfg) else None
-    summ = rest[0] if rest and wants_summary(cfg) else None
-    loo = rest[0] if rest and wants_loo(cfg) else None
-    psis = rest[0] if rest and wants_psis(cfg) else None
-    waic = rest[0] if rest and wants_waic(cfg) else None
-    ppred = rest[0] if rest and wants_pred(cfg) else None
+    extra, auto_pred, adapt = _split_rest(cfg, rest)
+    auto = extra if wants_auto(cfg) else None
+    lap = extra if wants_laplace(cfg) else None
+    diag = extra if wants_diag(cfg) else None
+    summ = extra if wants_summary(cfg) else None
+    loo = extra if wants_loo(cfg) else None
+    psis = extra if wants_psis(cfg) else None
+    waic = extra if wants_waic(cfg) else None
+    ppred = extra if wants_pred(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
     return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic,
-                                auto=auto, ppred=ppred, adapt=adapt),
+                                auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred),
             make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred))
 
 
@@ -810,7 +854,7 @@ def _rank() -> int:
 
 
 CACHE_KEYS = ["min_alignments", "min_y_sum", "substitution_bases_forward", "substitution_bases_reverse",
-              "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws", "psis_adapt"]
+              "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws", "psis_adapt", "auto_pred"]
 
 
 def _cache_hit(cfg) -> bool:
@@ -861,19 +905,19 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
                      laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
                      loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg),
                      auto=wants_auto(cfg), ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg),
-                     psis_adapt=psis_adapt_of(cfg))
+                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
-    adapt = rest[1] if psis_adapt_of(cfg) > 0 else None
-    auto = rest[0] if rest and wants_auto(cfg) else None
-    lap = rest[0] if rest and wants_laplace(cfg) else None
-    diag = rest[0] if rest and wants_diag(cfg) else None
-    summ = rest[0] if rest and wants_summary(cfg) else None
-    loo = rest[0] if rest and wants_loo(cfg) else None
-    psis = rest[0] if rest and wants_psis(cfg) else None
-    waic = rest[0] if rest and wants_waic(cfg) else None
-    ppred = rest[0] if rest and wants_pred(cfg) else None
+    extra, auto_pred, adapt = _split_rest(cfg, rest)
+    auto = extra if wants_auto(cfg) else None
+    lap = extra if wants_laplace(cfg) else None
+    diag = extra if wants_diag(cfg) else None
+    summ = extra if wants_summary(cfg) else None
+    loo = extra if wants_loo(cfg) else None
+    psis = extra if wants_psis(cfg) else None
+    waic = extra if wants_waic(cfg) else None
+    ppred = extra if wants_pred(cfg) else None
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
@@ -882,7 +926,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
         from .counts import _save
 
         df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis,
-                                             waic=waic, auto=auto, ppred=ppred, adapt=adapt)
+                                             waic=waic, auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())

@@ -68,9 +68,12 @@ class Config:
     psis_draws: int = 256
     # the predictive draws per job of "map-pred" (25..1024; the reference's 1000); in the metadata of such a run only
     pred_draws: int = 1000
-    # moment-matched proposal rounds of "map-psis", "map-waic" and "auto" (0..4; MDFIT-ADAPT v1); in the metadata and
+    # moment-matched proposal rounds of "map-psis", "map-waic", "map-pred" and "auto" (0..4; MDFIT-ADAPT v1); in the metadata and
     # the cache key of a run with a non-zero value only
     psis_adapt: int = 0
+    # "auto": a settled taxon's predictive columns and prediction rows from the importance-weighted posterior
+    # predictive (MDFIT-AUTO v1.1; pred_draws then applies); in the metadata and the cache key only when set
+    auto_pred: bool = False
     N_cores: int = field(init=False)
 
     def __post_init__(self):
@@ -138,10 +141,12 @@ class Config:
         d_out = asdict(self)
         if self.inference not in ("map-psis", "map-waic", "map-pred", "auto"):
             del d_out["psis_draws"]
-        if self.inference != "map-pred":
+        if self.inference != "map-pred" and not self.auto_pred:
             del d_out["pred_draws"]
         if not self.psis_adapt:
             del d_out["psis_adapt"]
+        if not self.auto_pred:
+            del d_out["auto_pred"]
         for key, val in d_out.items():
             if isinstance(val, Path):
                 d_out[key] = str(val)
