@@ -650,6 +650,95 @@ int mdfit_map_waic_adapt(const uint32_t* y, const uint32_t* N, const double* out
                          int64_t index_base, double* waic, double* adapt, double* pointwise, double* draws,
                          void* hip_stream);
 
+/* Importance-sampled evidence record: double evid[T][7][MDFIT_NMAPEVID].  Rows
+ * 0..5, one per sub-fit in diagnostic-slot order (PMD-all, null-all, PMD-fwd,
+ * PMD-rev, null-fwd, null-rev): log_evidence, se, khat, ess = 1 / sum w^2,
+ * n_infeasible, log_w_max = K_prior - K_prop + max lw, the best adapt round (0
+ * without rounds and in a null row), flags (an integer stored as double: bit 0
+ * the row is valid, bit 1 khat <= min(1 - 1 / log10 S, 0.7), bits 2..5
+ * coordinate (q, A, c, phi) free, bit 6 MDFIT_FLAG_ADAPTED).  Row 6, the
+ * comparisons: log_bf = lZ_0 - lZ_1, log_bf_forward = lZ_2 - lZ_4,
+ * log_bf_reverse = lZ_3 - lZ_5, log_bf_asymmetry = lZ_0 - (lZ_2 + lZ_3) (the
+ * sign of the reference's asymmetry: positive favours one decay for both
+ * strands), log_bf_se = sqrt(se_0^2 + se_1^2), khat_max and ess_min over the
+ * valid rows, flags (bit 0 all six rows valid, bit 1 all six valid and at or
+ * under the khat threshold). */
+#define MDFIT_NMAPEVID 8
+
+/*
+ * Importance-sampled marginal likelihood (evidence) of the six sub-fits of a
+ * finished MODE_MAP call and the Bayes factors PMD : null on it (MDFIT-EVID v1,
+ * DESIGN.md §3.14).  Per sub-fit the raw log-weights lw_t are mdfit_map_waic's
+ * exactly -- the same proposal, Philox stream (sub-fit index = row), target,
+ * feasibility rule and dropped constants -- and are smoothed as there.  With c
+ * the largest finite lw_t, tot the sum of the smoothed weights exp(lw_t - c)
+ * (an infeasible draw adds 0 and still counts in S) and w the normalised ones,
+ *   log_evidence = K_prior - K_prop + c + log(tot / S),
+ *   se           = sqrt(sum_t (w_t - 1/S)^2)   (= sqrt(1/ess - 1/S)),
+ * the delta-method standard error of the log of the mean weight.  K_prior, the
+ * constants left out of the log prior: PMD log 12 + log 12 + log 9 + log
+ * (1/1000) (Beta(2,3) on q and A, Beta(1,9) on c, Exponential(rate 1/1000) on
+ * delta), null log 12 + log(1/1000).  K_prop, those left out of the log
+ * proposal density, with d free Student-t coordinates (nu = 4): lgamma((4 + d)
+ * / 2) - lgamma(2) - (d / 2) log(4 pi) - sum over free j of [log scale_j + log
+ * factor_jj], the log determinant of the map from the unit-scale t to u, plus
+ * log rate of the exponential when c is held on 0; a refitted proposal brings
+ * its own constant.  The prior is not renormalised for the region A + c >= 1 (a
+ * draw there has weight 0): the evidence is that of the density the sampling
+ * mode draws from.  khat says whether the estimate can be trusted, with the
+ * threshold of flags bit 1: the estimate is a plain mean of the weights.  A
+ * comparison of row 6 is NaN when a row it needs is invalid; a row's validity
+ * is exactly mdfit_map_waic's; an invalid row has NaN statistics and only its
+ * free bits in flags; a taxon with status != MDFIT_OK NaN statistics and flags
+ * 0 in all seven rows.
+ *   y, N, out, status : those of the MODE_MAP call (device; read only)
+ *   num_draws  : S in [25, 1024] (else MDFIT_E_ARG, before any device call)
+ *   seed, index_base : the Philox streams are keyed by (seed, index_base +
+ *                taxon, sub-fit), as mdfit_map_psis's
+ *   evid       : double[n_taxa][7][MDFIT_NMAPEVID]                 (device)
+ *   draws      : double[n_taxa][6][num_draws][6], as mdfit_map_waic's, or NULL
+ * khat, ess, n_infeasible, the valid / reliable / free bits of rows 0..5 and
+ * draws are mdfit_map_waic's bit for bit for the same num_draws, seed and
+ * index_base (rows 0, 2, 3 therefore mdfit_map_psis's).
+ * One launch on hip_stream, one wave per taxon; no workspace, no allocation,
+ * no side stream, no host synchronisation, no atomics; capturable in a graph.
+ * The records do not depend on the grid, the chunking or index_base's split.
+ * n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_evidence(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                       int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base,
+                       double* evid, double* draws, void* hip_stream);
+
+/*
+ * mdfit_map_evidence with the rounds of mdfit_map_psis_adapt on its PMD rows
+ * (0, 2, 3): khat, ess, n_infeasible, the valid / reliable / free / adapted
+ * bits of rows 0..5, the adapt record and draws are mdfit_map_waic_adapt's bit
+ * for bit for the same num_draws, adapt_rounds, seed and index_base (rows 0,
+ * 2, 3 therefore mdfit_map_psis_adapt's); the evidence is that of the best
+ * round's weights with that round's K_prop, and field 6 holds the best round.
+ * The null rows (1, 4, 5) are not adapted.  With adapt_rounds = 0 evid and
+ * draws are mdfit_map_evidence's bit for bit.
+ *   adapt_rounds : R in [0, MDFIT_ADAPT_MAX_ROUNDS] (else MDFIT_E_ARG, before
+ *                any device call)
+ *   adapt      : double[n_taxa][3][MDFIT_NMAPADAPT] (rows PMD-all, PMD-forward,
+ *                PMD-reverse), or NULL                              (device)
+ * The other arguments, the launch and its guarantees are mdfit_map_evidence's.
+ */
+int mdfit_map_evidence_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                             int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed,
+                             int64_t index_base, double* evid, double* adapt, double* draws, void* hip_stream);
+
+/*
+ * Test helper: the log of the mean weight of mdfit_map_evidence (its device
+ * functions) on given log-weight series lw[n_series][S], one wave per series,
+ * as mdfit_psis_weights: logz[i] = c + log(tot / S), se[i] and khat[i]; NaN
+ * where the smoothing refuses the series (a NaN or +inf, or an infeasible
+ * cut-off draw).  S in [25, 1024] (else MDFIT_E_ARG); n_series at most 2^25.
+ * Device pointers.
+ */
+int mdfit_log_mean_weight(const double* lw, int64_t n_series, int32_t S, double* logz, double* se,
+                          double* khat, void* hip_stream);
+
 /*
  * Test helper: the refit of one round of mdfit_map_psis_adapt (its device
  * function) on given series, one wave per series: from draws u[n_series][S][4]

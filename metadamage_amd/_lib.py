@@ -107,6 +107,15 @@ MAPWAIC_COMPARE_FIELDS = ["n_sigma_waic", "n_sigma_waic_forward", "n_sigma_waic_
                           "ess_min", "reserved", "flags"]
 MAPWAIC_VALID, MAPWAIC_RELIABLE = 1, 2  # flags: bit 0 valid, bit 1 khat <= threshold; rows 0..5: bits 2..5 free
 
+# importance-sampled evidence record (mdfit_map_evidence): float64 [T][NEVIDROW][NMAPEVID], rows 0..5 in SUBFITS order ...
+NMAPEVID = 8
+NEVIDROW = 7
+MAPEVID_FIELDS = ["log_evidence", "se", "khat", "ess", "n_infeasible", "log_w_max", "best_round", "flags"]
+# ... and row 6, the comparisons
+MAPEVID_COMPARE_FIELDS = ["log_bf", "log_bf_forward", "log_bf_reverse", "log_bf_asymmetry", "log_bf_se", "khat_max",
+                          "ess_min", "flags"]
+MAPEVID_VALID, MAPEVID_RELIABLE = 1, 2  # flags: bit 0 valid, bit 1 khat <= threshold; rows 0..5: bits 2..5 free, bit 6 adapted
+
 # route bits of mdfit_auto_route (MDFIT_ROUTE_*): the taxon is sampled iff route & ROUTE_SAMPLE
 ROUTE_WAIC, ROUTE_PSIS, ROUTE_STATUS, ROUTE_INVALID, ROUTE_SAMPLE = 1, 2, 4, 8, 7
 # the nine result columns mdfit_auto_route composes for a taxon with route 0
@@ -152,6 +161,9 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_waic",
     "mdfit_map_psis_adapt",
     "mdfit_map_waic_adapt",
+    "mdfit_map_evidence",
+    "mdfit_map_evidence_adapt",
+    "mdfit_log_mean_weight",
     "mdfit_adapt_proposal",
     "mdfit_map_pred",
     "mdfit_map_pred_adapt",
@@ -254,6 +266,12 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.mdfit_map_psis_adapt.restype = ctypes.c_int
     lib.mdfit_map_waic_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]
     lib.mdfit_map_waic_adapt.restype = ctypes.c_int
+    lib.mdfit_map_evidence.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp]
+    lib.mdfit_map_evidence.restype = ctypes.c_int
+    lib.mdfit_map_evidence_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp]
+    lib.mdfit_map_evidence_adapt.restype = ctypes.c_int
+    lib.mdfit_log_mean_weight.argtypes = [vp, i64, i32, vp, vp, vp, vp]
+    lib.mdfit_log_mean_weight.restype = ctypes.c_int
     lib.mdfit_adapt_proposal.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
     lib.mdfit_adapt_proposal.restype = ctypes.c_int
     lib.mdfit_map_pred.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]

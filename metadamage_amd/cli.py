@@ -59,14 +59,16 @@ def cli_fit(
                                   "nuts-loo: NUTS with PSIS-LOO model comparison and Pareto-k diagnostics; "
                                   "map-psis: MAP fit with an importance-sampled posterior and its Pareto-k; "
                                   "map-waic: MAP fit with importance-weighted WAIC n_sigma and asymmetry; "
+                                  "map-evidence: MAP fit with the importance-sampled evidence of the damage and "
+                                  "null models, their Bayes factor and the probability of damage; "
                                   "map-pred: MAP fit with the importance-weighted posterior predictive D_max, its "
                                   "68 % interval and fit_predictions columns; "
                                   "auto: MAP fit with its importance-sampled correction, NUTS only for the taxa "
                                   "whose Pareto-k says it cannot be trusted"),
-    psis_draws: int = typer.Option(256, help="map-psis, map-waic, map-pred, auto: importance draws per sub-fit, "
+    psis_draws: int = typer.Option(256, help="map-psis, map-waic, map-evidence, map-pred, auto: importance draws per sub-fit, "
                                    "25 to 1024"),
     pred_draws: int = typer.Option(1000, help="map-pred, auto with --auto-pred: predictive draws per position, 25 to 1024"),
-    psis_adapt: int = typer.Option(0, help="map-psis, map-waic, auto: at most this many moment-matched proposal "
+    psis_adapt: int = typer.Option(0, help="map-psis, map-waic, map-evidence, auto: at most this many moment-matched proposal "
                                    "rounds for a sub-fit whose Pareto-k is over the threshold, 0 to 4"),
     auto_pred: bool = typer.Option(False, "--auto-pred", help="auto: D_max, its 68 % interval and the fit_predictions "
                                    "rows of a taxon that is not sampled from the importance-weighted posterior "
@@ -96,18 +98,18 @@ def cli_fit(
         "psis_adapt": psis_adapt,
         "auto_pred": auto_pred,
     }
-    if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "nuts-diag",
+    if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "map-evidence", "nuts-diag",
                          "nuts-summary", "nuts-loo", "auto"):
         raise typer.BadParameter("--inference must be nuts, map, map-laplace, map-psis, map-waic, map-pred, "
-                                 "nuts-diag, nuts-summary, nuts-loo or auto")
+                                 "map-evidence, nuts-diag, nuts-summary, nuts-loo or auto")
     if not 25 <= psis_draws <= 1024:
         raise typer.BadParameter("--psis-draws must be in [25, 1024]")
     if not 25 <= pred_draws <= 1024:
         raise typer.BadParameter("--pred-draws must be in [25, 1024]")
     if not 0 <= psis_adapt <= 4:
         raise typer.BadParameter("--psis-adapt must be in [0, 4]")
-    if psis_adapt and inference not in ("map-psis", "map-waic", "auto"):
-        raise typer.BadParameter("--psis-adapt goes with --inference map-psis, map-waic or auto")
+    if psis_adapt and inference not in ("map-psis", "map-waic", "map-evidence", "auto"):
+        raise typer.BadParameter("--psis-adapt goes with --inference map-psis, map-waic, map-evidence or auto")
     if auto_pred and inference != "auto":
         raise typer.BadParameter("--auto-pred goes with --inference auto")
     cfg = utils.Config(**d_cfg)

@@ -46,6 +46,7 @@
 #include "mdfit_mappred.h"
 #include "mdfit_mappsis.h"
 #include "mdfit_mapwaic.h"
+#include "mdfit_mapevid.h"
 #include "mdfit_model.h"
 #include "mdfit_primitive.h"
 #include "mdfit_special.h"
@@ -2181,6 +2182,61 @@ int mdfit_map_waic_adapt(const uint32_t* y, const uint32_t* N, const double* out
                      (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
                      seed, index_base, mp::khat_threshold(S), waic, pointwise, draws, (int)adapt_rounds, adapt);
   return check_launch("map_waic_kernel<adapt>");
+}
+
+int mdfit_map_evidence(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                       int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base, double* evid,
+                       double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace me = mdfit::mapevid;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !evid) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(me::map_evidence_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), evid, draws, 0, (double*)nullptr);
+  return check_launch("map_evidence_kernel");
+}
+
+int mdfit_map_evidence_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                             int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed,
+                             int64_t index_base, double* evid, double* adapt, double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace me = mdfit::mapevid;
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
+    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
+  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
+    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
+  if (n_taxa == 0) return 0;
+  if (!y || !N || !out || !status || !evid) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(me::map_evidence_kernel<true>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), evid, draws, (int)adapt_rounds, adapt);
+  return check_launch("map_evidence_kernel<adapt>");
+}
+
+int mdfit_log_mean_weight(const double* lw, int64_t n_series, int32_t S, double* logz, double* se, double* khat,
+                          void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
+  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
+  if (n_series == 0) return 0;
+  if (!lw || !logz || !se || !khat) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mdfit::mapevid::log_mean_weight_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
+                     (size_t)mp::work_len((int)S) * sizeof(double), (hipStream_t)hip_stream, lw, n_series, (int)S, logz,
+                     se, khat);
+  return check_launch("log_mean_weight_kernel");
 }
 
 int mdfit_adapt_proposal(const double* u, const double* w, const int32_t* mask, const int32_t* c_held, const double* K,

@@ -32,6 +32,11 @@ constexpr int kMinDraws = 25, kMaxDraws = 1024;
 // S <= 1024: the tail holds M <= 96 draws and the grid m <= 39 points
 constexpr int kMaxTail = 96, kMaxGrid = 48;
 constexpr double kFloor = -800.0;  // an infeasible draw's rank value below the maximum: exp() of it is exactly 0
+// one sub-fit's proposal, kNPar words in LDS: the centre u, the scale d, the
+// factor M (psis_draw: draw_j = u_j + d_j sum_{p >= j} M[p][j] t_p), the centre's
+// shift K with a held c, the held c's exponential rate, the free mask, valid,
+// c held
+constexpr int kPU = 0, kPD = 4, kPM = 8, kPK = 24, kPGc = 28, kPMask = 29, kPValid = 30, kPCHeld = 31, kNPar = 32;
 
 using nutsloo::isqrt_floor;
 using nutsloo::khat_threshold;
@@ -87,8 +92,14 @@ MDFIT_NS_FN void sort_pairs(const L& w, double* v, int* ix, int S) {
 // true return buf[t] is the weight of draw t, summing to 1.  False -- buf then
 // unspecified, khat NaN -- when a value is NaN or +inf, or when the draw that
 // sets the tail's cut-off is infeasible.  S in [kMinDraws, kMaxDraws].
+// psis_weights_level is that routine; it also gives up the level that the
+// normalisation drops (MDFIT-EVID v1, mdfit_mapevid.h): shift, the largest
+// finite log-weight, and total, the sum of the smoothed weights exp(buf[t]) of
+// step 6 before they are divided by it (an infeasible draw adds 0).  Both are
+// unspecified on a false return.
 template <class L>
-MDFIT_NS_FN bool psis_weights(const L& w, double* buf, int S, double& khat, double& n_inf) {
+MDFIT_NS_FN bool psis_weights_level(const L& w, double* buf, int S, double& khat, double& n_inf, double& shift,
+                                    double& total) {
   const int lane = w.lane(), nl = w.nlanes();
   double* sv = buf + S;
   double* xs = sv + sort_len(S);
@@ -106,6 +117,8 @@ MDFIT_NS_FN bool psis_weights(const L& w, double* buf, int S, double& khat, doub
   n_inf = w.sum(ninf);
   c = w.max(c);
   khat = ns_nan();
+  shift = c;
+  total = ns_nan();
   if (bad > 0.0 || !(c > -ns_inf())) return false;
   // 2. shifted by the maximum; the rank values (an infeasible draw: the floor), stably sorted
   for (int t = lane; t < S; t += nl) {
@@ -176,9 +189,15 @@ MDFIT_NS_FN bool psis_weights(const L& w, double* buf, int S, double& khat, doub
   double part = 0.0;
   for (int t = lane; t < S; t += nl) part += std::exp(buf[t]);
   const double tot = w.sum(part);
+  total = tot;
   for (int t = lane; t < S; t += nl) buf[t] = std::exp(buf[t]) / tot;
   w.sync();
   return true;
+}
+template <class L>
+MDFIT_NS_FN bool psis_weights(const L& w, double* buf, int S, double& khat, double& n_inf) {
+  double shift, total;
+  return psis_weights_level(w, buf, S, khat, n_inf, shift, total);
 }
 
 // all-NaN record; flags: the free bits alone
@@ -307,9 +326,6 @@ __device__ __forceinline__ uint4 philox(uint32_t k0, uint32_t k1, uint32_t c0, u
 __device__ __forceinline__ double u53(uint32_t a, uint32_t b) {  // [0, 1)
   return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
 }
-
-// one sub-fit's proposal in LDS
-constexpr int kPU = 0, kPD = 4, kPM = 8, kPK = 24, kPGc = 28, kPMask = 29, kPValid = 30, kPCHeld = 31, kNPar = 32;
 
 struct Stream {
   uint32_t k0, k1, c0, c1;

@@ -348,8 +348,129 @@ __device__ __forceinline__ void proposals(const uint32_t* __restrict__ gy, const
   }
 }
 
+// What phases 2-3 leave of one sub-fit: ok, khat and n_inf are psis_weights'
+// of the pass whose weights stand in s_w (the best round's), shift and total
+// its level (psis_weights_level); k0, ess0, best and tried the adapt record.
+struct SubfitWeights {
+  bool ok;
+  double khat, n_inf, shift, total, k0, ess0;
+  int best, tried;
+};
+
+// Phases 2-3 of one sub-fit whose proposal P = s_par[s] is valid, shared by
+// map_waic_kernel and map_evidence_kernel (mdfit_mapevid.h).  Phase 2 -- lanes
+// over draws, the raw log-weight into s_w (map_psis_kernel's statements for a
+// PMD row), u and the log-weight into dr when it is given; with kShift the
+// log-pmf at the proposal's centre into s_l0 (waic_points' shift).  Phase 3 --
+// psis_weights.  kAdapt: the rounds of MDFIT-ADAPT v1 for a PMD row (one pass
+// otherwise): a round's proposal is written over the best one in P, which lane
+// j < 32 keeps word j of in `keep` and puts back when the round is dropped.
+template <bool kAdapt, bool kShift>
+__device__ __forceinline__ SubfitWeights subfit_weights(const PsisWave& w, bool pmd, int lo, int hi, double* P,
+                                                        Stream st, int S, double tau, int adapt_rounds,
+                                                        const double* s_y, const double* s_N, double* s_w,
+                                                        double* s_l0, double* dr) {
+  const int lane = threadIdx.x;
+  const int n = hi - lo;
+  bool ok;
+  double khat, n_inf, shift, total;
+  double k0 = NAN, ess0 = NAN, k_best = NAN, keep = 0.0;
+  int best = 0, tried = 0;
+  bool rerun = false;
+  for (int rnd = 0;;) {
+    // ---- phase 2: lanes over draws ----
+    for (int i = lane; i < S; i += 64) {
+      const DrawU r = mappsis::psis_draw(P, st, i);
+      double lw = -INFINITY;
+      if (pmd) {
+        const ThetaD th = mappsis::psis_theta(r);
+        if (th.feasible) {
+          const double ph = th.delta + 2.0;
+          double ll = 0.0;
+#pragma unroll 1
+          for (int col = lo; col < hi; ++col) {
+            const int kk = col < kNHalf ? col : col - kNHalf;
+            const double D = fma(th.A, powk(th.omq, kk), th.c);
+            ll += bb_logpmf(s_y[col], s_N[col], D, ph);
+          }
+          lw = (ll + th.lj) - r.lg;
+        }
+      } else {
+        const ThetaD th = null_theta(r);
+        const double ph = th.delta + 2.0;
+        double ll = 0.0;
+#pragma unroll 1
+        for (int col = lo; col < hi; ++col) ll += bb_logpmf(s_y[col], s_N[col], th.q, ph);
+        lw = (ll + th.lj) - r.lg;
+      }
+      s_w[i] = lw;
+      if (dr != nullptr) {
+        dr[i * 6 + 0] = r.u0;
+        dr[i * 6 + 1] = r.u1;
+        dr[i * 6 + 2] = r.u2;
+        dr[i * 6 + 3] = r.u3;
+        dr[i * 6 + 4] = lw;
+      }
+    }
+    if constexpr (kShift) {
+      // the shift of the second moments: the log-pmf at the mode (lanes over points)
+      if (lane < n) {
+        DrawU m;
+        m.u0 = P[kPU + 0];
+        m.u1 = P[kPU + 1];
+        m.u2 = P[kPU + 2];
+        m.u3 = P[kPU + 3];
+        m.lg = 0.0;
+        const DrawPt d = draw_point(pmd, m);
+        const int col = lo + lane;
+        const int kk = col < kNHalf ? col : col - kNHalf;
+        const double l = bb_logpmf(s_y[col], s_N[col], fma(d.A, powk(d.w, kk), d.c), d.ph);
+        s_l0[lane] = isfinite(l) ? l : 0.0;
+      }
+    }
+    // ---- phase 3: the smoothed weights ----
+    ok = mappsis::psis_weights_level(w, s_w, S, khat, n_inf, shift, total);
+    if constexpr (!kAdapt) {
+      break;
+    } else {
+      if (!pmd || rerun) break;  // (rerun: the best round's weights are back in s_w, khat and n_inf its own)
+      if (rnd == 0) {
+        if (!ok) break;
+        k0 = khat;
+        ess0 = mapadapt::weights_ess(w, s_w, S);
+      } else {
+        tried = rnd;
+        if (!(ok && isfinite(khat) && khat < k_best)) {  // 6. the round is dropped: the best one once more
+          if (lane < kNPar) P[lane] = keep;
+          __syncthreads();
+          rerun = true;
+          continue;
+        }
+        best = rnd;
+      }
+      k_best = khat;
+      if (rnd == adapt_rounds || k_best <= tau) break;      // 1. the stop test
+      if (lane < kNPar) keep = P[lane];
+      if (!mapadapt::next_proposal(s_w, S, P, st)) break;  // 2-4. the refitted proposal, in place
+      ++rnd;
+    }
+  }
+  SubfitWeights r;
+  r.ok = ok;
+  r.khat = khat;
+  r.n_inf = n_inf;
+  r.shift = shift;
+  r.total = total;
+  r.k0 = k0;
+  r.ess0 = ess0;
+  r.best = best;
+  r.tried = tried;
+  return r;
+}
+
 // One wave per taxon, its six sub-fits one after another in diagnostic-slot
-// order.  Phase 1 twice (proposals<true>, proposals<false>).  Per sub-fit:
+// order.  Phase 1 twice (proposals<true>, proposals<false>).  Per sub-fit
+// (phases 2-3: subfit_weights above, shared with map_evidence_kernel):
 // phase 2 -- lanes over draws, the raw log-weight into LDS (map_psis_kernel's
 // statements for a PMD row); phase 3 -- psis_weights; phase 4 -- waic_points
 // with the draws regenerated from the stream, 64 at a time through a tile of
@@ -426,88 +547,11 @@ __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict
       st.k1 = (uint32_t)(seed >> 32);
       st.c0 = (uint32_t)gtaxon;
       st.c1 = (uint32_t)(gtaxon >> 32) + ((uint32_t)s << 24);  // the chain's sub-fit index
-      // the rounds of MDFIT-ADAPT v1 for a PMD row (one pass otherwise): a round's proposal is written over the
-      // best one in s_par[s], which lane j < 32 keeps word j of in `keep` and puts back when the round is dropped
-      double khat, n_inf;
-      double k0 = NAN, ess0 = NAN, k_best = NAN, keep = 0.0;
-      int best = 0, tried = 0;
-      bool rerun = false;
-      for (int rnd = 0;;) {
-        // ---- phase 2: lanes over draws ----
-        for (int i = lane; i < S; i += 64) {
-          const DrawU r = mappsis::psis_draw(P, st, i);
-          double lw = -INFINITY;
-          if (pmd) {
-            const ThetaD th = mappsis::psis_theta(r);
-            if (th.feasible) {
-              const double ph = th.delta + 2.0;
-              double ll = 0.0;
-#pragma unroll 1
-              for (int col = lo; col < hi; ++col) {
-                const int kk = col < kNHalf ? col : col - kNHalf;
-                const double D = fma(th.A, powk(th.omq, kk), th.c);
-                ll += bb_logpmf(s_y[col], s_N[col], D, ph);
-              }
-              lw = (ll + th.lj) - r.lg;
-            }
-          } else {
-            const ThetaD th = null_theta(r);
-            const double ph = th.delta + 2.0;
-            double ll = 0.0;
-#pragma unroll 1
-            for (int col = lo; col < hi; ++col) ll += bb_logpmf(s_y[col], s_N[col], th.q, ph);
-            lw = (ll + th.lj) - r.lg;
-          }
-          s_w[i] = lw;
-          if (dr != nullptr) {
-            dr[i * 6 + 0] = r.u0;
-            dr[i * 6 + 1] = r.u1;
-            dr[i * 6 + 2] = r.u2;
-            dr[i * 6 + 3] = r.u3;
-            dr[i * 6 + 4] = lw;
-          }
-        }
-        // the shift of the second moments: the log-pmf at the mode (lanes over points)
-        if (lane < n) {
-          DrawU m;
-          m.u0 = P[kPU + 0];
-          m.u1 = P[kPU + 1];
-          m.u2 = P[kPU + 2];
-          m.u3 = P[kPU + 3];
-          m.lg = 0.0;
-          const DrawPt d = draw_point(pmd, m);
-          const int col = lo + lane;
-          const int kk = col < kNHalf ? col : col - kNHalf;
-          const double l = bb_logpmf(s_y[col], s_N[col], fma(d.A, powk(d.w, kk), d.c), d.ph);
-          s_l0[lane] = isfinite(l) ? l : 0.0;
-        }
-        // ---- phase 3: the smoothed weights ----
-        ok = mappsis::psis_weights(w, s_w, S, khat, n_inf);
-        if constexpr (!kAdapt) {
-          break;
-        } else {
-          if (!pmd || rerun) break;  // (rerun: the best round's weights are back in s_w, khat and n_inf its own)
-          if (rnd == 0) {
-            if (!ok) break;
-            k0 = khat;
-            ess0 = mapadapt::weights_ess(w, s_w, S);
-          } else {
-            tried = rnd;
-            if (!(ok && isfinite(khat) && khat < k_best)) {  // 6. the round is dropped: the best one once more
-              if (lane < kNPar) s_par[s][lane] = keep;
-              __syncthreads();
-              rerun = true;
-              continue;
-            }
-            best = rnd;
-          }
-          k_best = khat;
-          if (rnd == adapt_rounds || k_best <= tau) break;              // 1. the stop test
-          if (lane < kNPar) keep = s_par[s][lane];
-          if (!mapadapt::next_proposal(s_w, S, s_par[s], st)) break;  // 2-4. the refitted proposal, in place
-          ++rnd;
-        }
-      }
+      const SubfitWeights sw = subfit_weights<kAdapt, true>(w, pmd, lo, hi, s_par[s], st, S, tau, adapt_rounds, s_y,
+                                                            s_N, s_w, s_l0, dr);
+      ok = sw.ok;
+      const double khat = sw.khat, n_inf = sw.n_inf, k0 = sw.k0, ess0 = sw.ess0;
+      const int best = sw.best, tried = sw.tried;
       if constexpr (kAdapt) {
         if (pmd && adapt != nullptr && lane == 0) {
           double* ar = adapt + (t * 3 + (s == 0 ? 0 : s - 1)) * 4;

@@ -53,6 +53,18 @@ REC_PSIS = 3 * _lib.NMAPPSIS * 4
 # with_waic (a "map-waic" run; never together with any of them): the same for the
 # importance-weighted WAIC records, one more f32 block [n, 7, NMAPWAIC], 224 B per taxon
 REC_WAIC = _lib.NWAICROW * _lib.NMAPWAIC * 4
+# with_evidence (a "map-evidence" run; never together with any of them): the importance-sampled evidence records
+# have the WAIC records' shape, f32 [n, 7, NMAPEVID], and take their place in the layout
+REC_EVID = _lib.NEVIDROW * _lib.NMAPEVID * 4
+assert REC_EVID == REC_WAIC
+
+
+def _evidence_as_waic(with_evidence: bool, with_waic: bool, *others: bool) -> bool:
+    """The with_waic switch of the layout for a run with the evidence block (its only extra block)."""
+    if with_evidence and (with_waic or any(others)):
+        raise ValueError("with_evidence, with_ppred, with_auto, with_waic, with_psis, with_loo, with_summary, with_diag "
+                         "and with_laplace are mutually exclusive: one extra block per run")
+    return bool(with_waic or with_evidence)
 # with_auto (an "auto" run; never together with any of them): the same for the
 # auto block, one more f32 block [n, NAUTO] = route, sampled, khat_max, ess_min, 16 B per taxon
 REC_AUTO = _lib.NAUTO * 4
@@ -144,14 +156,19 @@ class Records:
     6, 16]; with_loo: n * REC_LOO bytes, `loo` f32[n, 7, 8]; with_psis: n *
     REC_PSIS bytes, `psis` f32[n, 3, 16]; with_waic: n * REC_WAIC bytes, `waic`
     f32[n, 7, 8]; with_auto: n * REC_AUTO bytes, `auto` f32[n, 4]; with_ppred: n
-    * REC_PPRED bytes, `ppred` f32[n, 106].  At most one of the eight."""
+    * REC_PPRED bytes, `ppred` f32[n, 106]; with_evidence: n * REC_EVID bytes,
+    `evid` f32[n, 7, 8], where with_waic's block would lie.  At most one of the
+    nine."""
 
     def __init__(self, n: int, device, with_laplace: bool = False, with_diag: bool = False,
                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
                  with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False,
-                 with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False):
+                 with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False,
+                 with_evidence: bool = False):
         import torch
 
+        with_waic = _evidence_as_waic(with_evidence, with_waic, with_laplace, with_diag, with_summary, with_loo,
+                                      with_psis, with_auto, with_ppred)
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
         extra = _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto, with_ppred)
@@ -183,6 +200,9 @@ class Records:
             self.pred, self.status, self.ints, self.floats, self.waic = packed_views(self.buf, n, with_waic=True)
         else:
             self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
+        self.evid = None
+        if with_evidence:  # (the [n, 7, 8] block is the evidence records')
+            self.evid, self.waic = self.waic, None
         self._fidx = torch.as_tensor(FLOAT_COLS, device=device)
 
     def stage(self):
@@ -266,13 +286,14 @@ def _torch_dtype(name):
 def alloc_records(n: int, device, with_laplace: bool = False, with_diag: bool = False,
                   with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
                   with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False,
-                  with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False) -> Records:
+                  with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False,
+                  with_evidence: bool = False) -> Records:
     """with_adapt (psis_adapt > 0, beside with_psis, with_waic or with_auto), or
     with_ppred_adapt (the same beside with_ppred): the buffer is n * REC_ADAPT
     bytes longer, `adapt` f32[n, 2] behind the extra block.  with_auto_pred (beside with_auto): n * REC_AUTO_PRED bytes
     longer, `auto_pred` f32[n, 2] behind the auto block and before `adapt`."""
     return Records(n, device, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto,
-                   with_ppred, with_adapt, with_auto_pred, with_ppred_adapt)
+                   with_ppred, with_adapt, with_auto_pred, with_ppred_adapt, with_evidence)
 
 
 def gather_records(buf, n_cap: int, rank: int, world: int, group=None, async_op: bool = False):
@@ -380,7 +401,8 @@ def run_distributed(fn, *args, **kwargs):
 def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, with_diag: bool = False,
                     with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
                     with_waic: bool = False, with_auto: bool = False, with_ppred: bool = False,
-                    with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False):
+                    with_adapt: bool = False, with_auto_pred: bool = False, with_ppred_adapt: bool = False,
+                    with_evidence: bool = False):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  with_laplace: the
     parts carry the Laplace block and a fourth array lap[T, 3, 8] f32 is returned;
@@ -394,9 +416,13 @@ def unpack_gathered(parts, n_taxa: int, world: int, with_laplace: bool = False, 
     with_psis, with_waic or with_auto; with_ppred_adapt beside with_ppred): the
     parts carry the adapt block behind it, returned last as adapt[T, 2] f32.  with_auto_pred (beside
     with_auto): the parts carry the auto-pred block behind the auto block,
-    returned behind auto[T, 4] as auto_pred[T, 2] f32."""
+    returned behind auto[T, 4] as auto_pred[T, 2] f32.  with_evidence: the
+    importance-sampled evidence records in with_waic's place, returned as
+    evid[T, 7, 8] f32 (with_adapt goes with it too)."""
     import torch
 
+    with_waic = _evidence_as_waic(with_evidence, with_waic, with_laplace, with_diag, with_summary, with_loo, with_psis,
+                                  with_auto, with_ppred)
     outs, preds, sts, laps, adapts, apreds = [], [], [], [], [], []
     rec_extra = _extra(with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic, with_auto, with_ppred)
     rec_bytes = REC_BYTES + rec_extra + _check_adapt(with_adapt, with_psis, with_waic, with_auto, with_ppred,

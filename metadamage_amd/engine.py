@@ -47,6 +47,7 @@ class FitBatch:
     auto: "object" = None  # torch.float32 [T, NAUTO]: route, sampled, khat_max, ess_min (fit_auto_chunks)
     adapt: "object" = None  # torch.float32 [T, NADAPTOUT]: largest round-0 khat, largest best round (psis_adapt > 0)
     auto_pred: "object" = None  # torch.float32 [T, NAUTOPRED]: pred_ess_min, pred_distinct_min (auto with auto_pred)
+    evid: "object" = None  # torch.float32 [T, 7, NMAPEVID]: the importance-sampled evidence records (with_evidence)
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -261,6 +262,57 @@ def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
                                   _stream_handle(torch, stream)))
     got = (waic,) + tuple(x for x in (pointwise, draws) if x is not None)
     return waic if len(got) == 1 else got
+
+
+def map_evidence_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, evid=None,
+                        draws=False, adapt_rounds: int = 0, adapt=None, stream=None):
+    """Launch mdfit_map_evidence on the records of a finished MAP call
+    (asynchronous on `stream`): the importance-sampled marginal likelihood of
+    the six sub-fits and the Bayes factors PMD : null on it (MDFIT-EVID v1),
+    float64 evid[T, 7, NMAPEVID] (_lib.MAPEVID_FIELDS; row 6
+    _lib.MAPEVID_COMPARE_FIELDS).  The Philox streams are keyed by (seed,
+    index_base + taxon, sub-fit).  draws: False / None, True (allocated) or a
+    float64 tensor [T, 6, num_draws, 6] = u[4], the raw log-weight, the weight.
+    Returns evid, or the tuple (evid[, draws]) of what was asked for.
+
+    adapt_rounds > 0, or adapt given (True, or a float64 tensor [T, 3,
+    NMAPADAPT]): mdfit_map_evidence_adapt, the PMD rows with
+    mdfit_map_psis_adapt's rounds; the adapt block is then the last element of
+    the returned tuple."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
+    if draws is False:
+        draws = None
+    use_adapt = R != 0 or adapt is not None
+    if use_adapt and (adapt is None or adapt is True):
+        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
+    if evid is None:
+        evid = torch.empty((T, _lib.NEVIDROW, _lib.NMAPEVID), dtype=torch.float64, device=ty.device)
+    if draws is True:
+        draws = torch.empty((T, _lib.NSUBFIT, S, 6), dtype=torch.float64, device=ty.device)
+    for name, t, n in (("evid", evid, T * _lib.NEVIDROW * _lib.NMAPEVID), ("draws", draws, T * _lib.NSUBFIT * S * 6),
+                       ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    if use_adapt:
+        _lib.check(lib.mdfit_map_evidence_adapt(
+            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
+            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(seed), int(index_base),
+            ctypes.c_void_p(evid.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
+            ctypes.c_void_p(draws.data_ptr()) if draws is not None else None, _stream_handle(torch, stream)))
+        return (evid,) + ((draws,) if draws is not None else ()) + (adapt,)
+    _lib.check(lib.mdfit_map_evidence(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
+                                      ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T,
+                                      S, int(seed), int(index_base), ctypes.c_void_p(evid.data_ptr()),
+                                      ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
+                                      _stream_handle(torch, stream)))
+    return evid if draws is None else (evid, draws)
 
 
 def fit_batch_indexed_device(ty, tN, tm, taxon_index, opts: _lib.MdfitOpts, res: FitBatch | None = None,
@@ -943,6 +995,20 @@ def _check_waic_mode(with_waic: bool, opts: _lib.MdfitOpts | None, with_laplace:
                          "exclusive: one extra block per run")
 
 
+def _check_evidence_mode(with_evidence: bool, opts: _lib.MdfitOpts | None, *others: bool) -> None:
+    """with_evidence is the MAP mode's (opts None: the default options, MAP) and
+    the run's one optional extra block (others: the other blocks' switches).  Its
+    records have the WAIC records' shape, f32 [7][8] on the way out: the buffers,
+    the chunk plan and the gather layout of with_waic serve it."""
+    if not with_evidence:
+        return
+    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
+        raise ValueError("with_evidence needs MAP records (opts.mode == MODE_MAP)")
+    if any(others):
+        raise ValueError("with_evidence, with_ppred, with_waic, with_psis, with_loo, with_summary, with_diag and "
+                         "with_laplace are mutually exclusive: one extra block per run")
+
+
 PRED_DRAWS = 1000  # predictive draws per job of mdfit_map_pred where the caller gives none (the reference's)
 # one taxon's posterior predictive block on the way out, f32: ppred [3][30], then the record [16]
 PPRED_WORDS = _lib.NPRED * _lib.NPOS + _lib.NMAPPRED
@@ -990,7 +1056,7 @@ def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
                  dest_on_device: bool = False, with_laplace: bool = False, with_diag: bool = False,
                  with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                 with_waic: bool = False, with_ppred: bool = False) -> int:
+                 with_waic: bool = False, with_ppred: bool = False, with_evidence: bool = False) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -1014,8 +1080,12 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     ValueError).  with_ppred: the posterior predictive, 360 + 128 B as computed
     (f32 predictions, f64 record) and -- unless they go to the caller's device
     buffer -- 424 B as one f32 block (MAP only, and the run's only extra block:
-    ValueError)."""
+    ValueError).  with_evidence: the importance-sampled evidence records, as
+    with_waic's (MAP only, and the run's only extra block: ValueError)."""
     C = int(C)
+    _check_evidence_mode(with_evidence, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic,
+                         with_ppred)
+    with_waic = with_waic or with_evidence
     _check_diag_mode(with_diag, opts)
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
@@ -1047,7 +1117,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
                 dest_on_device: bool = False, with_laplace: bool = False,
                 with_diag: bool = False, with_summary: bool = False,
                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False,
-                with_ppred: bool = False) -> list[tuple[int, int]]:
+                with_ppred: bool = False, with_evidence: bool = False) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk fit in budget_bytes (None: no memory
     bound), no chunk exceeds the per-call limit (2^25 taxa) or chunk_taxa (> 0;
@@ -1055,6 +1125,9 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     streams are keyed by the global taxon index (opts.index_base + lo), so any
     split gives the records of one call bit for bit."""
     T = int(T)
+    _check_evidence_mode(with_evidence, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic,
+                         with_ppred)
+    with_waic = with_waic or with_evidence
     _check_diag_mode(with_diag, opts)
     _check_summary_mode(with_summary, opts, with_laplace, with_diag)
     _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
@@ -1225,8 +1298,15 @@ class ChunkedFitter:
     rounded to f32 there, leave as one f32 block [T, 106] = ppred [3][30] |
     rec [16], 424 B per taxon (run's fourth array; dest.ppred; split_ppred).
 
-    psis_adapt = R > 0 (with_psis, with_waic or with_ppred): the chunk's launch is
-    mdfit_map_psis_adapt / mdfit_map_waic_adapt / mdfit_map_pred_adapt with at most R moment-matched
+    with_evidence (MAP only; the run's only extra block): mdfit_map_evidence
+    follows each chunk's fit on the compute stream in the same way (psis_draws
+    draws per sub-fit, opts.seed, the chunk's global taxon index), and its
+    records, rounded to f32 there, leave as f32 [T, 7, 8], 224 B per taxon (run's
+    fourth array; dest.evid).  They have the WAIC records' shape and take their
+    buffers.
+
+    psis_adapt = R > 0 (with_psis, with_waic, with_evidence or with_ppred): the chunk's launch is
+    mdfit_map_psis_adapt / mdfit_map_waic_adapt / mdfit_map_evidence_adapt / mdfit_map_pred_adapt with at most R moment-matched
     proposal rounds per PMD row (MDFIT-ADAPT v1), and one more f32 block [T, 2] =
     (largest round-0 khat over the PMD rows, largest best round), reduced on the
     device (adapt_summary), leaves behind the psis, waic or ppred block (run's fifth
@@ -1236,7 +1316,12 @@ class ChunkedFitter:
                  with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False,
                  with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
                  with_psis: bool = False, psis_draws: int = PSIS_DRAWS, with_waic: bool = False,
-                 with_ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0):
+                 with_ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0,
+                 with_evidence: bool = False):
+        _check_evidence_mode(with_evidence, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic,
+                             with_ppred)
+        self.with_evidence = bool(with_evidence)
+        with_waic = with_waic or self.with_evidence  # (the [7][8] block's buffers serve both)
         _check_diag_mode(with_diag, opts)
         _check_summary_mode(with_summary, opts, with_laplace, with_diag)
         _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
@@ -1342,7 +1427,9 @@ class ChunkedFitter:
         if self.with_psis and dest is not None and dest.psis is None:
             raise ValueError("with_psis: dest.psis (float32 [T, 3, NMAPPSIS]) required")
         _check_waic_mode(self.with_waic, o0)
-        if self.with_waic and dest is not None and dest.waic is None:
+        if self.with_evidence and dest is not None and dest.evid is None:
+            raise ValueError("with_evidence: dest.evid (float32 [T, 7, NMAPEVID]) required")
+        if self.with_waic and not self.with_evidence and dest is not None and dest.waic is None:
             raise ValueError("with_waic: dest.waic (float32 [T, 7, NMAPWAIC]) required")
         _check_ppred_mode(self.with_ppred, o0)
         if self.with_ppred and dest is not None and dest.ppred is None:
@@ -1430,7 +1517,13 @@ class ChunkedFitter:
                 with torch.cuda.stream(comp):
                     psis32.copy_(st.psis64[:n])
             waic32 = None
-            if self.with_waic:  # the records are final: their WAIC comparisons, rounded to f32 in place
+            if self.with_evidence:  # the records are final: their evidence, rounded to f32 in place
+                map_evidence_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
+                                    evid=st.waic64[:n], stream=comp, **ad_kw)
+                waic32 = dest.evid[lo:hi] if dest is not None else st.waic[:n]
+                with torch.cuda.stream(comp):
+                    waic32.copy_(st.waic64[:n])
+            elif self.with_waic:  # the records are final: their WAIC comparisons, rounded to f32 in place
                 map_waic_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
                                 waic=st.waic64[:n], stream=comp, **ad_kw)
                 waic32 = dest.waic[lo:hi] if dest is not None else st.waic[:n]
@@ -1596,7 +1689,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
             with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
             with_loo: bool = False, with_psis: bool = False, psis_draws: int = PSIS_DRAWS,
             with_waic: bool = False, with_ppred: bool = False, pred_draws: int = PRED_DRAWS,
-            psis_adapt: int = 0) -> ChunkedFitter:
+            psis_adapt: int = 0, with_evidence: bool = False) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind and sampler length): the
     multi-file pipeline fits one file after another, and pinned + device
@@ -1618,6 +1711,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
            (int(psis_draws), int(pred_draws)) if with_ppred else 0)
     if int(psis_adapt) > 0:  # (the keys of the runs without it are unchanged)
         key = key + (int(psis_adapt),)
+    if with_evidence:
+        key = key + ("evidence", int(psis_draws))
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1635,12 +1730,14 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
                       with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                      with_loo=with_loo, with_psis=with_psis, with_waic=with_waic, with_ppred=with_ppred)[0]
+                      with_loo=with_loo, with_psis=with_psis, with_waic=with_waic, with_ppred=with_ppred,
+                      with_evidence=with_evidence)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
                        with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
                        with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws, with_waic=with_waic,
-                       with_ppred=with_ppred, pred_draws=pred_draws, psis_adapt=psis_adapt)
+                       with_ppred=with_ppred, pred_draws=pred_draws, psis_adapt=psis_adapt,
+                       with_evidence=with_evidence)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1650,7 +1747,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, laplace: bool = False, diag: bool = False,
                    summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = PSIS_DRAWS,
-                   waic: bool = False, ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0):
+                   waic: bool = False, ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0,
+                   evidence: bool = False):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
     the PMD sub-fits (_lib.LAPLACE_FIELDS), or, with diag (NUTS only), diag[T, 6,
@@ -1665,7 +1763,9 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     (_lib.MAPWAIC_FIELDS), or, with ppred (MAP only; the only one), the block
     [T, 106] f32 = ppred [3][30] | rec [16] of the posterior predictive from
     psis_draws importance draws and pred_draws predictive draws (split_ppred,
-    _lib.MAPPRED_FIELDS) --, chunked
+    _lib.MAPPRED_FIELDS), or, with evidence (MAP only; the only one), evid[T, 7,
+    8] f32, the importance-sampled evidence records from psis_draws draws per
+    sub-fit (_lib.MAPEVID_FIELDS) --, chunked
     through the device budget (ChunkedFitter).  mm goes to the device (the
     assembly computes the noise columns); without it, `noise` (float64[T][3],
     ingest.noise) fills them when given.  pinned: y, N, mm are views of that
@@ -1676,17 +1776,18 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace, with_diag=diag,
                      with_summary=summary, with_loo=loo, with_psis=psis, psis_draws=psis_draws,
-                     with_waic=waic, with_ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt)
+                     with_waic=waic, with_ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt,
+                     with_evidence=evidence)
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
-        extra = got[3].copy() if laplace or diag or summary or loo or psis or waic or ppred else None
+        extra = got[3].copy() if laplace or diag or summary or loo or psis or waic or ppred or evidence else None
         adapt = got[4].copy() if int(psis_adapt) > 0 else None
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
     if adapt is not None:
         return out, pred, status, extra, adapt
-    if laplace or diag or summary or loo or psis or waic or ppred:
+    if laplace or diag or summary or loo or psis or waic or ppred or evidence:
         return out, pred, status, extra
     return out, pred, status
 

@@ -118,6 +118,17 @@ MAP_WAIC_COLUMNS = [name for name, _, _ in _MAP_WAIC_PICKS]
 # ... then uint32 map_waic_valid (row 6's bit 0: all six rows valid) and
 # map_waic_reliable (its bit 1: valid, and all six khat at or below the threshold)
 MAP_WAIC_UINT_COLUMNS = ["map_waic_valid", "map_waic_reliable"]
+# "map-evidence": the importance-sampled evidence and Bayes factors appended after shortname,
+# float32 -- (column, row of the record: 0 PMD-all, 1 null-all, 6 the comparisons, its field index); between
+# log_evidence_null and pareto_k_evidence stands damage_probability = 1 / (1 + exp(-log_bf)), formed in float64 ...
+_MAP_EVIDENCE_PICKS = [("log_bf", 6, 0), ("log_bf_forward", 6, 1), ("log_bf_reverse", 6, 2), ("log_bf_asymmetry", 6, 3),
+                       ("log_bf_se", 6, 4), ("log_evidence", 0, 0), ("log_evidence_null", 1, 0),
+                       ("pareto_k_evidence", 6, 5), ("evidence_ess_min", 6, 6)]
+MAP_EVIDENCE_COLUMNS = ([name for name, _, _ in _MAP_EVIDENCE_PICKS[:7]] + ["damage_probability"]
+                        + [name for name, _, _ in _MAP_EVIDENCE_PICKS[7:]])
+# ... then uint32 map_evidence_valid (row 6's bit 0: all six rows valid) and map_evidence_reliable (its bit 1:
+# valid, and all six khat at or below the threshold)
+MAP_EVIDENCE_UINT_COLUMNS = ["map_evidence_valid", "map_evidence_reliable"]
 # a "map-pred" run (mdfit_map_pred, MDFIT-PPRED v1): the posterior predictive D_max columns from
 # importance-weighted draws, their worst k-hat and least ess / distinct draws over the three PMD rows
 _MAP_PRED_PICKS = [("D_max_predictive", "D_max"), ("D_max_predictive_lower_hpdi", "D_max_lower_hpdi"),
@@ -136,7 +147,7 @@ AUTO_COLUMNS = ["pareto_k_max", "psis_ess_min"]
 # (uint32, 0 where the taxon is sampled), the least ess and distinct importance draws over the three PMD rows of the
 # predictive the settled taxon's D_max columns and prediction rows come from
 AUTO_PRED_COLUMNS = ["pred_ess_min", "pred_distinct_min"]
-# psis_adapt > 0 ("map-psis", "map-waic", "map-pred", "auto"): the last two columns -- the largest round-0 Pareto-k over the PMD
+# psis_adapt > 0 ("map-psis", "map-waic", "map-evidence", "map-pred", "auto"): the last two columns -- the largest round-0 Pareto-k over the PMD
 # rows (float32) and the largest best round of MDFIT-ADAPT v1 (uint32)
 ADAPT_COLUMNS = ["pareto_k_initial", "psis_adapt_rounds"]
 INT_RESULT_FIELDS = {"N_alignments", "N_z1_forward", "N_z1_reverse", "N_sum_forward", "N_sum_reverse",
@@ -329,7 +340,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
                summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
                waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
-               psis_adapt: int = 0, auto_pred: bool = False):
+               psis_adapt: int = 0, auto_pred: bool = False, evidence: bool = False):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -352,8 +363,11 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     transfer overlap.  ppred (MAP): mdfit_map_pred follows the fit with
     psis_draws importance draws per sub-fit and pred_draws predictive draws per
     job and the fourth array is the posterior predictive block [T, 106] f32 =
-    ppred [3][30] | rec [16] (engine.split_ppred).  At most one of the eight.
-    psis_adapt > 0 (with psis, waic, ppred or auto): the importance sampling
+    ppred [3][30] | rec [16] (engine.split_ppred).  evidence (MAP):
+    mdfit_map_evidence follows the fit with psis_draws draws per sub-fit and the
+    fourth array is the importance-sampled evidence records evid[T, 7, 8] f32.
+    At most one of the nine.
+    psis_adapt > 0 (with psis, waic, evidence, ppred or auto): the importance sampling
     adapts its proposals in at most that many rounds (MDFIT-ADAPT v1) and one
     more array adapt[T, 2] f32 = (largest round-0 khat, largest best round) is
     returned, last.  auto_pred (with auto; MDFIT-AUTO v1.1): a settled taxon's
@@ -380,9 +394,9 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     # 10k taxa, bench host_to_host) costs no host time, while the host
     # statistics (ingest.noise) take ~1.5 ms of CPU per 10k taxa on the 16-thread
     # share of a multi-file pipeline that is host-bound
-    if auto and (laplace or diag or summary or loo or psis or waic or ppred):
+    if auto and (laplace or diag or summary or loo or psis or waic or ppred or evidence):
         raise ValueError("auto is the run's only extra block")
-    psis_adapt = engine._check_psis_adapt(psis_adapt, psis or waic or auto or ppred)
+    psis_adapt = engine._check_psis_adapt(psis_adapt, psis or waic or auto or ppred or evidence)
     if auto_pred and not auto:
         raise ValueError("auto_pred goes with the auto inference")
     if auto and not grouped:
@@ -395,12 +409,13 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
         try:
             return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
                                          summary=summary, loo=loo, psis=psis, psis_draws=psis_draws, waic=waic,
-                                         ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt)
+                                         ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt,
+                                         evidence=evidence)
         finally:
             p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
     try:
         return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic, auto,
-                            ppred, pred_draws, psis_adapt, auto_pred)
+                            ppred, pred_draws, psis_adapt, auto_pred, evidence)
     finally:
         p.release_pinned()
 
@@ -408,7 +423,7 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
                  summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
                  waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
-                 psis_adapt: int = 0, auto_pred: bool = False):
+                 psis_adapt: int = 0, auto_pred: bool = False, evidence: bool = False):
     import torch
 
     from . import engine
@@ -422,7 +437,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
                         with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred,
                         with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                        with_auto_pred=auto_pred)
+                        with_auto_pred=auto_pred, with_evidence=evidence)
     adapt = rec.adapt[: hi - lo] if psis_adapt > 0 else None
     if hi > lo and auto:  # each rank runs auto on its shard, its rows written in place into the gather buffers
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
@@ -440,7 +455,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
                                 with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
                                 with_psis=psis, psis_draws=psis_draws, with_waic=waic, with_ppred=ppred,
-                                pred_draws=pred_draws, psis_adapt=psis_adapt)
+                                pred_draws=pred_draws, psis_adapt=psis_adapt, with_evidence=evidence)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
                                engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                                                lap=rec.lap[: hi - lo] if laplace else None,
@@ -449,7 +464,8 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
                                                loo=rec.loo[: hi - lo] if loo else None,
                                                psis=rec.psis[: hi - lo] if psis else None,
                                                waic=rec.waic[: hi - lo] if waic else None,
-                                               ppred=rec.ppred[: hi - lo] if ppred else None, adapt=adapt))
+                                               ppred=rec.ppred[: hi - lo] if ppred else None, adapt=adapt,
+                                               evid=rec.evid[: hi - lo] if evidence else None))
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -460,7 +476,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
                            with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred,
                            with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                           with_auto_pred=auto_pred)
+                           with_auto_pred=auto_pred, with_evidence=evidence)
 
 
 # --------------------------------------------------------------------------
@@ -517,7 +533,8 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
-                        psis=None, waic=None, auto=None, ppred=None, adapt=None, auto_pred=None) -> pd.DataFrame:
+                        psis=None, waic=None, auto=None, ppred=None, adapt=None, auto_pred=None,
+                        evid=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -609,6 +626,16 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["map_waic_valid"] = ((flags & _lib.MAPWAIC_VALID) != 0).astype(np.uint32)
         data["map_waic_reliable"] = ((flags & _lib.MAPWAIC_RELIABLE) != 0).astype(np.uint32)
         columns += MAP_WAIC_COLUMNS + MAP_WAIC_UINT_COLUMNS
+    if evid is not None:
+        ke = np.asarray(evid) if keep is None else np.asarray(evid)[keep]
+        for name, row, field in _MAP_EVIDENCE_PICKS:
+            data[name] = np.ascontiguousarray(ke[:, row, field], dtype=np.float32)
+        with np.errstate(over="ignore"):  # (exp(-log_bf) = inf: probability 0)
+            data["damage_probability"] = (1.0 / (1.0 + np.exp(-ke[:, 6, 0].astype(np.float64)))).astype(np.float32)
+        flags = np.nan_to_num(ke[:, 6, _lib.MAPEVID_COMPARE_FIELDS.index("flags")]).astype(np.int64)
+        data["map_evidence_valid"] = ((flags & _lib.MAPEVID_VALID) != 0).astype(np.uint32)
+        data["map_evidence_reliable"] = ((flags & _lib.MAPEVID_RELIABLE) != 0).astype(np.uint32)
+        columns += MAP_EVIDENCE_COLUMNS + MAP_EVIDENCE_UINT_COLUMNS
     if auto is not None:
         ka = np.asarray(auto) if keep is None else np.asarray(auto)[keep]
         data["auto_route"] = _uint32(np.nan_to_num(ka[:, 0]).astype(np.int64))
@@ -676,6 +703,7 @@ def make_opts(cfg, mcmc_kwargs=None):
     "map-laplace" (the MAP fit; wants_laplace adds the standard errors) or
     "map-psis" (the MAP fit; wants_psis adds the importance-sampled posterior) or
     "map-waic" (the MAP fit; wants_waic adds the importance-weighted WAIC comparison) or
+    "map-evidence" (the MAP fit; wants_evidence adds the importance-sampled evidence and Bayes factors) or
     "map-pred" (the MAP fit; wants_pred adds the importance-weighted posterior predictive) or
     "auto" (one option set for the MAP fit and the sampler of engine.fit_auto_device:
     the sampler's mode and lengths, the MAP fit's defaults)."""
@@ -691,14 +719,14 @@ def mode_of(inference: str) -> int:
     """The engine mode of an --inference value: "nuts", "nuts-diag",
     "nuts-summary" and "nuts-loo" (the sampler; wants_diag adds mdfit_nuts_diag,
     wants_summary mdfit_nuts_summary, wants_loo mdfit_nuts_loo) or "map" and
-    "map-laplace", "map-psis", "map-waic" and "map-pred".  "auto" runs both: its option set
+    "map-laplace", "map-psis", "map-waic", "map-evidence" and "map-pred".  "auto" runs both: its option set
     is the sampler's (engine.auto_opts makes the MAP copy)."""
-    if inference in ("map", "map-laplace", "map-psis", "map-waic", "map-pred"):
+    if inference in ("map", "map-laplace", "map-psis", "map-waic", "map-pred", "map-evidence"):
         return _lib.MODE_MAP
     if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo", "auto"):
         return _lib.MODE_NUTS
-    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'map-waic', 'map-pred', 'nuts-diag', "
-                     "'nuts-summary', 'nuts-loo' or 'auto', "
+    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'map-waic', 'map-pred', "
+                     "'map-evidence', 'nuts-diag', 'nuts-summary', 'nuts-loo' or 'auto', "
                      f"got {inference!r}")
 
 
@@ -730,6 +758,11 @@ def wants_psis(cfg) -> bool:
 def wants_waic(cfg) -> bool:
     """cfg.inference "map-waic": the MAP fit followed by mdfit_map_waic."""
     return getattr(cfg, "inference", "nuts") == "map-waic"
+
+
+def wants_evidence(cfg) -> bool:
+    """cfg.inference "map-evidence": the MAP fit followed by mdfit_map_evidence."""
+    return getattr(cfg, "inference", "nuts") == "map-evidence"
 
 
 def wants_pred(cfg) -> bool:
@@ -789,11 +822,12 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
                      summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
                      psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg), auto=wants_auto(cfg),
                      ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg), psis_adapt=psis_adapt_of(cfg),
-                     auto_pred=auto_pred_of(cfg))
+                     auto_pred=auto_pred_of(cfg), evidence=wants_evidence(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
     extra, auto_pred, adapt = _split_rest(cfg, rest)
+    evid = extra if wants_evidence(cfg) else None
     auto = extra if wants_auto(cfg) else None
     lap = extra if wants_laplace(cfg) else None
     diag = extra if wants_diag(cfg) else None
@@ -806,7 +840,7 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
     return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic,
-                                auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred),
+                                auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred, evid=evid),
             make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred))
 
 
@@ -905,11 +939,12 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
                      laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
                      loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg),
                      auto=wants_auto(cfg), ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg),
-                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg))
+                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg), evidence=wants_evidence(cfg))
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
     out, pred, status, *rest = res
     extra, auto_pred, adapt = _split_rest(cfg, rest)
+    evid = extra if wants_evidence(cfg) else None
     auto = extra if wants_auto(cfg) else None
     lap = extra if wants_laplace(cfg) else None
     diag = extra if wants_diag(cfg) else None
@@ -926,7 +961,8 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
         from .counts import _save
 
         df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis,
-                                             waic=waic, auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred)
+                                             waic=waic, auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred,
+                                             evid=evid)
         df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred)
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())

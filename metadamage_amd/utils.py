@@ -61,14 +61,14 @@ class Config:
     N_fits: Optional[int] = None
     # this engine's addition: "nuts" samples like the reference (fits.py:382-387),
     # "map" is the frequentist MAP fit (BASELINE config 2); "map-laplace",
-    # "map-psis", "map-waic", "map-pred", "nuts-diag", "nuts-summary" and "nuts-loo" add their columns
+    # "map-psis", "map-waic", "map-evidence", "map-pred", "nuts-diag", "nuts-summary" and "nuts-loo" add their columns
     # to fit_results; "auto" samples only the taxa the MAP fit's importance sampling cannot settle; saved in the parquet metadata and part of the cache key
     inference: str = "nuts"
-    # the draws per sub-fit of "map-psis", "map-waic", "map-pred" and "auto" (25..1024); in the metadata of such a run only
+    # the draws per sub-fit of "map-psis", "map-waic", "map-evidence", "map-pred" and "auto" (25..1024); in the metadata of such a run only
     psis_draws: int = 256
     # the predictive draws per job of "map-pred" (25..1024; the reference's 1000); in the metadata of such a run only
     pred_draws: int = 1000
-    # moment-matched proposal rounds of "map-psis", "map-waic", "map-pred" and "auto" (0..4; MDFIT-ADAPT v1); in the metadata and
+    # moment-matched proposal rounds of "map-psis", "map-waic", "map-evidence", "map-pred" and "auto" (0..4; MDFIT-ADAPT v1); in the metadata and
     # the cache key of a run with a non-zero value only
     psis_adapt: int = 0
     # "auto": a settled taxon's predictive columns and prediction rows from the importance-weighted posterior
@@ -139,7 +139,7 @@ class Config:
 
     def to_dict(self):
         d_out = asdict(self)
-        if self.inference not in ("map-psis", "map-waic", "map-pred", "auto"):
+        if self.inference not in ("map-psis", "map-waic", "map-pred", "auto", "map-evidence"):
             del d_out["psis_draws"]
         if self.inference != "map-pred" and not self.auto_pred:
             del d_out["pred_draws"]
