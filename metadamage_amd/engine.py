@@ -13,7 +13,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _lib, blocks
 
 
 def _torch():
@@ -37,17 +37,21 @@ class FitBatch:
     pred: "object"  # torch.float32 [T, 3, 30]
     status: "object"  # torch.int32 [T]
     workspace: "object" = None  # torch.uint8 [mdfit_workspace_bytes(T, opts)] (work queues; NUTS: the draws)
-    lap: "object" = None  # torch.float32 [T, 3, NLAPLACE]: the Laplace records (ChunkedFitter with_laplace)
-    diag: "object" = None  # torch.float32 [T, 6, NNUTSDIAG]: the sampling diagnostics (ChunkedFitter with_diag)
-    summ: "object" = None  # torch.float32 [T, 6, NNUTSSUMM]: the posterior summaries (ChunkedFitter with_summary)
-    loo: "object" = None  # torch.float32 [T, 7, NNUTSLOO]: the PSIS-LOO records (ChunkedFitter with_loo)
-    psis: "object" = None  # torch.float32 [T, 3, NMAPPSIS]: the importance-sampled posteriors (ChunkedFitter with_psis)
-    waic: "object" = None  # torch.float32 [T, 7, NMAPWAIC]: the importance-weighted WAIC records (with_waic)
-    ppred: "object" = None  # torch.float32 [T, PPRED_WORDS]: the posterior predictive block (with_ppred; split_ppred)
-    auto: "object" = None  # torch.float32 [T, NAUTO]: route, sampled, khat_max, ess_min (fit_auto_chunks)
-    adapt: "object" = None  # torch.float32 [T, NADAPTOUT]: largest round-0 khat, largest best round (psis_adapt > 0)
-    auto_pred: "object" = None  # torch.float32 [T, NAUTOPRED]: pred_ess_min, pred_distinct_min (auto with auto_pred)
-    evid: "object" = None  # torch.float32 [T, 7, NMAPEVID]: the importance-sampled evidence records (with_evidence)
+    # the run's one optional block, float32 [T, *shape] of its blocks.BLOCKS entry, under the entry's attr (ppred:
+    # split_ppred; auto: fit_auto_chunks), and the tail blocks behind it:
+    # adapt float32 [T, NADAPTOUT], largest round-0 khat, largest best round (psis_adapt > 0);
+    # auto_pred float32 [T, NAUTOPRED], pred_ess_min, pred_distinct_min (auto with auto_pred)
+    lap: "object" = None
+    diag: "object" = None
+    summ: "object" = None
+    loo: "object" = None
+    psis: "object" = None
+    waic: "object" = None
+    ppred: "object" = None
+    auto: "object" = None
+    adapt: "object" = None
+    auto_pred: "object" = None
+    evid: "object" = None
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -924,95 +928,13 @@ N_SETS = 2  # device buffer sets in flight: chunk k+1's H2D (and fit) beside chu
 _BUDGET_FRAC = 0.6  # default device budget of a staging: this fraction of the free device memory
 
 
-LAP_BYTES = 3 * _lib.NLAPLACE * 4  # one taxon's Laplace records as they leave the device: f32 [3][8]
-DIAG_BYTES = _lib.NSUBFIT * _lib.NNUTSDIAG * 4  # one taxon's sampling diagnostics on the way out: f32 [6][12]
-
-
-SUMM_BYTES = _lib.NSUBFIT * _lib.NNUTSSUMM * 4  # one taxon's posterior summaries on the way out: f32 [6][16]
-
-
-def _check_summary_mode(with_summary: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
-                        with_diag: bool = False) -> None:
-    """with_summary is the sampling mode's (opts None: the default options, MAP)
-    and the run's one optional extra block: not together with with_diag or
-    with_laplace."""
-    if not with_summary:
-        return
-    if opts is None or int(opts.mode) != _lib.MODE_NUTS:
-        raise ValueError("with_summary needs the chains of a sampling call (opts.mode == MODE_NUTS)")
-    if with_diag or with_laplace:
-        raise ValueError("with_summary, with_diag and with_laplace are mutually exclusive: one extra block per run")
-
-
-LOO_BYTES = _lib.NLOOROW * _lib.NNUTSLOO * 4  # one taxon's PSIS-LOO records on the way out: f32 [7][8]
-
-
-def _check_loo_mode(with_loo: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
-                    with_diag: bool = False, with_summary: bool = False) -> None:
-    """with_loo is the sampling mode's (opts None: the default options, MAP) and
-    the run's one optional extra block: not together with with_diag,
-    with_summary or with_laplace."""
-    if not with_loo:
-        return
-    if opts is None or int(opts.mode) != _lib.MODE_NUTS:
-        raise ValueError("with_loo needs the chains of a sampling call (opts.mode == MODE_NUTS)")
-    if with_diag or with_summary or with_laplace:
-        raise ValueError("with_loo, with_summary, with_diag and with_laplace are mutually exclusive: "
-                         "one extra block per run")
-
-
-PSIS_BYTES = 3 * _lib.NMAPPSIS * 4  # one taxon's importance-sampled posteriors on the way out: f32 [3][16]
-PSIS_DRAWS = 256  # the default number of draws per sub-fit
-
-
-def _check_psis_mode(with_psis: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
-                     with_diag: bool = False, with_summary: bool = False, with_loo: bool = False) -> None:
-    """with_psis is the MAP mode's (opts None: the default options, MAP) and the
-    run's one optional extra block."""
-    if not with_psis:
-        return
-    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
-        raise ValueError("with_psis needs MAP records (opts.mode == MODE_MAP)")
-    if with_laplace or with_diag or with_summary or with_loo:
-        raise ValueError("with_psis, with_loo, with_summary, with_diag and with_laplace are mutually exclusive: "
-                         "one extra block per run")
-
-
-WAIC_BYTES = _lib.NWAICROW * _lib.NMAPWAIC * 4  # one taxon's WAIC records on the way out: f32 [7][8]
-
-
-def _check_waic_mode(with_waic: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
-                     with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
-                     with_psis: bool = False) -> None:
-    """with_waic is the MAP mode's (opts None: the default options, MAP) and the
-    run's one optional extra block."""
-    if not with_waic:
-        return
-    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
-        raise ValueError("with_waic needs MAP records (opts.mode == MODE_MAP)")
-    if with_laplace or with_diag or with_summary or with_loo or with_psis:
-        raise ValueError("with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace are mutually "
-                         "exclusive: one extra block per run")
-
-
-def _check_evidence_mode(with_evidence: bool, opts: _lib.MdfitOpts | None, *others: bool) -> None:
-    """with_evidence is the MAP mode's (opts None: the default options, MAP) and
-    the run's one optional extra block (others: the other blocks' switches).  Its
-    records have the WAIC records' shape, f32 [7][8] on the way out: the buffers,
-    the chunk plan and the gather layout of with_waic serve it."""
-    if not with_evidence:
-        return
-    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
-        raise ValueError("with_evidence needs MAP records (opts.mode == MODE_MAP)")
-    if any(others):
-        raise ValueError("with_evidence, with_ppred, with_waic, with_psis, with_loo, with_summary, with_diag and "
-                         "with_laplace are mutually exclusive: one extra block per run")
-
-
+_BLOCK = {b.name: b for b in blocks.BLOCKS}
+# one taxon's block as it leaves the device (f32), bytes
+LAP_BYTES, DIAG_BYTES, SUMM_BYTES, LOO_BYTES, PSIS_BYTES, WAIC_BYTES, PPRED_BYTES = (
+    _BLOCK[name].out_bytes for name in ("laplace", "diag", "summary", "loo", "psis", "waic", "ppred"))
+PPRED_WORDS = PPRED_BYTES // 4
+PSIS_DRAWS = 256  # the default number of importance draws per sub-fit
 PRED_DRAWS = 1000  # predictive draws per job of mdfit_map_pred where the caller gives none (the reference's)
-# one taxon's posterior predictive block on the way out, f32: ppred [3][30], then the record [16]
-PPRED_WORDS = _lib.NPRED * _lib.NPOS + _lib.NMAPPRED
-PPRED_BYTES = PPRED_WORDS * 4
 
 
 def split_ppred(block):
@@ -1021,24 +943,17 @@ def split_ppred(block):
     return block[:, :n].reshape(-1, _lib.NPRED, _lib.NPOS), block[:, n:]
 
 
-def _check_ppred_mode(with_ppred: bool, opts: _lib.MdfitOpts | None, with_laplace: bool = False,
-                      with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
-                      with_psis: bool = False, with_waic: bool = False) -> None:
-    """with_ppred is the MAP mode's (opts None: the default options, MAP) and the
-    run's one optional extra block."""
-    if not with_ppred:
-        return
-    if opts is not None and int(opts.mode) != _lib.MODE_MAP:
-        raise ValueError("with_ppred needs MAP records (opts.mode == MODE_MAP)")
-    if with_laplace or with_diag or with_summary or with_loo or with_psis or with_waic:
-        raise ValueError("with_ppred, with_waic, with_psis, with_loo, with_summary, with_diag and with_laplace are "
-                         "mutually exclusive: one extra block per run")
+def _chunked_block(opts, switches):
+    """blocks.resolve for the chunked dispatch: the run's one block, or None."""
+    block = blocks.resolve(opts, **switches)
+    if block is not None and not block.chunked:
+        raise ValueError(f"{block.switch} is not the chunked dispatch's: fit_auto_chunks runs it")
+    return block
 
 
 def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
     """psis_adapt (MDFIT-ADAPT v1's round cap) is 0 .. ADAPT_MAX_ROUNDS and, when
-    not 0, goes with an importance-sampled block (with_psis, with_waic,
-    with_ppred) or auto."""
+    not 0, goes with an importance-sampled block (blocks.Block.sampled)."""
     R = int(psis_adapt)
     if not 0 <= R <= _lib.ADAPT_MAX_ROUNDS:
         raise ValueError(f"psis_adapt must be in [0, {_lib.ADAPT_MAX_ROUNDS}]")
@@ -1047,93 +962,38 @@ def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
     return R
 
 
-def _check_diag_mode(with_diag: bool, opts: _lib.MdfitOpts | None) -> None:
-    """with_diag is the sampling mode's (opts None: the default options, MAP)."""
-    if with_diag and (opts is None or int(opts.mode) != _lib.MODE_NUTS):
-        raise ValueError("with_diag needs the chains of a sampling call (opts.mode == MODE_NUTS)")
-
-
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
-                 dest_on_device: bool = False, with_laplace: bool = False, with_diag: bool = False,
-                 with_summary: bool = False, with_loo: bool = False, with_psis: bool = False,
-                 with_waic: bool = False, with_ppred: bool = False, with_evidence: bool = False) -> int:
+                 dest_on_device: bool = False, **switches) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
     call's workspace (mdfit_workspace_bytes: MAP ~48 B below 60k taxa and
-    ~4.9 KB from 60k, NUTS 6 x num_samples x 32 B, the draws).  with_laplace:
-    the Laplace records, 192 B as computed (f64) and -- unless they go to the
-    caller's device buffer -- 96 B rounded to f32.  with_diag: the sampling
-    diagnostics, 576 B as computed (f64) and -- unless they go to the caller's
-    device buffer -- 288 B rounded to f32 (NUTS only: ValueError under MAP).
-    with_summary: the posterior summaries, 768 B as computed (f64) and --
-    unless they go to the caller's device buffer -- 384 B rounded to f32 (NUTS
-    only, and not together with with_diag or with_laplace: ValueError).
-    with_loo: the PSIS-LOO records, 448 B as computed (f64) and -- unless they
-    go to the caller's device buffer -- 224 B rounded to f32 (NUTS only, and the
-    run's only extra block: ValueError).  with_psis: the importance-sampled
-    posteriors, 384 B as computed (f64) and -- unless they go to the caller's
-    device buffer -- 192 B rounded to f32 (MAP only, and the run's only extra
-    block: ValueError).  with_waic: the importance-weighted WAIC records, 448 B
-    as computed (f64) and -- unless they go to the caller's device buffer --
-    224 B rounded to f32 (MAP only, and the run's only extra block:
-    ValueError).  with_ppred: the posterior predictive, 360 + 128 B as computed
-    (f32 predictions, f64 record) and -- unless they go to the caller's device
-    buffer -- 424 B as one f32 block (MAP only, and the run's only extra block:
-    ValueError).  with_evidence: the importance-sampled evidence records, as
-    with_waic's (MAP only, and the run's only extra block: ValueError)."""
+    ~4.9 KB from 60k, NUTS 6 x num_samples x 32 B, the draws).  switches (one
+    with_* of blocks.BLOCKS, checked by blocks.resolve): the run's block as the
+    launch computes it and -- unless it goes to the caller's device buffer --
+    as it leaves, rounded to f32."""
     C = int(C)
-    _check_evidence_mode(with_evidence, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic,
-                         with_ppred)
-    with_waic = with_waic or with_evidence
-    _check_diag_mode(with_diag, opts)
-    _check_summary_mode(with_summary, opts, with_laplace, with_diag)
-    _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
-    _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
-    _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
-    _check_ppred_mode(with_ppred, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
+    block = _chunked_block(opts, switches)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
-    if with_laplace:
-        b += C * (2 * LAP_BYTES + (0 if dest_on_device else LAP_BYTES))
-    if with_diag:
-        b += C * (2 * DIAG_BYTES + (0 if dest_on_device else DIAG_BYTES))
-    if with_summary:
-        b += C * (2 * SUMM_BYTES + (0 if dest_on_device else SUMM_BYTES))
-    if with_loo:
-        b += C * (2 * LOO_BYTES + (0 if dest_on_device else LOO_BYTES))
-    if with_psis:
-        b += C * (2 * PSIS_BYTES + (0 if dest_on_device else PSIS_BYTES))
-    if with_waic:
-        b += C * (2 * WAIC_BYTES + (0 if dest_on_device else WAIC_BYTES))
-    if with_ppred:
-        b += C * (_lib.NPRED * _lib.NPOS * 4 + _lib.NMAPPRED * 8 + (0 if dest_on_device else PPRED_BYTES))
+    if block is not None:
+        b += C * (block.device_bytes + (0 if dest_on_device else block.out_bytes))
     return b + workspace_bytes(C, opts)
 
 
 def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | None = None, *,
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
-                dest_on_device: bool = False, with_laplace: bool = False,
-                with_diag: bool = False, with_summary: bool = False,
-                with_loo: bool = False, with_psis: bool = False, with_waic: bool = False,
-                with_ppred: bool = False, with_evidence: bool = False) -> list[tuple[int, int]]:
+                dest_on_device: bool = False, **switches) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
-    buffer sets of the largest chunk fit in budget_bytes (None: no memory
-    bound), no chunk exceeds the per-call limit (2^25 taxa) or chunk_taxa (> 0;
-    env MDFIT_CHUNK_TAXA when 0).  Taxa are independent and the sampler's
-    streams are keyed by the global taxon index (opts.index_base + lo), so any
-    split gives the records of one call bit for bit."""
+    buffer sets of the largest chunk (device_bytes, with the run's block of
+    switches) fit in budget_bytes (None: no memory bound), no chunk exceeds the
+    per-call limit (2^25 taxa) or chunk_taxa (> 0; env MDFIT_CHUNK_TAXA when 0).
+    Taxa are independent and the sampler's streams are keyed by the global taxon
+    index (opts.index_base + lo), so any split gives the records of one call bit
+    for bit."""
     T = int(T)
-    _check_evidence_mode(with_evidence, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic,
-                         with_ppred)
-    with_waic = with_waic or with_evidence
-    _check_diag_mode(with_diag, opts)
-    _check_summary_mode(with_summary, opts, with_laplace, with_diag)
-    _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
-    _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
-    _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
-    _check_ppred_mode(with_ppred, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
+    _chunked_block(opts, switches)
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -1142,8 +1002,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     if chunk_taxa > 0:
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
-        per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, with_laplace,  # noqa: E731
-                                              with_diag, with_summary, with_loo, with_psis, with_waic, with_ppred)
+        per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, **switches)  # noqa: E731
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
         if per(cap) > budget_bytes:  # largest c with per(c) <= budget (per is monotone in c)
@@ -1175,9 +1034,7 @@ class _Set:
     run one after another on the compute stream)."""
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
-                 with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-                 with_loo: bool = False, with_psis: bool = False, with_waic: bool = False,
-                 with_ppred: bool = False, with_adapt: bool = False):
+                 block: blocks.Block | None = None, with_adapt: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -1187,50 +1044,66 @@ class _Set:
             self.pred = (torch.empty((C, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=device)
                          if with_pred else None)
             self.status = torch.empty((C,), dtype=torch.int32, device=device)
-        self.lap64 = self.lap = None
-        if with_laplace:  # as mdfit_map_laplace writes them, and rounded to f32 for the way out
-            self.lap64 = torch.empty((C, 3, _lib.NLAPLACE), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.lap = torch.empty((C, 3, _lib.NLAPLACE), dtype=torch.float32, device=device)
-        self.diag64 = self.diag = None
-        if with_diag:  # as mdfit_nuts_diag writes them, and rounded to f32 for the way out
-            self.diag64 = torch.empty((C, _lib.NSUBFIT, _lib.NNUTSDIAG), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.diag = torch.empty((C, _lib.NSUBFIT, _lib.NNUTSDIAG), dtype=torch.float32, device=device)
-        self.summ64 = self.summ = None
-        if with_summary:  # as mdfit_nuts_summary writes them, and rounded to f32 for the way out
-            self.summ64 = torch.empty((C, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.summ = torch.empty((C, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float32, device=device)
-        self.loo64 = self.loo = None
-        if with_loo:  # as mdfit_nuts_loo writes them, and rounded to f32 for the way out
-            self.loo64 = torch.empty((C, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.loo = torch.empty((C, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float32, device=device)
-        self.psis64 = self.psis = None
-        if with_psis:  # as mdfit_map_psis writes them, and rounded to f32 for the way out
-            self.psis64 = torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.psis = torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float32, device=device)
-        self.waic64 = self.waic = None
-        if with_waic:  # as mdfit_map_waic writes them, and rounded to f32 for the way out
-            self.waic64 = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.waic = torch.empty((C, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32, device=device)
+        # the run's block as its launch writes it, and as one f32 block for the way out
+        self.computed = [torch.empty((C, *shape), dtype=getattr(torch, dtype), device=device)
+                         for shape, dtype in (block.device if block is not None else ())]
+        self.block = None
+        if block is not None and not dest_on_device:
+            self.block = torch.empty((C, *block.shape), dtype=torch.float32, device=device)
         self.adapt64 = self.adapt = None
         if with_adapt:  # as the adapt entries write it, and reduced to f32 [C, 2] for the way out
             self.adapt64 = torch.empty((C, 3, _lib.NMAPADAPT), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.adapt = torch.empty((C, _lib.NADAPTOUT), dtype=torch.float32, device=device)
-        self.ppred32 = self.prec64 = self.ppred = None
-        if with_ppred:  # as mdfit_map_pred writes them, and one f32 block for the way out
-            self.ppred32 = torch.empty((C, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=device)
-            self.prec64 = torch.empty((C, _lib.NMAPPRED), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.ppred = torch.empty((C, PPRED_WORDS), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
+
+
+# One launch function per chunked block: the block's *_device call on the first n taxa of buffer set st, whose
+# records res holds, into st.computed on the compute stream comp.  f: the fitter (the draw counts); o: the chunk's
+# options (its index_base is the chunk's global taxon index, which keys the Philox streams beside o.seed); ad_kw:
+# adapt_rounds and adapt of the sampled blocks when psis_adapt > 0 (the launch is then the *_adapt entry).  The MAP
+# blocks read the final records; the NUTS blocks read this chunk's draws in the one workspace, which the stream
+# keeps until the next chunk's fit.
+def _launch_laplace(f, st, n, res, o, comp, ad_kw):
+    map_laplace_device(st.d_y[:n], st.d_N[:n], res, lap=st.computed[0][:n], stream=comp)
+
+
+def _launch_diag(f, st, n, res, o, comp, ad_kw):
+    nuts_diag_device(res, n, o, diag=st.computed[0][:n], stream=comp)
+
+
+def _launch_summary(f, st, n, res, o, comp, ad_kw):
+    nuts_summary_device(res, n, o, summ=st.computed[0][:n], stream=comp)
+
+
+def _launch_loo(f, st, n, res, o, comp, ad_kw):
+    nuts_loo_device(st.d_y[:n], st.d_N[:n], res, n, o, loo=st.computed[0][:n], stream=comp)
+
+
+def _launch_psis(f, st, n, res, o, comp, ad_kw):
+    map_psis_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
+                    psis=st.computed[0][:n], stream=comp, **ad_kw)
+
+
+def _launch_waic(f, st, n, res, o, comp, ad_kw):
+    map_waic_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
+                    waic=st.computed[0][:n], stream=comp, **ad_kw)
+
+
+def _launch_evidence(f, st, n, res, o, comp, ad_kw):
+    map_evidence_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
+                        evid=st.computed[0][:n], stream=comp, **ad_kw)
+
+
+def _launch_ppred(f, st, n, res, o, comp, ad_kw):
+    map_pred_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, f.pred_draws, int(o.seed), int(o.index_base),
+                    ppred=st.computed[0][:n], rec=st.computed[1][:n], stream=comp, **ad_kw)
+
+
+_LAUNCH = {"laplace": _launch_laplace, "diag": _launch_diag, "summary": _launch_summary, "loo": _launch_loo,
+           "psis": _launch_psis, "waic": _launch_waic, "evidence": _launch_evidence, "ppred": _launch_ppred}
 
 
 class ChunkedFitter:
@@ -1256,104 +1129,40 @@ class ChunkedFitter:
     straight into the caller's device tensors (the sharded fit's gather
     records).
 
-    with_laplace (MAP only): mdfit_map_laplace follows each chunk's fit on the
-    compute stream, its records are rounded to f32 there and leave with the
-    chunk's other results (96 B per taxon; run returns them as a fourth array,
-    run_into_device writes dest.lap) -- no further stream or hardware queue.
+    switches (one with_* of blocks.BLOCKS; one optional block per run keeps the
+    gather record's layout a single switch): the block's launch (_LAUNCH)
+    follows each chunk's fit on the compute stream -- no further stream or
+    hardware queue --, its records are rounded to f32 there and leave with the
+    chunk's other results (run's fourth array; run_into_device writes dest's
+    attribute of the block).  The sampled blocks take psis_draws draws per
+    sub-fit (ppred also pred_draws predictive draws per job).
 
-    with_diag (NUTS only): mdfit_nuts_diag follows each chunk's fit on the
-    compute stream -- the one workspace holds that chunk's draws until the next
-    chunk's fit, which the stream orders behind it -- and its records leave as
-    with_laplace's do (f32 [T, 6, 12], 288 B per taxon; dest.diag).  In that f32
-    block a row's flags are valid + 2 * the chain's divergence count (the
-    record's diagnostic slot 7, which does not leave the device otherwise).
-
-    with_summary (NUTS only; not together with with_diag or with_laplace -- one
-    optional extra block per run keeps the gather record's layout a single
-    switch): mdfit_nuts_summary follows each chunk's fit on the compute stream
-    in the same way, and its records, rounded to f32 there, leave as f32 [T, 6,
-    16], 384 B per taxon (run's fourth array; dest.summ).
-
-    with_loo (NUTS only; the run's only extra block): mdfit_nuts_loo follows
-    each chunk's fit on the compute stream in the same way, reading the chunk's
-    device counts beside its draws, and its records, rounded to f32 there, leave
-    as f32 [T, 7, 8], 224 B per taxon (run's fourth array; dest.loo).
-
-    with_psis (MAP only; the run's only extra block): mdfit_map_psis follows
-    each chunk's fit on the compute stream with psis_draws draws per sub-fit,
-    its streams keyed by opts.seed and the chunk's global taxon index, and its
-    records, rounded to f32 there, leave as f32 [T, 3, 16], 192 B per taxon
-    (run's fourth array; dest.psis).
-
-    with_waic (MAP only; the run's only extra block): mdfit_map_waic follows
-    each chunk's fit on the compute stream in the same way (psis_draws draws
-    per sub-fit, opts.seed, the chunk's global taxon index), and its records,
-    rounded to f32 there, leave as f32 [T, 7, 8], 224 B per taxon (run's fourth
-    array; dest.waic).
-
-    with_ppred (MAP only; the run's only extra block): mdfit_map_pred follows
-    each chunk's fit on the compute stream in the same way (psis_draws
-    importance draws per sub-fit, pred_draws predictive draws per job,
-    opts.seed, the chunk's global taxon index); its predictions and its record,
-    rounded to f32 there, leave as one f32 block [T, 106] = ppred [3][30] |
-    rec [16], 424 B per taxon (run's fourth array; dest.ppred; split_ppred).
-
-    with_evidence (MAP only; the run's only extra block): mdfit_map_evidence
-    follows each chunk's fit on the compute stream in the same way (psis_draws
-    draws per sub-fit, opts.seed, the chunk's global taxon index), and its
-    records, rounded to f32 there, leave as f32 [T, 7, 8], 224 B per taxon (run's
-    fourth array; dest.evid).  They have the WAIC records' shape and take their
-    buffers.
-
-    psis_adapt = R > 0 (with_psis, with_waic, with_evidence or with_ppred): the chunk's launch is
-    mdfit_map_psis_adapt / mdfit_map_waic_adapt / mdfit_map_evidence_adapt / mdfit_map_pred_adapt with at most R moment-matched
-    proposal rounds per PMD row (MDFIT-ADAPT v1), and one more f32 block [T, 2] =
-    (largest round-0 khat over the PMD rows, largest best round), reduced on the
-    device (adapt_summary), leaves behind the psis, waic or ppred block (run's fifth
-    array; dest.adapt)."""
+    psis_adapt = R > 0 (a sampled block): the chunk's launch runs at most R
+    moment-matched proposal rounds per PMD row (MDFIT-ADAPT v1), and one more
+    f32 block [T, 2] = (largest round-0 khat over the PMD rows, largest best
+    round), reduced on the device (adapt_summary), leaves behind the block
+    (run's fifth array; dest.adapt)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
-                 with_mm: bool = True, dest_on_device: bool = False, with_laplace: bool = False,
-                 with_diag: bool = False, with_summary: bool = False, with_loo: bool = False,
-                 with_psis: bool = False, psis_draws: int = PSIS_DRAWS, with_waic: bool = False,
-                 with_ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0,
-                 with_evidence: bool = False):
-        _check_evidence_mode(with_evidence, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic,
-                             with_ppred)
-        self.with_evidence = bool(with_evidence)
-        with_waic = with_waic or self.with_evidence  # (the [7][8] block's buffers serve both)
-        _check_diag_mode(with_diag, opts)
-        _check_summary_mode(with_summary, opts, with_laplace, with_diag)
-        _check_loo_mode(with_loo, opts, with_laplace, with_diag, with_summary)
-        _check_psis_mode(with_psis, opts, with_laplace, with_diag, with_summary, with_loo)
-        _check_waic_mode(with_waic, opts, with_laplace, with_diag, with_summary, with_loo, with_psis)
-        _check_ppred_mode(with_ppred, opts, with_laplace, with_diag, with_summary, with_loo, with_psis, with_waic)
+                 with_mm: bool = True, dest_on_device: bool = False, psis_draws: int = PSIS_DRAWS,
+                 pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, **switches):
+        self.block = _chunked_block(opts, switches)
         torch = _torch()
-        if with_laplace and opts is not None and int(opts.mode) != _lib.MODE_MAP:
-            raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
-        self.with_laplace = bool(with_laplace)
-        self.with_diag = bool(with_diag)
-        self.with_summary = bool(with_summary)
-        self.with_loo = bool(with_loo)
-        self.with_psis = bool(with_psis)
-        self.with_waic = bool(with_waic)
-        self.with_ppred = bool(with_ppred)
-        self.psis_adapt = _check_psis_adapt(psis_adapt, with_psis or with_waic or with_ppred)
+        self.psis_adapt = _check_psis_adapt(psis_adapt, self.block is not None and self.block.sampled)
         self.pred_draws = int(pred_draws)
         self.psis_draws = int(psis_draws)
         self.chunk_cap = int(chunk_cap)
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
-        self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.with_laplace,
-                          self.with_diag, self.with_summary, self.with_loo, self.with_psis, self.with_waic,
-                          self.with_ppred, self.psis_adapt > 0)
+        self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.block,
+                          self.psis_adapt > 0)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
-        self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = self.h_lap = None
-        self.h_diag = self.h_summ = self.h_loo = self.h_psis = self.h_waic = self.h_ppred = self.h_adapt = None
+        self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = None
+        self.h_block = self.h_adapt = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -1369,20 +1178,8 @@ class ChunkedFitter:
             self.h_pred = (torch.empty((cap, _lib.NPRED, _lib.NPOS), dtype=torch.float32).pin_memory()
                            if self.with_pred else None)
             self.h_status = torch.empty((cap,), dtype=torch.int32).pin_memory()
-            if self.with_laplace:
-                self.h_lap = torch.empty((cap, 3, _lib.NLAPLACE), dtype=torch.float32).pin_memory()
-            if self.with_diag:
-                self.h_diag = torch.empty((cap, _lib.NSUBFIT, _lib.NNUTSDIAG), dtype=torch.float32).pin_memory()
-            if self.with_summary:
-                self.h_summ = torch.empty((cap, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float32).pin_memory()
-            if self.with_loo:
-                self.h_loo = torch.empty((cap, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float32).pin_memory()
-            if self.with_psis:
-                self.h_psis = torch.empty((cap, 3, _lib.NMAPPSIS), dtype=torch.float32).pin_memory()
-            if self.with_waic:
-                self.h_waic = torch.empty((cap, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float32).pin_memory()
-            if self.with_ppred:
-                self.h_ppred = torch.empty((cap, PPRED_WORDS), dtype=torch.float32).pin_memory()
+            if self.block is not None:
+                self.h_block = torch.empty((cap, *self.block.shape), dtype=torch.float32).pin_memory()
             if self.psis_adapt > 0:
                 self.h_adapt = torch.empty((cap, _lib.NADAPTOUT), dtype=torch.float32).pin_memory()
         self.capacity = cap
@@ -1410,30 +1207,12 @@ class ChunkedFitter:
         torch = _torch()
         lib = _lib.load()
         o0 = opts if opts is not None else _lib.default_opts()
-        if self.with_laplace and int(o0.mode) != _lib.MODE_MAP:
-            raise ValueError("with_laplace needs MAP records (opts.mode == MODE_MAP)")
-        if self.with_laplace and dest is not None and dest.lap is None:
-            raise ValueError("with_laplace: dest.lap (float32 [T, 3, NLAPLACE]) required")
-        _check_diag_mode(self.with_diag, o0)  # (the mirror image of with_laplace)
-        if self.with_diag and dest is not None and dest.diag is None:
-            raise ValueError("with_diag: dest.diag (float32 [T, 6, NNUTSDIAG]) required")
-        _check_summary_mode(self.with_summary, o0)
-        if self.with_summary and dest is not None and dest.summ is None:
-            raise ValueError("with_summary: dest.summ (float32 [T, 6, NNUTSSUMM]) required")
-        _check_loo_mode(self.with_loo, o0)
-        if self.with_loo and dest is not None and dest.loo is None:
-            raise ValueError("with_loo: dest.loo (float32 [T, 7, NNUTSLOO]) required")
-        _check_psis_mode(self.with_psis, o0)
-        if self.with_psis and dest is not None and dest.psis is None:
-            raise ValueError("with_psis: dest.psis (float32 [T, 3, NMAPPSIS]) required")
-        _check_waic_mode(self.with_waic, o0)
-        if self.with_evidence and dest is not None and dest.evid is None:
-            raise ValueError("with_evidence: dest.evid (float32 [T, 7, NMAPEVID]) required")
-        if self.with_waic and not self.with_evidence and dest is not None and dest.waic is None:
-            raise ValueError("with_waic: dest.waic (float32 [T, 7, NMAPWAIC]) required")
-        _check_ppred_mode(self.with_ppred, o0)
-        if self.with_ppred and dest is not None and dest.ppred is None:
-            raise ValueError("with_ppred: dest.ppred (float32 [T, PPRED_WORDS]) required")
+        block = self.block
+        if block is not None:
+            blocks.resolve(o0, **{block.switch: True})  # (this run's options, not only the constructor's)
+            if dest is not None and getattr(dest, block.attr) is None:
+                shape = ", ".join(map(str, block.shape))
+                raise ValueError(f"{block.switch}: dest.{block.attr} (float32 [T, {shape}]) required")
         if self.psis_adapt > 0 and dest is not None and dest.adapt is None:
             raise ValueError("psis_adapt: dest.adapt (float32 [T, NADAPTOUT]) required")
         src_y, src_N, src_mm = src
@@ -1478,66 +1257,21 @@ class ChunkedFitter:
                 _lib.check(lib.mdfit_noise(ctypes.c_void_p(st.d_y.data_ptr()), ctypes.c_void_p(st.d_N.data_ptr()),
                                            ctypes.c_void_p(st.d_mm.data_ptr()), n, ctypes.c_void_p(res.out.data_ptr()),
                                            h_s))
-            lap32 = None
-            if self.with_laplace:  # the records are final: their standard errors, rounded to f32 in place
-                map_laplace_device(st.d_y[:n], st.d_N[:n], res, lap=st.lap64[:n], stream=comp)
-                lap32 = dest.lap[lo:hi] if dest is not None else st.lap[:n]
+            block32 = adapt32 = None
+            if block is not None:  # the records are final: the block's launch, then one f32 block for the way out
+                ad_kw = {"adapt_rounds": self.psis_adapt, "adapt": st.adapt64[:n]} if self.psis_adapt > 0 else {}
+                _LAUNCH[block.name](self, st, n, res, o, comp, ad_kw)
+                block32 = getattr(dest, block.attr)[lo:hi] if dest is not None else st.block[:n]
                 with torch.cuda.stream(comp):
-                    lap32.copy_(st.lap64[:n])
-            diag32 = None
-            if self.with_diag:  # this chunk's draws, before the next chunk's fit overwrites the workspace
-                nuts_diag_device(res, n, o, diag=st.diag64[:n], stream=comp)
-                diag32 = dest.diag[lo:hi] if dest is not None else st.diag[:n]
-                with torch.cuda.stream(comp):
-                    diag32.copy_(st.diag64[:n])
-                    # on the way out the flags also carry the chain's divergence count (the record's
-                    # slot 7, not among the columns that leave the device): valid + 2 * divergences
-                    div = torch.nan_to_num(res.out[:, _lib.F_DIAG + 7::_lib.DIAG_STRIDE], nan=0.0)
-                    diag32[:, :, _lib.NNUTSDIAG - 1] += (2.0 * div).to(torch.float32)
-            summ32 = None
-            if self.with_summary:  # this chunk's draws, before the next chunk's fit overwrites the workspace
-                nuts_summary_device(res, n, o, summ=st.summ64[:n], stream=comp)
-                summ32 = dest.summ[lo:hi] if dest is not None else st.summ[:n]
-                with torch.cuda.stream(comp):
-                    summ32.copy_(st.summ64[:n])
-            loo32 = None
-            if self.with_loo:  # this chunk's draws and counts, before the next chunk's fit overwrites the workspace
-                nuts_loo_device(st.d_y[:n], st.d_N[:n], res, n, o, loo=st.loo64[:n], stream=comp)
-                loo32 = dest.loo[lo:hi] if dest is not None else st.loo[:n]
-                with torch.cuda.stream(comp):
-                    loo32.copy_(st.loo64[:n])
-            psis32 = adapt32 = None
-            ad_kw = {}
-            if self.psis_adapt > 0:
-                ad_kw = {"adapt_rounds": self.psis_adapt, "adapt": st.adapt64[:n]}
-            if self.with_psis:  # the records are final: their posteriors, rounded to f32 in place
-                map_psis_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
-                                psis=st.psis64[:n], stream=comp, **ad_kw)
-                psis32 = dest.psis[lo:hi] if dest is not None else st.psis[:n]
-                with torch.cuda.stream(comp):
-                    psis32.copy_(st.psis64[:n])
-            waic32 = None
-            if self.with_evidence:  # the records are final: their evidence, rounded to f32 in place
-                map_evidence_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
-                                    evid=st.waic64[:n], stream=comp, **ad_kw)
-                waic32 = dest.evid[lo:hi] if dest is not None else st.waic[:n]
-                with torch.cuda.stream(comp):
-                    waic32.copy_(st.waic64[:n])
-            elif self.with_waic:  # the records are final: their WAIC comparisons, rounded to f32 in place
-                map_waic_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
-                                waic=st.waic64[:n], stream=comp, **ad_kw)
-                waic32 = dest.waic[lo:hi] if dest is not None else st.waic[:n]
-                with torch.cuda.stream(comp):
-                    waic32.copy_(st.waic64[:n])
-            ppred32 = None
-            if self.with_ppred:  # the records are final: their posterior predictive, one f32 block for the way out
-                map_pred_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, self.pred_draws, int(o.seed),
-                                int(o.index_base), ppred=st.ppred32[:n], rec=st.prec64[:n], stream=comp, **ad_kw)
-                ppred32 = dest.ppred[lo:hi] if dest is not None else st.ppred[:n]
-                with torch.cuda.stream(comp):
-                    pp_v, rec_v = split_ppred(ppred32)
-                    pp_v.copy_(st.ppred32[:n])
-                    rec_v.copy_(st.prec64[:n])
+                    # (ppred: its two computed pieces into the two views of the block; the others: one rounding copy)
+                    views = split_ppred(block32) if block.name == "ppred" else (block32,)
+                    for view, computed in zip(views, st.computed):
+                        view.copy_(computed[:n])
+                    if block.name == "diag":
+                        # on the way out the flags also carry the chain's divergence count (the record's
+                        # slot 7, not among the columns that leave the device): valid + 2 * divergences
+                        div = torch.nan_to_num(res.out[:, _lib.F_DIAG + 7::_lib.DIAG_STRIDE], nan=0.0)
+                        block32[:, :, _lib.NNUTSDIAG - 1] += (2.0 * div).to(torch.float32)
             if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
                 adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
                 with torch.cuda.stream(comp):
@@ -1552,20 +1286,8 @@ class ChunkedFitter:
                     if res.pred is not None:
                         self.h_pred[lo:hi].copy_(res.pred, non_blocking=True)
                     self.h_status[lo:hi].copy_(res.status, non_blocking=True)
-                    if lap32 is not None:
-                        self.h_lap[lo:hi].copy_(lap32, non_blocking=True)
-                    if diag32 is not None:
-                        self.h_diag[lo:hi].copy_(diag32, non_blocking=True)
-                    if summ32 is not None:
-                        self.h_summ[lo:hi].copy_(summ32, non_blocking=True)
-                    if loo32 is not None:
-                        self.h_loo[lo:hi].copy_(loo32, non_blocking=True)
-                    if psis32 is not None:
-                        self.h_psis[lo:hi].copy_(psis32, non_blocking=True)
-                    if waic32 is not None:
-                        self.h_waic[lo:hi].copy_(waic32, non_blocking=True)
-                    if ppred32 is not None:
-                        self.h_ppred[lo:hi].copy_(ppred32, non_blocking=True)
+                    if block32 is not None:
+                        self.h_block[lo:hi].copy_(block32, non_blocking=True)
                     if adapt32 is not None:
                         self.h_adapt[lo:hi].copy_(adapt32, non_blocking=True)
                 last_d2h = cp
@@ -1576,13 +1298,11 @@ class ChunkedFitter:
 
     def run(self, y, N, mm=None, opts: _lib.MdfitOpts | None = None, sync: bool = True,
             pinned: PinnedPack | None = None, chunks=None):
-        """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status -- and,
-        with_laplace, lap[:, 3, 8] f32, or, with_diag, diag[:, 6, 12] f32, or,
-        with_summary, summ[:, 6, 16] f32, or, with_loo, loo[:, 7, 8] f32, or,
-        with_psis, psis[:, 3, 16] f32, or, with_waic, waic[:, 7, 8] f32) of the
-        pinned buffers (valid until the next run).  pinned: y, N, mm are that
-        PinnedPack's views.  chunks: the split (default plan_chunks at this
-        staging's chunk_cap)."""
+        """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status[, the
+        run's block f32 [T, *shape]][, adapt f32 [T, 2]]) of the pinned buffers
+        (valid until the next run).  pinned: y, N, mm are that PinnedPack's
+        views.  chunks: the split (default plan_chunks at this staging's
+        chunk_cap)."""
         T = int(y.shape[0])
         if chunks is None:
             chunks = plan_chunks(T, opts, chunk_taxa=self.chunk_cap)
@@ -1592,34 +1312,19 @@ class ChunkedFitter:
         end = self._launch(chunks, self._sources(y, N, mm, pinned), opts)
         if sync:
             end.synchronize()
-        pred = self.h_pred[:T].numpy() if self.h_pred is not None else None
-        if self.with_laplace:
-            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_lap[:T].numpy()
-        if self.with_diag:
-            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_diag[:T].numpy()
-        if self.with_summary:
-            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_summ[:T].numpy()
-        if self.with_loo:
-            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_loo[:T].numpy()
-        if self.psis_adapt > 0:  # (a fifth array beside the psis, waic or ppred block)
-            block = self.h_psis if self.with_psis else (self.h_waic if self.with_waic else self.h_ppred)
-            return (self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), block[:T].numpy(),
-                    self.h_adapt[:T].numpy())
-        if self.with_psis:
-            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_psis[:T].numpy()
-        if self.with_waic:
-            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_waic[:T].numpy()
-        if self.with_ppred:
-            return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy(), self.h_ppred[:T].numpy()
-        return self.h_out[:T].numpy(), pred, self.h_status[:T].numpy()
+        got = (self.h_out[:T].numpy(), self.h_pred[:T].numpy() if self.h_pred is not None else None,
+               self.h_status[:T].numpy())
+        if self.block is not None:
+            got += (self.h_block[:T].numpy(),)
+        if self.psis_adapt > 0:
+            got += (self.h_adapt[:T].numpy(),)
+        return got
 
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
-        (out[T, NOUT], pred, status -- with_laplace also lap, f32 [T, 3, 8],
-        with_diag also diag, f32 [T, 6, 12], with_summary also summ, f32 [T, 6, 16], with_loo also loo, f32
-        [T, 7, 8], with_psis also psis, f32 [T, 3, 16], with_waic also waic, f32 [T, 7, 8],
-        with_ppred also ppred, f32 [T, 106]: rows written in place),
-        ordered on the caller's current stream."""
+        (out[T, NOUT], pred, status -- and the run's block under its attribute,
+        adapt when psis_adapt > 0: rows written in place), ordered on the
+        caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
             chunks = plan_chunks(T, opts, chunk_taxa=self.chunk_cap)
@@ -1685,13 +1390,11 @@ _STAGING_LOCK = __import__("threading").Lock()
 
 
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
-            dest_on_device: bool = False, budget_bytes: int | None = None,
-            with_laplace: bool = False, with_diag: bool = False, with_summary: bool = False,
-            with_loo: bool = False, with_psis: bool = False, psis_draws: int = PSIS_DRAWS,
-            with_waic: bool = False, with_ppred: bool = False, pred_draws: int = PRED_DRAWS,
-            psis_adapt: int = 0, with_evidence: bool = False) -> ChunkedFitter:
+            dest_on_device: bool = False, budget_bytes: int | None = None, psis_draws: int = PSIS_DRAWS,
+            pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, **switches) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
-    of this process (per device, buffer kind and sampler length): the
+    of this process (per device, buffer kind, sampler length and the run's block
+    of switches with the draw counts it uses and psis_adapt): the
     multi-file pipeline fits one file after another, and pinned + device
     buffers allocated per file cost more host time than the fit.  Its chunk
     capacity is the largest chunk N_SETS buffer sets of which fit the device
@@ -1705,14 +1408,11 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
         dev = torch.device(dev.type, torch.cuda.current_device())
     o = opts if opts is not None else _lib.default_opts()
     env_chunk = int(os.environ.get("MDFIT_CHUNK_TAXA", "0") or 0)
+    block = _chunked_block(o, switches)
     key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
-           bool(with_laplace), bool(with_diag), bool(with_summary), bool(with_loo),
-           int(psis_draws) if with_psis else 0, int(psis_draws) if with_waic else 0,
-           (int(psis_draws), int(pred_draws)) if with_ppred else 0)
-    if int(psis_adapt) > 0:  # (the keys of the runs without it are unchanged)
-        key = key + (int(psis_adapt),)
-    if with_evidence:
-        key = key + ("evidence", int(psis_draws))
+           block.name if block is not None else None,
+           int(psis_draws) if block is not None and block.sampled else 0,
+           int(pred_draws) if block is not None and block.name == "ppred" else 0, int(psis_adapt))
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1729,15 +1429,10 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     if T < _lib.STREAM_MAX_TAXA:
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
-                      with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                      with_loo=with_loo, with_psis=with_psis, with_waic=with_waic, with_ppred=with_ppred,
-                      with_evidence=with_evidence)[0]
+                      **switches)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
-                       with_laplace=with_laplace, with_diag=with_diag, with_summary=with_summary,
-                       with_loo=with_loo, with_psis=with_psis, psis_draws=psis_draws, with_waic=with_waic,
-                       with_ppred=with_ppred, pred_draws=pred_draws, psis_adapt=psis_adapt,
-                       with_evidence=with_evidence)
+                       psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, **switches)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1745,51 +1440,28 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 
 
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
-                   pinned: PinnedPack | None = None, laplace: bool = False, diag: bool = False,
-                   summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = PSIS_DRAWS,
-                   waic: bool = False, ppred: bool = False, pred_draws: int = PRED_DRAWS, psis_adapt: int = 0,
-                   evidence: bool = False):
+                   pinned: PinnedPack | None = None, psis_draws: int = PSIS_DRAWS, pred_draws: int = PRED_DRAWS,
+                   psis_adapt: int = 0, **named):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
-    laplace (MAP only), a fourth array lap[T, 3, 8] f32, the Laplace records of
-    the PMD sub-fits (_lib.LAPLACE_FIELDS), or, with diag (NUTS only), diag[T, 6,
-    12] f32, the sampling diagnostics of the six sub-fits (_lib.NUTSDIAG_FIELDS), or, with summary
-    (NUTS only; at most one of the three), summ[T, 6, 16] f32, their posterior
-    summaries (_lib.NUTSSUMM_FIELDS), or, with loo (NUTS only; the only one),
-    loo[T, 7, 8] f32, the PSIS-LOO records (_lib.NUTSLOO_FIELDS), or, with psis
-    (MAP only; the only one), psis[T, 3, 16] f32, the importance-sampled
-    posteriors of the PMD sub-fits from psis_draws draws each
-    (_lib.MAPPSIS_FIELDS), or, with waic (MAP only; the only one), waic[T, 7, 8]
-    f32, the importance-weighted WAIC records from psis_draws draws per sub-fit
-    (_lib.MAPWAIC_FIELDS), or, with ppred (MAP only; the only one), the block
-    [T, 106] f32 = ppred [3][30] | rec [16] of the posterior predictive from
-    psis_draws importance draws and pred_draws predictive draws (split_ppred,
-    _lib.MAPPRED_FIELDS), or, with evidence (MAP only; the only one), evid[T, 7,
-    8] f32, the importance-sampled evidence records from psis_draws draws per
-    sub-fit (_lib.MAPEVID_FIELDS) --, chunked
-    through the device budget (ChunkedFitter).  mm goes to the device (the
-    assembly computes the noise columns); without it, `noise` (float64[T][3],
-    ingest.noise) fills them when given.  pinned: y, N, mm are views of that
-    PinnedPack (copied to the device from there).  psis_adapt > 0 (with psis,
-    waic or ppred): the launch adapts its proposals (ChunkedFitter psis_adapt) and a fifth
-    array adapt[T, 2] f32 (_lib.ADAPTOUT_FIELDS) is returned."""
+    named (one chunked block of blocks.BLOCKS by its name, e.g. laplace=True), a
+    fourth array, the block's f32 [T, *shape] --, chunked through the device
+    budget (ChunkedFitter, which documents psis_draws, pred_draws and
+    psis_adapt; psis_adapt > 0 returns a fifth array adapt[T, 2] f32,
+    _lib.ADAPTOUT_FIELDS).  mm goes to the device (the assembly computes the
+    noise columns); without it, `noise` (float64[T][3], ingest.noise) fills them
+    when given.  pinned: y, N, mm are views of that PinnedPack (copied to the
+    device from there)."""
     T = int(y.shape[0])
     with _STAGING_LOCK:
-        st = staging(T, device=device, opts=opts, with_mm=mm is not None, with_laplace=laplace, with_diag=diag,
-                     with_summary=summary, with_loo=loo, with_psis=psis, psis_draws=psis_draws,
-                     with_waic=waic, with_ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt,
-                     with_evidence=evidence)
+        st = staging(T, device=device, opts=opts, with_mm=mm is not None, psis_draws=psis_draws,
+                     pred_draws=pred_draws, psis_adapt=psis_adapt, **{"with_" + k: v for k, v in named.items()})
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
-        out, pred, status = got[0].copy(), got[1].copy(), got[2].copy()
-        extra = got[3].copy() if laplace or diag or summary or loo or psis or waic or ppred or evidence else None
-        adapt = got[4].copy() if int(psis_adapt) > 0 else None
+        got = tuple(a.copy() for a in got)
+    out, status = got[0], got[2]
     if mm is None and noise is not None:
         ok = status != _lib.INVALID
         out[ok, _lib.RESULT_FIELDS.index("normalized_noise"):_lib.NRESULT] = np.asarray(noise)[ok]
-    if adapt is not None:
-        return out, pred, status, extra, adapt
-    if laplace or diag or summary or loo or psis or waic or ppred or evidence:
-        return out, pred, status, extra
-    return out, pred, status
+    return got
 
 
 def special(x, device="cuda"):

@@ -24,7 +24,7 @@ import warnings
 import numpy as np
 import pandas as pd
 
-from . import _lib, io, utils
+from . import _lib, blocks, io, utils
 
 logger = logging.getLogger(__name__)
 
@@ -337,40 +337,23 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
-def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, diag: bool = False,
-               summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-               waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
-               psis_adapt: int = 0, auto_pred: bool = False, evidence: bool = False):
+def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, pred_draws: int = 1000,
+               psis_adapt: int = 0, auto_pred: bool = False, **named):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
-    laplace (MAP): mdfit_map_laplace follows the fit and a fourth array, the
-    Laplace records lap[T, 3, 8] f32, is returned.  diag (NUTS): mdfit_nuts_diag
-    follows the fit and the fourth array is the sampling diagnostics diag[T, 6,
-    12] f32 (flags: bit 0 valid, above it the chain's divergence count).  summary
-    (NUTS): mdfit_nuts_summary follows the fit and the fourth array is the
-    posterior summaries summ[T, 6, 16] f32.  loo (NUTS): mdfit_nuts_loo follows
-    the fit and the fourth array is the PSIS-LOO records loo[T, 7, 8] f32.
-    psis (MAP): mdfit_map_psis follows the fit with psis_draws draws per sub-fit
-    and the fourth array is the importance-sampled posteriors psis[T, 3, 16]
-    f32.  waic (MAP): mdfit_map_waic follows the fit with psis_draws draws per
-    sub-fit and the fourth array is the importance-weighted WAIC records
-    waic[T, 7, 8] f32.  auto: the auto inference (engine.fit_auto_chunks: the
-    MAP fit, its importance-sampled correction with psis_draws draws per sub-fit
-    and the sampler over the taxa that does not settle; opts carries both fits'
-    options) and the fourth array is the auto block auto[T, 4] f32 = route,
-    sampled, khat_max, ess_min; its chunks run one after another, with no
-    transfer overlap.  ppred (MAP): mdfit_map_pred follows the fit with
-    psis_draws importance draws per sub-fit and pred_draws predictive draws per
-    job and the fourth array is the posterior predictive block [T, 106] f32 =
-    ppred [3][30] | rec [16] (engine.split_ppred).  evidence (MAP):
-    mdfit_map_evidence follows the fit with psis_draws draws per sub-fit and the
-    fourth array is the importance-sampled evidence records evid[T, 7, 8] f32.
-    At most one of the nine.
-    psis_adapt > 0 (with psis, waic, evidence, ppred or auto): the importance sampling
-    adapts its proposals in at most that many rounds (MDFIT-ADAPT v1) and one
-    more array adapt[T, 2] f32 = (largest round-0 khat, largest best round) is
-    returned, last.  auto_pred (with auto; MDFIT-AUTO v1.1): a settled taxon's
+    named (at most one block of blocks.BLOCKS by its name, e.g. laplace=True):
+    the block's launch follows the fit (engine.ChunkedFitter) and a fourth
+    array, the block's f32 [T, *shape], is returned; the sampled blocks take
+    psis_draws draws per sub-fit, ppred also pred_draws predictive draws per
+    job.  auto: the auto inference instead (engine.fit_auto_chunks: the MAP fit,
+    its importance-sampled correction and the sampler over the taxa that does
+    not settle; opts carries both fits' options); its chunks run one after
+    another, with no transfer overlap.
+    psis_adapt > 0 (with a sampled block): the importance sampling adapts its
+    proposals in at most that many rounds (MDFIT-ADAPT v1) and one more array
+    adapt[T, 2] f32 = (largest round-0 khat, largest best round) is returned,
+    last.  auto_pred (with auto; MDFIT-AUTO v1.1): a settled taxon's
     predictive columns and prediction rows are the importance-weighted posterior
     predictive from pred_draws draws per job, and auto_pred[T, 2] f32 =
     (pred_ess_min, pred_distinct_min) is returned behind the auto block."""
@@ -394,36 +377,26 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, laplace: bool = False, 
     # 10k taxa, bench host_to_host) costs no host time, while the host
     # statistics (ingest.noise) take ~1.5 ms of CPU per 10k taxa on the 16-thread
     # share of a multi-file pipeline that is host-bound
-    if auto and (laplace or diag or summary or loo or psis or waic or ppred or evidence):
-        raise ValueError("auto is the run's only extra block")
-    psis_adapt = engine._check_psis_adapt(psis_adapt, psis or waic or auto or ppred or evidence)
+    # (the block's mode is checked against opts where the fit is planned: engine.staging)
+    block = blocks.select(**{"with_" + name: on for name, on in named.items()})
+    auto = block is not None and not block.chunked
+    psis_adapt = engine._check_psis_adapt(psis_adapt, block is not None and block.sampled)
     if auto_pred and not auto:
         raise ValueError("auto_pred goes with the auto inference")
-    if auto and not grouped:
-        try:
+    try:
+        if grouped:
+            return _fit_sharded(p, opts, dev, rank, world, block, psis_draws, pred_draws, psis_adapt, auto_pred)
+        if auto:
             return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt,
                                           auto_pred=auto_pred, pred_draws=pred_draws)
-        finally:
-            p.release_pinned()
-    if not grouped:
-        try:
-            return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, laplace=laplace, diag=diag,
-                                         summary=summary, loo=loo, psis=psis, psis_draws=psis_draws, waic=waic,
-                                         ppred=ppred, pred_draws=pred_draws, psis_adapt=psis_adapt,
-                                         evidence=evidence)
-        finally:
-            p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
-    try:
-        return _fit_sharded(p, opts, dev, rank, world, laplace, diag, summary, loo, psis, psis_draws, waic, auto,
-                            ppred, pred_draws, psis_adapt, auto_pred, evidence)
+        return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, psis_draws=psis_draws,
+                                     pred_draws=pred_draws, psis_adapt=psis_adapt, **named)
     finally:
-        p.release_pinned()
+        p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
 
 
-def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = False, diag: bool = False,
-                 summary: bool = False, loo: bool = False, psis: bool = False, psis_draws: int = 256,
-                 waic: bool = False, auto: bool = False, ppred: bool = False, pred_draws: int = 1000,
-                 psis_adapt: int = 0, auto_pred: bool = False, evidence: bool = False):
+def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Block | None = None,
+                 psis_draws: int = 256, pred_draws: int = 1000, psis_adapt: int = 0, auto_pred: bool = False):
     import torch
 
     from . import engine
@@ -434,38 +407,26 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
         opts = _lib.MdfitOpts.from_buffer_copy(opts)
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
-    rec = alloc_records(cap, dev, with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                        with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred,
-                        with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                        with_auto_pred=auto_pred, with_evidence=evidence)
-    adapt = rec.adapt[: hi - lo] if psis_adapt > 0 else None
-    if hi > lo and auto:  # each rank runs auto on its shard, its rows written in place into the gather buffers
+    switch = {block.switch: True} if block is not None else {}
+    ppred = block is not None and block.name == "ppred"  # (its adapt tail has a switch of its own)
+    layout = dict(switch, with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
+                  with_auto_pred=auto_pred)
+    rec = alloc_records(cap, dev, **layout)
+    # the rows are written in place into the gather buffers
+    dest = engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
+                           adapt=rec.adapt[: hi - lo] if psis_adapt > 0 else None,
+                           auto_pred=rec.auto_pred[: hi - lo] if auto_pred else None,
+                           **({block.attr: getattr(rec, block.attr)[: hi - lo]} if block is not None else {}))
+    if hi > lo and block is not None and not block.chunked:  # each rank runs auto on its shard
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
-                               device=dev, dest=engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo],
-                                                                rec.status[: hi - lo], auto=rec.auto[: hi - lo],
-                                                                adapt=adapt,
-                                                                auto_pred=rec.auto_pred[: hi - lo] if auto_pred
-                                                                else None),
-                               psis_adapt=psis_adapt, auto_pred=auto_pred, pred_draws=pred_draws)
+                               device=dev, dest=dest, psis_adapt=psis_adapt, auto_pred=auto_pred,
+                               pred_draws=pred_draws)
         torch.cuda.synchronize(dev)
-    elif hi > lo:
-        # the shard through the bounded-memory chunked dispatch, each chunk's
-        # records written in place into the gather buffers
+    elif hi > lo:  # the shard through the bounded-memory chunked dispatch
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
-                                with_laplace=laplace, with_diag=diag, with_summary=summary, with_loo=loo,
-                                with_psis=psis, psis_draws=psis_draws, with_waic=waic, with_ppred=ppred,
-                                pred_draws=pred_draws, psis_adapt=psis_adapt, with_evidence=evidence)
-            st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts,
-                               engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
-                                               lap=rec.lap[: hi - lo] if laplace else None,
-                                               diag=rec.diag[: hi - lo] if diag else None,
-                                               summ=rec.summ[: hi - lo] if summary else None,
-                                               loo=rec.loo[: hi - lo] if loo else None,
-                                               psis=rec.psis[: hi - lo] if psis else None,
-                                               waic=rec.waic[: hi - lo] if waic else None,
-                                               ppred=rec.ppred[: hi - lo] if ppred else None, adapt=adapt,
-                                               evid=rec.evid[: hi - lo] if evidence else None))
+                                psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, **switch)
+            st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, dest)
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -473,10 +434,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, laplace: bool = Fa
     parts = gather_records(buf, cap, rank, world)
     if rank != 0:
         return None
-    return unpack_gathered(parts, p.n_taxa, world, with_laplace=laplace, with_diag=diag, with_summary=summary,
-                           with_loo=loo, with_psis=psis, with_waic=waic, with_auto=auto, with_ppred=ppred,
-                           with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                           with_auto_pred=auto_pred, with_evidence=evidence)
+    return unpack_gathered(parts, p.n_taxa, world, **layout)
 
 
 # --------------------------------------------------------------------------
@@ -715,19 +673,18 @@ def make_opts(cfg, mcmc_kwargs=None):
                              num_samples=int(kw.get("num_samples", 1000)))
 
 
+# the engine mode of every --inference value: the plain fits, then each block's ("auto" runs both: its option set is
+# the sampler's, engine.auto_opts makes the MAP copy)
+_MODE_OF = {"map": _lib.MODE_MAP, "nuts": _lib.MODE_NUTS,
+            **{b.inference: _lib.MODE_NUTS if b.mode is None else b.mode for b in blocks.BLOCKS}}
+
+
 def mode_of(inference: str) -> int:
-    """The engine mode of an --inference value: "nuts", "nuts-diag",
-    "nuts-summary" and "nuts-loo" (the sampler; wants_diag adds mdfit_nuts_diag,
-    wants_summary mdfit_nuts_summary, wants_loo mdfit_nuts_loo) or "map" and
-    "map-laplace", "map-psis", "map-waic", "map-evidence" and "map-pred".  "auto" runs both: its option set
-    is the sampler's (engine.auto_opts makes the MAP copy)."""
-    if inference in ("map", "map-laplace", "map-psis", "map-waic", "map-pred", "map-evidence"):
-        return _lib.MODE_MAP
-    if inference in ("nuts", "nuts-diag", "nuts-summary", "nuts-loo", "auto"):
-        return _lib.MODE_NUTS
-    raise ValueError("inference must be 'nuts', 'map', 'map-laplace', 'map-psis', 'map-waic', 'map-pred', "
-                     "'map-evidence', 'nuts-diag', 'nuts-summary', 'nuts-loo' or 'auto', "
-                     f"got {inference!r}")
+    """The engine mode of an --inference value: "nuts" and the nuts-* values
+    (the sampler), "map" and the map-* values, or "auto" (the sampler's)."""
+    if inference not in _MODE_OF:
+        raise ValueError("inference must be " + ", ".join(repr(k) for k in _MODE_OF) + f", got {inference!r}")
+    return _MODE_OF[inference]
 
 
 def wants_diag(cfg) -> bool:
@@ -810,6 +767,28 @@ def psis_draws_of(cfg) -> int:
     return int(getattr(cfg, "psis_draws", 256) or 256)
 
 
+def _fit_for_frames(p: Packed, cfg, opts, shard: bool):
+    """fit_packed as cfg asks: None on a non-zero rank of a multi-GPU job, else
+    (out, pred, keep, kw) -- keep the taxa that fitted (the others warned
+    about), kw the optional arrays under make_df_fit_results' keywords."""
+    inference = getattr(cfg, "inference", "nuts")
+    block = next((b for b in blocks.BLOCKS if b.inference == inference), None)
+    res = fit_packed(p, opts, shard=shard, psis_draws=psis_draws_of(cfg), pred_draws=pred_draws_of(cfg),
+                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg),
+                     **({block.name: True} if block is not None else {}))
+    if res is None:
+        return None
+    out, pred, status, *rest = res
+    extra, auto_pred, adapt = _split_rest(cfg, rest)
+    kw = {"adapt": adapt, "auto_pred": auto_pred}
+    if block is not None:
+        kw[block.attr] = extra
+    keep = status == _lib.OK
+    for t in np.where(~keep)[0]:
+        logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
+    return out, pred, keep, kw
+
+
 def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     """fits.py:709-730: (df_fit_results, df_fit_predictions) for every taxon of
     df_counts, in df_counts order, by the sampler (cfg.inference "nuts", the
@@ -818,30 +797,12 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
     if opts is None:
         opts = make_opts(cfg, mcmc_kwargs)
     p = pack_counts(df_counts, cfg)
-    res = fit_packed(p, opts, shard=shard, laplace=wants_laplace(cfg), diag=wants_diag(cfg),
-                     summary=wants_summary(cfg), loo=wants_loo(cfg), psis=wants_psis(cfg),
-                     psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg), auto=wants_auto(cfg),
-                     ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg), psis_adapt=psis_adapt_of(cfg),
-                     auto_pred=auto_pred_of(cfg), evidence=wants_evidence(cfg))
+    res = _fit_for_frames(p, cfg, opts, shard)
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
-    out, pred, status, *rest = res
-    extra, auto_pred, adapt = _split_rest(cfg, rest)
-    evid = extra if wants_evidence(cfg) else None
-    auto = extra if wants_auto(cfg) else None
-    lap = extra if wants_laplace(cfg) else None
-    diag = extra if wants_diag(cfg) else None
-    summ = extra if wants_summary(cfg) else None
-    loo = extra if wants_loo(cfg) else None
-    psis = extra if wants_psis(cfg) else None
-    waic = extra if wants_waic(cfg) else None
-    ppred = extra if wants_pred(cfg) else None
-    keep = status == _lib.OK
-    for t in np.where(~keep)[0]:
-        logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
-    return (make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis, waic=waic,
-                                auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred, evid=evid),
-            make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred))
+    out, pred, keep, kw = res
+    return (make_df_fit_results(p, out, keep, cfg, **kw),
+            make_df_fit_predictions(p, pred, keep, cfg, ppred=kw.get("ppred")))
 
 
 def extract_top_max_fits(df_counts, max_fits):
@@ -935,35 +896,16 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
     p = packed if packed is not None else pack_counts(get_top_max_fits(df_counts, cfg.N_fits), cfg)
     # fits.py:792-799
     mcmc_kwargs = dict(progress_bar=False, num_warmup=500, num_samples=1000, num_chains=1, chain_method="sequential")
-    res = fit_packed(p, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard=shard,
-                     laplace=wants_laplace(cfg), diag=wants_diag(cfg), summary=wants_summary(cfg),
-                     loo=wants_loo(cfg), psis=wants_psis(cfg), psis_draws=psis_draws_of(cfg), waic=wants_waic(cfg),
-                     auto=wants_auto(cfg), ppred=wants_pred(cfg), pred_draws=pred_draws_of(cfg),
-                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg), evidence=wants_evidence(cfg))
+    res = _fit_for_frames(p, cfg, opts if opts is not None else make_opts(cfg, mcmc_kwargs), shard)
     if res is None:  # non-zero rank of a multi-GPU job
         return None, None
-    out, pred, status, *rest = res
-    extra, auto_pred, adapt = _split_rest(cfg, rest)
-    evid = extra if wants_evidence(cfg) else None
-    auto = extra if wants_auto(cfg) else None
-    lap = extra if wants_laplace(cfg) else None
-    diag = extra if wants_diag(cfg) else None
-    summ = extra if wants_summary(cfg) else None
-    loo = extra if wants_loo(cfg) else None
-    psis = extra if wants_psis(cfg) else None
-    waic = extra if wants_waic(cfg) else None
-    ppred = extra if wants_pred(cfg) else None
-    keep = status == _lib.OK
-    for t in np.where(~keep)[0]:
-        logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")
+    out, pred, keep, kw = res
 
     def finish():
         from .counts import _save
 
-        df_fit_results = make_df_fit_results(p, out, keep, cfg, lap=lap, diag=diag, summ=summ, loo=loo, psis=psis,
-                                             waic=waic, auto=auto, ppred=ppred, adapt=adapt, auto_pred=auto_pred,
-                                             evid=evid)
-        df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=ppred)
+        df_fit_results = make_df_fit_results(p, out, keep, cfg, **kw)
+        df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=kw.get("ppred"))
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
         return df_fit_results, df_fit_predictions

@@ -434,8 +434,11 @@ def test_config_metadata_cache_key_and_cli(tmp_path):
         engine.plan_chunks(10, fits.make_opts(_cfg(tmp_path, "nuts")), with_evidence=True)
     assert engine._check_psis_adapt(2, True) == 2
     assert d.REC_EVID == 7 * 8 * 4
+    n = 5
     with pytest.raises(ValueError, match="mutually exclusive"):
-        d._evidence_as_waic(True, True)
+        d.alloc_records(n, "cpu", with_evidence=True, with_waic=True)
     with pytest.raises(ValueError, match="mutually exclusive"):
-        d._evidence_as_waic(True, False, False, True)
-    assert d._evidence_as_waic(True, False) and d._evidence_as_waic(False, True) and not d._evidence_as_waic(False, False)
+        d.alloc_records(n, "cpu", with_evidence=True, with_diag=True)
+    for kw in ({"with_evidence": True}, {"with_waic": True}):
+        assert d.alloc_records(n, "cpu", **kw).buf.numel() == n * (d.REC_BYTES + 224)
+    assert d.alloc_records(n, "cpu").buf.numel() == n * d.REC_BYTES
