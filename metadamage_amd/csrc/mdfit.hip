@@ -1765,6 +1765,123 @@ int launch_hpdi(const mdfit::HpdiIO& io, int64_t n_items, int* ctr, mdfit::hpdi:
 
 void mdfit::host::prof_mark(int slot, hipStream_t s) { prof_record(slot, s); }
 
+namespace {
+
+// The argument checks of the importance sampler's entries, in the order every
+// one of them makes them: the entries proper over n taxa (num_draws, num_pred,
+// adapt_rounds) and the one-wave helpers over n series (S, R).  num_pred and
+// adapt_rounds: null in an entry that has no such argument.  ptrs: the
+// required pointers are all there.  Returns 1 -- launch; 0 -- nothing to do;
+// MDFIT_E_ARG, the message recorded.
+int check_is_args(bool helper, int64_t n, int32_t num_draws, const int32_t* num_pred, const int32_t* adapt_rounds,
+                  bool ptrs) {
+  namespace mp = mdfit::mappsis;
+  namespace mq = mdfit::mappred;
+  if (n < 0) return set_err(MDFIT_E_ARG, helper ? "n_series < 0" : "n_taxa < 0");
+  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)  // (a five-draw tail; the LDS bound)
+    return set_err(MDFIT_E_ARG, helper ? "S must be in [25, 1024]" : "num_draws must be in [25, 1024]");
+  if (num_pred != nullptr && (*num_pred < mq::kMinPred || *num_pred > mq::kMaxPred))
+    return set_err(MDFIT_E_ARG, helper ? "R must be in [25, 1024]" : "num_pred must be in [25, 1024]");
+  if (adapt_rounds != nullptr && (*adapt_rounds < 0 || *adapt_rounds > mdfit::mapadapt::kMaxRounds))
+    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
+  if (n == 0) return 0;
+  if (!ptrs) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n > ((int64_t)1 << 25))
+    return set_err(MDFIT_E_ARG, helper ? "n_series exceeds 2^25 per call" : "n_taxa exceeds 2^25 per call");
+  return 1;
+}
+
+// One launch function per kernel: the plain entry is <false> with no rounds
+// and no adapt record, the _adapt entry <true>.
+template <bool kAdapt>
+int launch_map_psis(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                    int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base, double* psis,
+                    double* adapt, double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  const int rc = check_is_args(false, n_taxa, num_draws, nullptr, &adapt_rounds, y && N && out && status && psis);
+  if (rc <= 0) return rc;
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mp::map_psis_kernel<kAdapt>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), psis, draws, (int)adapt_rounds, adapt);
+  return check_launch(kAdapt ? "map_psis_kernel<adapt>" : "map_psis_kernel");
+}
+
+template <bool kAdapt>
+int launch_map_waic(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                    int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base, double* waic,
+                    double* adapt, double* pointwise, double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace mw = mdfit::mapwaic;
+  const int rc = check_is_args(false, n_taxa, num_draws, nullptr, &adapt_rounds, y && N && out && status && waic);
+  if (rc <= 0) return rc;
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(mw::map_waic_kernel<kAdapt>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), waic, pointwise, draws, (int)adapt_rounds, adapt);
+  return check_launch(kAdapt ? "map_waic_kernel<adapt>" : "map_waic_kernel");
+}
+
+template <bool kAdapt>
+int launch_map_evidence(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                        int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base, double* evid,
+                        double* adapt, double* draws, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace me = mdfit::mapevid;
+  const int rc = check_is_args(false, n_taxa, num_draws, nullptr, &adapt_rounds, y && N && out && status && evid);
+  if (rc <= 0) return rc;
+  const int S = (int)num_draws;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  hipLaunchKernelGGL(me::map_evidence_kernel<kAdapt>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
+                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
+                     seed, index_base, mp::khat_threshold(S), evid, draws, (int)adapt_rounds, adapt);
+  return check_launch(kAdapt ? "map_evidence_kernel<adapt>" : "map_evidence_kernel");
+}
+
+// (map_pred_kernel<true> is launched from its own unit, mdfit_mappred_adapt.hip)
+template <bool kAdapt>
+int launch_map_pred(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                    int32_t num_draws, int32_t num_pred, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
+                    float* ppred, double* rec, double* adapt, int32_t* index, uint32_t* counts, void* hip_stream) {
+  namespace mp = mdfit::mappsis;
+  namespace mq = mdfit::mappred;
+  const int rc =
+      check_is_args(false, n_taxa, num_draws, &num_pred, &adapt_rounds, y && N && out && status && ppred && rec);
+  if (rc <= 0) return rc;
+  const int S = (int)num_draws, R = (int)num_pred;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  if constexpr (kAdapt) {
+    return mq::launch_adapt(y, N, out, status, n_taxa, S, R, (int)adapt_rounds, seed, index_base, ppred, rec, adapt,
+                            index, counts, (hipStream_t)hip_stream);
+  } else {
+    const int tc = mq::tile_cols(S, R);
+    hipLaunchKernelGGL(mq::map_pred_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave), mq::lds_bytes(S, R, tc),
+                       (hipStream_t)hip_stream, y, N, out, status, n_taxa, S, R, tc, seed, index_base,
+                       mp::khat_threshold(S), ppred, rec, index, counts, 0, (double*)nullptr);
+    return check_launch("map_pred_kernel");
+  }
+}
+
+// mdfit_nuts_diag, _summary, _loo and _post: the checks on n_taxa and on the
+// options of the NUTS call, in their order.  needs_mode: the entry's message
+// for any other mode; ptrs: the required pointers are all there.  Returns as
+// check_is_args.
+int check_nuts_post_args(int64_t n_taxa, const mdfit_opts* opts, const char* needs_mode, bool ptrs) {
+  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
+  if (!opts) return set_err(MDFIT_E_ARG, "opts is required (the options of the NUTS call)");
+  if (opts->mode != MDFIT_MODE_NUTS) return set_err(MDFIT_E_ARG, needs_mode);
+  if (opts->num_samples < 2 || opts->num_samples > 4096)
+    return set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
+  if (n_taxa == 0) return 0;
+  if (!ptrs) return set_err(MDFIT_E_ARG, "null required pointer");
+  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  return 1;
+}
+
+}  // namespace
+
 extern "C" {
 
 #ifdef MDFIT_DEV_HPTIME
@@ -2109,144 +2226,75 @@ int mdfit_map_laplace_u(const uint32_t* y, const uint32_t* N, const double* out,
 int mdfit_map_psis(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
                    int32_t num_draws, uint64_t seed, int64_t index_base, double* psis, double* draws,
                    void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)  // (a five-draw tail; the LDS bound)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !psis) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  const int S = (int)num_draws;
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mp::map_psis_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
-                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), psis, draws, 0, (double*)nullptr);
-  return check_launch("map_psis_kernel");
+  return launch_map_psis<false>(y, N, out, status, n_taxa, num_draws, 0, seed, index_base, psis, nullptr, draws,
+                                hip_stream);
 }
 
 int mdfit_map_psis_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
                          int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
                          double* psis, double* adapt, double* draws, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
-    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !psis) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  const int S = (int)num_draws;
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mp::map_psis_kernel<true>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
-                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), psis, draws, (int)adapt_rounds, adapt);
-  return check_launch("map_psis_kernel<adapt>");
+  return launch_map_psis<true>(y, N, out, status, n_taxa, num_draws, adapt_rounds, seed, index_base, psis, adapt, draws,
+                               hip_stream);
 }
 
 int mdfit_map_waic(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
                    int32_t num_draws, uint64_t seed, int64_t index_base, double* waic, double* pointwise,
                    double* draws, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  namespace mw = mdfit::mapwaic;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !waic) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  const int S = (int)num_draws;
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mw::map_waic_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
-                     (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), waic, pointwise, draws, 0, (double*)nullptr);
-  return check_launch("map_waic_kernel");
+  return launch_map_waic<false>(y, N, out, status, n_taxa, num_draws, 0, seed, index_base, waic, nullptr, pointwise,
+                                draws, hip_stream);
 }
 
 int mdfit_map_waic_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
                          int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
                          double* waic, double* adapt, double* pointwise, double* draws, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  namespace mw = mdfit::mapwaic;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
-    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !waic) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  const int S = (int)num_draws;
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mw::map_waic_kernel<true>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
-                     (size_t)mw::lds_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), waic, pointwise, draws, (int)adapt_rounds, adapt);
-  return check_launch("map_waic_kernel<adapt>");
+  return launch_map_waic<true>(y, N, out, status, n_taxa, num_draws, adapt_rounds, seed, index_base, waic, adapt,
+                               pointwise, draws, hip_stream);
 }
 
 int mdfit_map_evidence(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
                        int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base, double* evid,
                        double* draws, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  namespace me = mdfit::mapevid;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !evid) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  const int S = (int)num_draws;
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(me::map_evidence_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
-                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), evid, draws, 0, (double*)nullptr);
-  return check_launch("map_evidence_kernel");
+  return launch_map_evidence<false>(y, N, out, status, n_taxa, num_draws, 0, seed, index_base, evid, nullptr, draws,
+                                    hip_stream);
 }
 
 int mdfit_map_evidence_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
                              int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed,
                              int64_t index_base, double* evid, double* adapt, double* draws, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  namespace me = mdfit::mapevid;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
-    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !evid) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  const int S = (int)num_draws;
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(me::map_evidence_kernel<true>, dim3((unsigned)n_taxa), dim3(mdfit::kWave),
-                     (size_t)mp::work_len(S) * sizeof(double), (hipStream_t)hip_stream, y, N, out, status, n_taxa, S,
-                     seed, index_base, mp::khat_threshold(S), evid, draws, (int)adapt_rounds, adapt);
-  return check_launch("map_evidence_kernel<adapt>");
+  return launch_map_evidence<true>(y, N, out, status, n_taxa, num_draws, adapt_rounds, seed, index_base, evid, adapt,
+                                   draws, hip_stream);
+}
+
+int mdfit_map_pred(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                   int32_t num_draws, int32_t num_pred, uint64_t seed, int64_t index_base, float* ppred, double* rec,
+                   int32_t* index, uint32_t* counts, void* hip_stream) {
+  return launch_map_pred<false>(y, N, out, status, n_taxa, num_draws, num_pred, 0, seed, index_base, ppred, rec,
+                                nullptr, index, counts, hip_stream);
+}
+
+int mdfit_map_pred_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                         int64_t n_taxa, int32_t num_draws, int32_t num_pred, int32_t adapt_rounds, uint64_t seed,
+                         int64_t index_base, float* ppred, double* rec, double* adapt, int32_t* index,
+                         uint32_t* counts, void* hip_stream) {
+  return launch_map_pred<true>(y, N, out, status, n_taxa, num_draws, num_pred, adapt_rounds, seed, index_base, ppred,
+                               rec, adapt, index, counts, hip_stream);
 }
 
 int mdfit_log_mean_weight(const double* lw, int64_t n_series, int32_t S, double* logz, double* se, double* khat,
                           void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
-  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
-  if (n_series == 0) return 0;
-  if (!lw || !logz || !se || !khat) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  const int rc = check_is_args(true, n_series, S, nullptr, nullptr, lw && logz && se && khat);
+  if (rc <= 0) return rc;
   mdfit::host::debug_poison((hipStream_t)hip_stream);
   hipLaunchKernelGGL(mdfit::mapevid::log_mean_weight_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
-                     (size_t)mp::work_len((int)S) * sizeof(double), (hipStream_t)hip_stream, lw, n_series, (int)S, logz,
-                     se, khat);
+                     (size_t)mdfit::mappsis::work_len((int)S) * sizeof(double), (hipStream_t)hip_stream, lw, n_series,
+                     (int)S, logz, se, khat);
   return check_launch("log_mean_weight_kernel");
 }
 
 int mdfit_adapt_proposal(const double* u, const double* w, const int32_t* mask, const int32_t* c_held, const double* K,
                          int64_t n_series, int32_t S, double* prop, int32_t* ok, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
-  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
-  if (n_series == 0) return 0;
-  if (!u || !w || !mask || !c_held || !K || !prop || !ok) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  const int rc = check_is_args(true, n_series, S, nullptr, nullptr, u && w && mask && c_held && K && prop && ok);
+  if (rc <= 0) return rc;
   mdfit::host::debug_poison((hipStream_t)hip_stream);
   hipLaunchKernelGGL(mdfit::mapadapt::adapt_proposal_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
                      (size_t)S * sizeof(double), (hipStream_t)hip_stream, u, w, mask, c_held, K, n_series, (int)S, prop,
@@ -2254,61 +2302,12 @@ int mdfit_adapt_proposal(const double* u, const double* w, const int32_t* mask, 
   return check_launch("adapt_proposal_kernel");
 }
 
-int mdfit_map_pred(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
-                   int32_t num_draws, int32_t num_pred, uint64_t seed, int64_t index_base, float* ppred, double* rec,
-                   int32_t* index, uint32_t* counts, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  namespace mq = mdfit::mappred;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (num_pred < mq::kMinPred || num_pred > mq::kMaxPred)
-    return set_err(MDFIT_E_ARG, "num_pred must be in [25, 1024]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !ppred || !rec) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  const int S = (int)num_draws, R = (int)num_pred;
-  const int tc = mq::tile_cols(S, R);
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mq::map_pred_kernel<false>, dim3((unsigned)n_taxa), dim3(mdfit::kWave), mq::lds_bytes(S, R, tc),
-                     (hipStream_t)hip_stream, y, N, out, status, n_taxa, S, R, tc, seed, index_base,
-                     mp::khat_threshold(S), ppred, rec, index, counts, 0, (double*)nullptr);
-  return check_launch("map_pred_kernel");
-}
-
-int mdfit_map_pred_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
-                         int64_t n_taxa, int32_t num_draws, int32_t num_pred, int32_t adapt_rounds, uint64_t seed,
-                         int64_t index_base, float* ppred, double* rec, double* adapt, int32_t* index,
-                         uint32_t* counts, void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  namespace mq = mdfit::mappred;
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (num_draws < mp::kMinDraws || num_draws > mp::kMaxDraws)
-    return set_err(MDFIT_E_ARG, "num_draws must be in [25, 1024]");
-  if (num_pred < mq::kMinPred || num_pred > mq::kMaxPred)
-    return set_err(MDFIT_E_ARG, "num_pred must be in [25, 1024]");
-  if (adapt_rounds < 0 || adapt_rounds > mdfit::mapadapt::kMaxRounds)
-    return set_err(MDFIT_E_ARG, "adapt_rounds must be in [0, 4]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !out || !status || !ppred || !rec) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
-  mdfit::host::debug_poison((hipStream_t)hip_stream);
-  return mq::launch_adapt(y, N, out, status, n_taxa, (int)num_draws, (int)num_pred, (int)adapt_rounds, seed,
-                          index_base, ppred, rec, adapt, index, counts, (hipStream_t)hip_stream);
-}
-
 int mdfit_resample(const double* w, int64_t n_series, int32_t S, int32_t R, int32_t* idx, int32_t* n_distinct,
                    void* hip_stream) {
-  namespace mp = mdfit::mappsis;
-  namespace mq = mdfit::mappred;
-  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
-  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
-  if (R < mq::kMinPred || R > mq::kMaxPred) return set_err(MDFIT_E_ARG, "R must be in [25, 1024]");
-  if (n_series == 0) return 0;
-  if (!w || !idx || !n_distinct) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  const int rc = check_is_args(true, n_series, S, &R, nullptr, w && idx && n_distinct);
+  if (rc <= 0) return rc;
   mdfit::host::debug_poison((hipStream_t)hip_stream);
-  hipLaunchKernelGGL(mq::resample_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
+  hipLaunchKernelGGL(mdfit::mappred::resample_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
                      (size_t)S * sizeof(double) + (size_t)R * sizeof(int), (hipStream_t)hip_stream, w, n_series,
                      (int)S, (int)R, idx, n_distinct);
   return check_launch("resample_kernel");
@@ -2340,11 +2339,8 @@ int mdfit_auto_route_pred(const int32_t* status, const double* psis, const doubl
 
 int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w, double* khat, void* hip_stream) {
   namespace mp = mdfit::mappsis;
-  if (n_series < 0) return set_err(MDFIT_E_ARG, "n_series < 0");
-  if (S < mp::kMinDraws || S > mp::kMaxDraws) return set_err(MDFIT_E_ARG, "S must be in [25, 1024]");
-  if (n_series == 0) return 0;
-  if (!lw || !w || !khat) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_series > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_series exceeds 2^25 per call");
+  const int rc = check_is_args(true, n_series, S, nullptr, nullptr, lw && w && khat);
+  if (rc <= 0) return rc;
   mdfit::host::debug_poison((hipStream_t)hip_stream);
   hipLaunchKernelGGL(mp::psis_weights_kernel, dim3((unsigned)n_series), dim3(mdfit::kWave),
                      (size_t)mp::work_len((int)S) * sizeof(double), (hipStream_t)hip_stream, lw, n_series, (int)S, w,
@@ -2368,55 +2364,34 @@ int mdfit_nuts_potential(const int32_t* model, const int32_t* subset, const uint
 
 int mdfit_nuts_diag(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts* opts, double* diag,
                     void* hip_stream) {
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (!opts) return set_err(MDFIT_E_ARG, "opts is required (the options of the NUTS call)");
-  if (opts->mode != MDFIT_MODE_NUTS) return set_err(MDFIT_E_ARG, "mdfit_nuts_diag needs opts->mode == MDFIT_MODE_NUTS");
-  if (opts->num_samples < 2 || opts->num_samples > 4096)
-    return set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
-  if (n_taxa == 0) return 0;
-  if (!workspace || !out || !diag) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int rc = check_nuts_post_args(n_taxa, opts, "mdfit_nuts_diag needs opts->mode == MDFIT_MODE_NUTS",
+                                      workspace && out && diag);
+  if (rc <= 0) return rc;
   return mdfit::nuts::diag(workspace, out, n_taxa, *opts, diag, (hipStream_t)hip_stream);
 }
 
 int mdfit_nuts_summary(const void* workspace, const double* out, int64_t n_taxa, const mdfit_opts* opts, double* summ,
                        void* hip_stream) {
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (!opts) return set_err(MDFIT_E_ARG, "opts is required (the options of the NUTS call)");
-  if (opts->mode != MDFIT_MODE_NUTS)
-    return set_err(MDFIT_E_ARG, "mdfit_nuts_summary needs opts->mode == MDFIT_MODE_NUTS");
-  if (opts->num_samples < 2 || opts->num_samples > 4096)
-    return set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
-  if (n_taxa == 0) return 0;
-  if (!workspace || !out || !summ) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int rc = check_nuts_post_args(n_taxa, opts, "mdfit_nuts_summary needs opts->mode == MDFIT_MODE_NUTS",
+                                      workspace && out && summ);
+  if (rc <= 0) return rc;
   return mdfit::nuts::summary(workspace, out, n_taxa, *opts, summ, (hipStream_t)hip_stream);
 }
 
 int mdfit_nuts_loo(const uint32_t* y, const uint32_t* N, const void* workspace, const double* out, int64_t n_taxa,
                    const mdfit_opts* opts, double* loo, double* pointwise, void* hip_stream) {
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (!opts) return set_err(MDFIT_E_ARG, "opts is required (the options of the NUTS call)");
-  if (opts->mode != MDFIT_MODE_NUTS) return set_err(MDFIT_E_ARG, "mdfit_nuts_loo needs opts->mode == MDFIT_MODE_NUTS");
-  if (opts->num_samples < 2 || opts->num_samples > 4096)
-    return set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !workspace || !out || !loo) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int rc = check_nuts_post_args(n_taxa, opts, "mdfit_nuts_loo needs opts->mode == MDFIT_MODE_NUTS",
+                                      y && N && workspace && out && loo);
+  if (rc <= 0) return rc;
   return mdfit::nuts::loo(y, N, workspace, out, n_taxa, *opts, loo, pointwise, (hipStream_t)hip_stream);
 }
 
 int mdfit_nuts_post(const uint32_t* y, const uint32_t* N, const uint32_t* mm, int64_t n_taxa, const mdfit_opts* opts,
                     const void* workspace, double* out, float* pred, int32_t* status, double* waic, uint32_t* counts,
                     uint8_t* count_flags, void* hip_stream) {
-  if (n_taxa < 0) return set_err(MDFIT_E_ARG, "n_taxa < 0");
-  if (!opts) return set_err(MDFIT_E_ARG, "opts is required (the options of the NUTS call)");
-  if (opts->mode != MDFIT_MODE_NUTS) return set_err(MDFIT_E_ARG, "mdfit_nuts_post needs opts->mode == MDFIT_MODE_NUTS");
-  if (opts->num_samples < 2 || opts->num_samples > 4096)
-    return set_err(MDFIT_E_ARG, "num_samples must be in [2, 4096]");
-  if (n_taxa == 0) return 0;
-  if (!y || !N || !workspace || !out || !status) return set_err(MDFIT_E_ARG, "null required pointer");
-  if (n_taxa > ((int64_t)1 << 25)) return set_err(MDFIT_E_ARG, "n_taxa exceeds 2^25 per call");
+  const int rc = check_nuts_post_args(n_taxa, opts, "mdfit_nuts_post needs opts->mode == MDFIT_MODE_NUTS",
+                                      y && N && workspace && out && status);
+  if (rc <= 0) return rc;
   return mdfit::nuts::post(y, N, mm, n_taxa, *opts, workspace, out, pred, status, waic, counts, count_flags,
                            (hipStream_t)hip_stream);
 }

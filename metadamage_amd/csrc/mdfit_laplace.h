@@ -160,6 +160,65 @@ MDFIT_LAP_FN void laplace4(const double H[10], unsigned free_mask, const double 
 #if defined(__HIPCC__)
 namespace mdfit {
 
+// The mode of one sub-fit and the objective's g and H there, in the row layout
+// of laplace_kernel below (lane = 16 row + k; rows 0-1 one all-position fit,
+// row 2 a forward, row 3 a reverse one): the one evaluation behind
+// mdfit_map_laplace and the proposals of the importance-sampled entries
+// (mdfit_mapis.h), so the mode, g, H and the free set are the same bits in all
+// of them.
+struct ModeEval {
+  double u[4];    // the mode in the unconstrained coordinates (logit q, logit A, c, log(phi - 2)), clamped
+  Theta th;       // the constrained parameters there
+  Eval e;         // g and H (the value and its rounding scale are not formed)
+  unsigned mask;  // bit j: coordinate j is free by the optimiser's own binding rule (eps = kEpsBind[j])
+};
+
+// dg: the sub-fit's diagnostic slot of the record, (q, A, c, phi).  kPmd: the
+// PMD objective; otherwise the null one, with A and c held (A = 0.5, c = 0).
+// Lane 0 of a row resolves logit q, lane 1 logit A, lane 2 log(phi - 2) (two
+// logarithms per lane instead of five), then the row shares them.
+template <bool kPmd>
+__device__ __forceinline__ void mode_eval(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN,
+                                          const double* __restrict__ dg, int64_t t, ModeEval& m) {
+  const int row = (int)threadIdx.x >> 4, k = (int)threadIdx.x & 15;
+  const double q = dg[0], A = kPmd ? dg[1] : 0.5, c = kPmd ? dg[2] : 0.0, phi = dg[3];
+  const double x = k == 0 ? q : (k == 1 ? A : phi - 2.0);
+  const double lx = flog(x), l1mx = flog1p(k < 2 ? -x : 0.0);
+  const double v = lx - l1mx;  // logit(x) on lanes 0, 1; log(x) on lane 2
+  m.u[0] = rowb<0>(v);
+  m.u[1] = rowb<1>(v);
+  m.u[2] = c;
+  m.u[3] = rowb<2>(v);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m.u[j] = clampd(m.u[j], kULo[j], kUHi[j]);
+
+  PointData pd;
+  pd.pmd = kPmd ? 1 : 0;
+  pd.valid = k < kNHalf;
+  pd.k = pd.valid ? k : 0;
+  const int col = pd.valid ? (row & 1) * kNHalf + k : 0;
+  pd.y = pd.valid ? (double)gy[t * kLD + col] : 0.0;
+  pd.N = pd.valid ? (double)gN[t * kLD + col] : 0.0;
+  m.th = make_theta<16>(kPmd, m.u);
+  double acc[kNAcc];
+#pragma unroll
+  for (int j = 0; j < kNAcc; ++j) acc[j] = 0.0;
+  point_accum<true>(pd, m.th, acc);
+#pragma unroll
+  for (int j = 2; j < kNAcc; ++j) {  // (not the value and its rounding scale: only g and H are used)
+    const double s16 = gsum<16>(acc[j]);
+    const double s32 = s16 + xrow(s16);  // the all-position fit: both halves
+    acc[j] = row < 2 ? s32 : s16;
+  }
+  acc[0] = acc[1] = 0.0;
+  finish_eval(kPmd, m.th, acc, m.e);
+  // held coordinates leave the system
+  bool fr[4];
+  double dbind[4];
+  free_set(kPmd, m.u, m.e.g, m.e.H, INFINITY, fr, dbind);
+  m.mask = (fr[0] ? 1u : 0u) | (fr[1] ? 2u : 0u) | (fr[2] ? 4u : 0u) | (fr[3] ? 8u : 0u);
+}
+
 // One wave per taxon; the three PMD sub-fits share it: rows 0-1 (lanes 0-31)
 // the all-position fit (diag sub-fit 0; row 0 z > 0, row 1 z < 0, summed as
 // objective_group<kAll> does), row 2 the forward fit (diag sub-fit 2), row 3
@@ -192,49 +251,13 @@ __global__ __launch_bounds__(64) void laplace_kernel(const uint32_t* __restrict_
     return;
   }
 
-  // the mode in the unconstrained coordinates, from the record's (q, A, c,
-  // phi): lane 0 of a row resolves logit q, lane 1 logit A, lane 2 log(phi - 2)
-  // (two logarithms per lane instead of five), then the row shares them
-  const double* dg = out + t * MDFIT_NOUT + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * (row < 2 ? 0 : row);
-  const double q = dg[0], A = dg[1], c = dg[2], phi = dg[3];
-  const double x = k == 0 ? q : (k == 1 ? A : phi - 2.0);
-  const double lx = flog(x), l1mx = flog1p(k < 2 ? -x : 0.0);
-  const double v = lx - l1mx;  // logit(x) on lanes 0, 1; log(x) on lane 2
-  double u[4] = {rowb<0>(v), rowb<1>(v), c, rowb<2>(v)};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) u[j] = clampd(u[j], kULo[j], kUHi[j]);
-
-  PointData pd;
-  pd.pmd = 1;
-  pd.valid = k < kNHalf;
-  pd.k = pd.valid ? k : 0;
-  const int col = pd.valid ? (row & 1) * kNHalf + k : 0;
-  pd.y = pd.valid ? (double)gy[t * kLD + col] : 0.0;
-  pd.N = pd.valid ? (double)gN[t * kLD + col] : 0.0;
-  const Theta th = make_theta<16>(true, u);
-  double acc[kNAcc];
-#pragma unroll
-  for (int j = 0; j < kNAcc; ++j) acc[j] = 0.0;
-  point_accum<true>(pd, th, acc);
-#pragma unroll
-  for (int j = 2; j < kNAcc; ++j) {  // (not the value and its rounding scale: only g and H are used)
-    const double s16 = gsum<16>(acc[j]);
-    const double s32 = s16 + xrow(s16);  // the all-position fit: both halves
-    acc[j] = row < 2 ? s32 : s16;
-  }
-  acc[0] = acc[1] = 0.0;
-  Eval e;
-  finish_eval(true, th, acc, e);
-
-  // the optimiser's own binding rule (eps = kEpsBind[j]): held coordinates
-  // leave the system
-  bool fr[4];
-  double dbind[4];
-  free_set(true, u, e.g, e.H, INFINITY, fr, dbind);
-  const unsigned mask = (fr[0] ? 1u : 0u) | (fr[1] ? 2u : 0u) | (fr[2] ? 4u : 0u) | (fr[3] ? 8u : 0u);
+  ModeEval me;
+  mode_eval<true>(gy, gN, out + t * MDFIT_NOUT + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * (row < 2 ? 0 : row), t, me);
+  const Theta& th = me.th;
+  const Eval& e = me.e;
   const double J[4] = {th.q * th.omq, th.JA, 1.0, th.delta};
   double rec[MDFIT_NLAPLACE];
-  laplace::laplace4(e.H, mask, J, th.A + th.c, rec);
+  laplace::laplace4(e.H, me.mask, J, th.A + th.c, rec);
 
   if (writer) {
     double* r = lap + (t * 3 + sub) * MDFIT_NLAPLACE;
@@ -242,7 +265,7 @@ __global__ __launch_bounds__(64) void laplace_kernel(const uint32_t* __restrict_
     for (int i = 0; i < MDFIT_NLAPLACE; ++i) r[i] = rec[i];
     if (uo != nullptr) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) uo[(t * 3 + sub) * 4 + j] = u[j];
+      for (int j = 0; j < 4; ++j) uo[(t * 3 + sub) * 4 + j] = me.u[j];
     }
     if (gh != nullptr) {
       double* o = gh + (t * 3 + sub) * 20;

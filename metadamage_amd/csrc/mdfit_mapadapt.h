@@ -8,16 +8,19 @@
 // sqrt(C_jj), the upper-triangular factor F of C_jm / (d_j d_m) = (F F')_jm and,
 // with c held on 0, the exponential's new rate 1 / sum w c_s.
 //
-// Written once over a `lanes` policy, as mdfit_mappsis.h: the kernels run it
-// with the 64 lanes of a wave; a plain C++ program (g++, no HIP) runs it with
-// the one-lane policy (tests/adapt_host_main.cpp).  Every sum is a per-lane
+// Written once over a `lanes` policy, as mdfit_mappsis.h: a plain C++ program
+// (g++, no HIP) runs it with the one-lane policy (tests/adapt_host_main.cpp).
+// This header has no device part.  What runs it with the 64 lanes of a wave
+// needs the core's wave policy and draw and lives in mdfit_mapis.h: StreamU and
+// next_proposal inside the rounds of subfit_weights, and mdfit_adapt_proposal's
+// one-wave kernel, mapadapt::adapt_proposal_kernel, at that header's end.  Every sum is a per-lane
 // strided partial sum in ascending draw index followed by the policy's
 // cross-lane reduction.
 #pragma once
 
 #include <cmath>
 
-#include "mdfit_mappsis.h"
+#include "mdfit_nutsloo.h"
 
 namespace mdfit::mapadapt {
 
@@ -27,7 +30,7 @@ constexpr unsigned kAdaptedBit = 64u;  // flags bit 6 of the psis and waic recor
 // the adapt record (MDFIT_NMAPADAPT = 4 doubles per PMD row)
 constexpr int kKhat0 = 0, kEss0 = 1, kBestRound = 2, kRoundsTried = 3;
 
-using mappsis::OneLane;
+using nutsloo::OneLane;
 
 // the refitted proposal: centre m (the residuals'), scale d, factor F[j][p]
 // (p >= j; held coordinates: the identity's rows and columns, d = 1, m = 0),
@@ -156,85 +159,6 @@ inline bool refit_host(const double* wt, int S, const double* u, unsigned mask, 
 
 }  // namespace mdfit::mapadapt
 
-#if defined(__HIPCC__)
-namespace mdfit::mapadapt {
-
-using mappsis::kNPar;
-using mappsis::kPCHeld;
-using mappsis::kPD;
-using mappsis::kPGc;
-using mappsis::kPK;
-using mappsis::kPM;
-using mappsis::kPMask;
-using mappsis::kPU;
-using mappsis::kPValid;
-using mappsis::PsisWave;
-using mappsis::Stream;
-
-// the kernels' draws for refit: u regenerated from the stream
-struct StreamU {
-  const double* P;
-  Stream st;
-  __device__ __forceinline__ void operator()(int t, double u[4]) const {
-    const mappsis::DrawU r = mappsis::psis_draw(P, st, t);
-    u[0] = r.u0;
-    u[1] = r.u1;
-    u[2] = r.u2;
-    u[3] = r.u3;
-  }
-};
-
-// Steps 2-4 in a kernel: from the best round's proposal P (LDS), weights wt
-// (LDS) and stream, the next round's proposal, written over P by lane 0 between
-// two barriers when the refit succeeds (P is untouched when it does not).  The
-// mask, the held set, K and the held coordinates' centre stay.
-__device__ __forceinline__ bool next_proposal(const double* wt, int S, double* P, Stream st) {
-  const unsigned mask = (unsigned)P[kPMask];
-  const bool cheld = P[kPCHeld] != 0.0;
-  Refit r;
-  const bool ok = refit(PsisWave{}, wt, S, StreamU{P, st}, mask, cheld, P + kPK, r);
-  __syncthreads();  // (every lane has drawn from P)
-  if (ok && threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if ((mask >> j) & 1u) P[kPU + j] = r.m[j];
-      P[kPD + j] = r.d[j];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) P[kPM + 4 * p + j] = r.F[j][p];
-    }
-    if (cheld) P[kPGc] = r.gc;
-  }
-  __syncthreads();
-  return ok;
-}
-
-// mdfit_adapt_proposal: one wave per series
-#ifndef MDFIT_NO_HELPER_KERNELS  // (a second unit of libmdfit.so includes this header for the templates alone)
-__global__ __launch_bounds__(64) void adapt_proposal_kernel(const double* __restrict__ u, const double* __restrict__ wt,
-                                                            const int32_t* __restrict__ mask,
-                                                            const int32_t* __restrict__ cheld,
-                                                            const double* __restrict__ K, int64_t n_series, int S,
-                                                            double* __restrict__ outp, int32_t* __restrict__ okp) {
-  extern __shared__ double s_w[];
-  const int64_t row = blockIdx.x;
-  if (row >= n_series) return;
-  for (int x = threadIdx.x; x < S; x += 64) s_w[x] = wt[row * (int64_t)S + x];
-  __syncthreads();
-  Refit r;
-  const bool ok = refit(PsisWave{}, s_w, S, ArrayDraws{u + row * (int64_t)S * 4}, (unsigned)mask[row] & 15u,
-                        cheld[row] != 0, K + row * 4, r);
-  if (threadIdx.x == 0) {
-    double* o = outp + row * 25;
-    for (int j = 0; j < 4; ++j) {
-      o[j] = ok ? r.m[j] : NAN;
-      o[4 + j] = ok ? r.d[j] : NAN;
-      for (int p = 0; p < 4; ++p) o[8 + 4 * j + p] = ok ? r.F[j][p] : NAN;
-    }
-    o[24] = ok ? r.gc : NAN;
-    okp[row] = ok ? 1 : 0;
-  }
-}
-#endif  // MDFIT_NO_HELPER_KERNELS
-
-}  // namespace mdfit::mapadapt
-#endif  // __HIPCC__
+// (the proposal that is refitted and the bounds on S; behind the definitions above, which the HIP part of that
+// header stands on through mdfit_mapis.h)
+#include "mdfit_mappsis.h"

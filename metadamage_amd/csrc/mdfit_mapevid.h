@@ -161,23 +161,21 @@ inline bool log_mean_weight_host(double* work, int S, double* logz, double* se, 
 }  // namespace mdfit::mapevid
 
 #if defined(__HIPCC__)
+#include "mdfit_mapis.h"  // (the importance sampler's device core)
+
 namespace mdfit::mapevid {
 
-using mappsis::kNPar;
-using mappsis::kPValid;
-using mappsis::PsisWave;
-using mappsis::Stream;
+using namespace mapis;
 
 // One wave per taxon, its six sub-fits one after another in diagnostic-slot
-// order.  Phases 1-3 are map_waic_kernel's: mapwaic::proposals<true> and
-// <false>, then per sub-fit mapwaic::subfit_weights (the draws, the raw
-// log-weights, psis_weights and, with kAdapt, the PMD rows' rounds), so khat,
-// ess, n_infeasible, the flags, the adapt record and the draws are its bits.
-// Phase 4: lane 0 forms K_prior - K_prop from the proposal of the round whose
-// weights stand in LDS, evidence_row the record; lane 0 then forms row 6 from
-// the six rows' log Z and se in s_ev.  No pointwise tile: dynamic LDS is
-// mappsis::work_len(S) doubles (22,016 B at S = 1024, 6,656 B at S = 256);
-// static: 2,144 B.  Reads y, N, out and status only.
+// order.  Phases 1-3 are the core's (mdfit_mapis.h), called as map_waic_kernel
+// calls them: proposals<true> and <false>, then per sub-fit subfit_weights (the
+// draws, the raw log-weights, psis_weights and, with kAdapt, the PMD rows'
+// rounds).  Phase 4: lane 0 forms K_prior - K_prop from the proposal of the
+// round whose weights stand in LDS, evidence_row the record; lane 0 then forms
+// row 6 from the six rows' log Z and se in s_ev.  No pointwise tile: dynamic
+// LDS is mappsis::work_len(S) doubles (22,016 B at S = 1024, 6,656 B at
+// S = 256); static: 2,144 B.  Reads y, N, out and status only.
 template <bool kAdapt>
 __global__ __launch_bounds__(64) void map_evidence_kernel(const uint32_t* __restrict__ gy,
                                                           const uint32_t* __restrict__ gN,
@@ -198,20 +196,14 @@ __global__ __launch_bounds__(64) void map_evidence_kernel(const uint32_t* __rest
 
   if (status[t] != MDFIT_OK) {  // wave-uniform: NaN statistics, flags 0
     if (lane < MDFIT_NSUBFIT + 1) invalid_row(rec + lane * MDFIT_NMAPEVID, 0u);
-    if (dr0 != nullptr)
-      for (int64_t i = lane; i < (int64_t)MDFIT_NSUBFIT * S * 6; i += 64) dr0[i] = NAN;
-    if constexpr (kAdapt)
-      if (adapt != nullptr && lane < 12) adapt[t * 12 + lane] = NAN;
+    bad_status_fills<kAdapt>(dr0, (int64_t)MDFIT_NSUBFIT * S * 6, adapt, t);
     return;
   }
-  if (lane < kLD) {
-    s_y[lane] = (double)gy[t * kLD + lane];
-    s_N[lane] = (double)gN[t * kLD + lane];
-  }
+  load_counts(gy, gN, t, s_y, s_N);
 
   // ---- phase 1: the modes, g and H there, the held sets ----
-  mapwaic::proposals<true>(gy, gN, out, t, s_par);
-  mapwaic::proposals<false>(gy, gN, out, t, s_par);
+  proposals<true>(gy, gN, out, t, s_par);
+  proposals<false>(gy, gN, out, t, s_par);
   __syncthreads();
 
   const PsisWave w;
@@ -225,27 +217,16 @@ __global__ __launch_bounds__(64) void map_evidence_kernel(const uint32_t* __rest
     const unsigned mask = (unsigned)P[kPMask];
     double* dr = dr0 != nullptr ? dr0 + (int64_t)s * S * 6 : nullptr;
     bool ok = P[kPValid] != 0.0;  // (wave-uniform)
+    const int arow = s == 0 ? 0 : s - 1;  // a PMD sub-fit's row of the adapt record
     if (ok) {
-      Stream st;
-      st.k0 = (uint32_t)seed;
-      st.k1 = (uint32_t)(seed >> 32);
-      st.c0 = (uint32_t)gtaxon;
-      st.c1 = (uint32_t)(gtaxon >> 32) + ((uint32_t)s << 24);  // the chain's sub-fit index
+      const Stream st = subfit_stream(seed, gtaxon, s);
       // ---- phases 2-3: the draws, the smoothed weights, the rounds ----
-      const mapwaic::SubfitWeights sw = mapwaic::subfit_weights<kAdapt, false>(
-          w, pmd, lo, hi, s_par[s], st, S, tau, adapt_rounds, s_y, s_N, s_w, nullptr, dr);
+      const SubfitWeights sw = subfit_weights<kAdapt, false>(w, pmd, lo, hi, s_par[s], st, S, tau, adapt_rounds, s_y,
+                                                             s_N, s_w, nullptr, dr);
       ok = sw.ok;
-      if constexpr (kAdapt) {
-        if (pmd && adapt != nullptr && lane == 0) {
-          double* ar = adapt + (t * 3 + (s == 0 ? 0 : s - 1)) * 4;
-          ar[mapadapt::kKhat0] = sw.k0;
-          ar[mapadapt::kEss0] = sw.ess0;
-          ar[mapadapt::kBestRound] = ok ? (double)sw.best : NAN;
-          ar[mapadapt::kRoundsTried] = ok ? (double)sw.tried : NAN;
-        }
-      }
-      if (dr != nullptr)
-        for (int i = lane; i < S; i += 64) dr[i * 6 + 5] = ok ? s_w[i] : NAN;
+      if constexpr (kAdapt)
+        if (pmd) adapt_row(adapt, t, arow, sw);
+      draws_weights(dr, s_w, S, ok);
       if (ok) {
         // ---- phase 4: the constants of the round in LDS, the row ----
         double K = 0.0;
@@ -265,10 +246,10 @@ __global__ __launch_bounds__(64) void map_evidence_kernel(const uint32_t* __rest
         all_rel = all_rel && sw.khat <= tau;
       }
     } else if (dr != nullptr) {
-      for (int i = lane; i < S * 6; i += 64) dr[i] = NAN;
+      nan_fill(dr, (int64_t)S * 6);
     }
     if constexpr (kAdapt)
-      if (!ok && pmd && adapt != nullptr && lane < 4) adapt[(t * 3 + (s == 0 ? 0 : s - 1)) * 4 + lane] = NAN;
+      if (!ok && pmd) adapt_row_nan(adapt, t, arow);
     if (!ok) {
       all_ok = false;
       if (lane == 0) {

@@ -2,7 +2,7 @@
 // reference's posterior predictive D_max columns and fit_predictions frame
 // (fits.py:89-120) of a MAP fit from importance-weighted draws.  Each PMD
 // sub-fit is importance-sampled exactly as mdfit_mappsis.h does it (the same
-// device functions, so the same bits); its smoothed weights are resampled to R
+// functions, mdfit_mapis.h, so the same bits); its smoothed weights are resampled to R
 // equally weighted draws by midpoint systematic resampling (no random number),
 // and draw r of each of the sampler's 32 predictive jobs is the oracle's
 // predictive_obs on theta of importance draw s(r), in the sampler's predictive
@@ -164,18 +164,14 @@ inline int tile_cols(int S, int R) {
 }  // namespace mdfit::mappred
 
 #if defined(__HIPCC__)
-#include "mdfit_mapwaic.h"
+#include "mdfit_mapis.h"  // (the importance sampler's device core)
 
 namespace mdfit::mappred {
 
-using mappsis::DrawU;
-using mappsis::kNPar;
-using mappsis::kPValid;
-using mappsis::Stream;
-using mappsis::ThetaD;
+using namespace mapis;
 
-// the 64 lanes of a wave: mappsis::PsisWave and the (width, index) reduction
-struct PredWave : mappsis::PsisWave {
+// the 64 lanes of a wave: PsisWave and the (width, index) reduction
+struct PredWave : PsisWave {
   __device__ __forceinline__ void argmin(double& wd, int& i) const {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -205,18 +201,18 @@ struct Draw {
       uh = false;
       return uc;
     }
-    const uint4 o = mappsis::philox(st.k0, st.k1, st.c0, st.c1, w2, w3++);
-    uc = mappsis::u53(o.z, o.w);
+    const uint4 o = philox(st.k0, st.k1, st.c0, st.c1, w2, w3++);
+    uc = u53(o.z, o.w);
     uh = true;
-    return mappsis::u53(o.x, o.y);
+    return u53(o.x, o.y);
   }
   __device__ __forceinline__ double nrm() {
     if (nh) {
       nh = false;
       return nc;
     }
-    const uint4 o = mappsis::philox(st.k0, st.k1, st.c0, st.c1, w2, w3++);
-    const double u1 = 1.0 - mappsis::u53(o.x, o.y), u2 = mappsis::u53(o.z, o.w);
+    const uint4 o = philox(st.k0, st.k1, st.c0, st.c1, w2, w3++);
+    const double u1 = 1.0 - u53(o.x, o.y), u2 = u53(o.z, o.w);
     double sn, cs;
     sincos(6.283185307179586 * u2, &sn, &cs);
     const double r = sqrt(-2.0 * flog(u1));
@@ -307,26 +303,20 @@ __device__ __forceinline__ int64_t predictive_count(Stream st, int r, int col, i
   return (obs >= 0.0 && obs <= Nn) ? (int64_t)obs : -1;
 }
 
-// One wave per taxon, its three PMD sub-fits one after another.  Phase 1 is
-// mapwaic::proposals<true> (map_psis_kernel's statements, so its bits).  Per
-// row: phase 2 -- lanes over draws, the raw log-weight into LDS
-// (map_psis_kernel's statements); phase 3 -- psis_weights, then ess by
-// psis_estimates' sum; phase 4 -- resample: the cumulative weights over the
-// weights, the index behind them; phase 5 -- lanes over the R predictive
-// draws, theta of draw idx[r] regenerated from the stream (psis_draw,
-// psis_theta: phase 2's bits) once per tile of tc columns of row 0, or for the
-// one column of rows 1 and 2, the counts into the tile behind the index;
-// phase 6 -- sort_counts and median_hpdi_counts per column.  Dynamic LDS:
-// lds_bytes(S, R, tc); static: 2,400 B.  Reads y, N, out and status only.
-//
-// kAdapt (mdfit_map_pred_adapt, MDFIT-AUTO v1.1): per row,
-// phases 2-3 run in map_psis_kernel<true>'s rounds, statement for statement, on
-// s_par[slot] (the by-slot layout map_waic_kernel<true> adapts in), so khat,
-// ess, the valid / reliable bits and the adapt record are mdfit_map_psis_adapt's
-// bits.  After the loop the best round's proposal is in s_par[slot] and its
-// weights are in the work buffer: phases 4-6 run unchanged and draw from the
-// best proposal.  The refit reads the weights s_w[0..S) and the proposal alone,
-// so no LDS is added.  adapt: [T][3][4], optional.
+// One wave per taxon, its three PMD sub-fits one after another.  Phases 1-3
+// are the core's (mdfit_mapis.h): proposals<true>, then per row subfit_weights
+// -- the draws, the raw log-weights, psis_weights (with kAdapt,
+// mdfit_map_pred_adapt, MDFIT-AUTO v1.1, DESIGN.md §3.13, in the rounds of
+// MDFIT-ADAPT v1: afterwards the best round's proposal is in s_par[slot] and its
+// weights are in the work buffer, so the phases below run unchanged and draw
+// from the best proposal) -- then ess by psis_estimates' sum.  Phase 4 --
+// resample: the cumulative weights over the weights, the index behind them;
+// phase 5 -- lanes over the R predictive draws, theta of draw idx[r]
+// regenerated from the stream (psis_draw, psis_theta: phase 2's bits) once per
+// tile of tc columns of row 0, or for the one column of rows 1 and 2, the
+// counts into the tile behind the index; phase 6 -- sort_counts and
+// median_hpdi_counts per column.  Dynamic LDS: lds_bytes(S, R, tc); static:
+// 2,400 B.  Reads y, N, out and status only.  adapt: [T][3][4], optional.
 template <bool kAdapt>
 __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict__ gy,
                                                       const uint32_t* __restrict__ gN,
@@ -359,17 +349,13 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
     if (lane < MDFIT_NMAPPRED) rec[lane] = lane == kFlags ? 0.0 : NAN;
     if (pp != nullptr)
       for (int x = lane; x < MDFIT_NPRED * kNPos; x += 64) pp[x] = NAN;
-    if constexpr (kAdapt)
-      if (adapt != nullptr && lane < 12) adapt[t * 12 + lane] = NAN;
+    bad_status_fills<kAdapt>(nullptr, 0, adapt, t);
     return;
   }
-  if (lane < kLD) {
-    s_y[lane] = (double)gy[t * kLD + lane];
-    s_N[lane] = (double)gN[t * kLD + lane];
-  }
+  load_counts(gy, gN, t, s_y, s_N);
 
   // ---- phase 1: the modes, g and H there, the held sets ----
-  mapwaic::proposals<true>(gy, gN, out, t, s_par);
+  proposals<true>(gy, gN, out, t, s_par);
   __syncthreads();
 
   const PredWave w;
@@ -386,73 +372,16 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
     bool ok = P[kPValid] != 0.0;  // (wave-uniform)
     double khat = NAN, ess = NAN, nd = NAN;
     if (ok) {
-      Stream st;
-      st.k0 = (uint32_t)seed;
-      st.k1 = (uint32_t)(seed >> 32);
-      st.c0 = (uint32_t)gtaxon;
-      st.c1 = (uint32_t)(gtaxon >> 32) + ((uint32_t)slot << 24);
+      const Stream st = subfit_stream(seed, gtaxon, slot);
       const int lo = row == 2 ? kNHalf : 0, hi = row == 1 ? kNHalf : kNPos;
-      // the rounds of MDFIT-ADAPT v1 (one pass without kAdapt): a round's proposal is written over the best one
-      // in s_par[slot], which lane j < 32 keeps word j of in `keep` and puts back when the round is dropped
-      double n_inf;
-      double k0 = NAN, ess0 = NAN, k_best = NAN, keep = 0.0;
-      int best = 0, tried = 0;
-      bool rerun = false;
-      for (int rnd = 0;;) {
-        // ---- phase 2: lanes over draws ----
-        for (int i = lane; i < S; i += 64) {
-          const DrawU r = mappsis::psis_draw(P, st, i);
-          const ThetaD th = mappsis::psis_theta(r);
-          double lw = -INFINITY;
-          if (th.feasible) {
-            const double ph = th.delta + 2.0;
-            double ll = 0.0;
-#pragma unroll 1
-            for (int col = lo; col < hi; ++col) {
-              const int kk = col < kNHalf ? col : col - kNHalf;
-              const double D = fma(th.A, powk(th.omq, kk), th.c);
-              ll += bb_logpmf(s_y[col], s_N[col], D, ph);
-            }
-            lw = (ll + th.lj) - r.lg;
-          }
-          s_w[i] = lw;
-        }
-        // ---- phase 3: the smoothed weights, their ess ----
-        ok = mappsis::psis_weights(w, s_w, S, khat, n_inf);
-        if constexpr (!kAdapt) {
-          break;
-        } else {
-          if (rerun) break;  // (the best round's weights are back in s_w, khat its own)
-          if (rnd == 0) {
-            if (!ok) break;
-            k0 = khat;
-            ess0 = mapadapt::weights_ess(w, s_w, S);
-          } else {
-            tried = rnd;
-            if (!(ok && isfinite(khat) && khat < k_best)) {  // 6. the round is dropped: the best one once more
-              if (lane < kNPar) s_par[slot][lane] = keep;
-              __syncthreads();
-              rerun = true;
-              continue;
-            }
-            best = rnd;
-          }
-          k_best = khat;
-          if (rnd == adapt_rounds || k_best <= tau) break;                // 1. the stop test
-          if (lane < kNPar) keep = s_par[slot][lane];
-          if (!mapadapt::next_proposal(s_w, S, s_par[slot], st)) break;  // 2-4. the refitted proposal, in place
-          ++rnd;
-        }
-      }
+      // ---- phases 2-3: the draws, the smoothed weights, the rounds ----
+      const SubfitWeights sw = subfit_weights<kAdapt, false>(w, true, lo, hi, s_par[slot], st, S, tau, adapt_rounds,
+                                                             s_y, s_N, s_w, nullptr, nullptr);
+      ok = sw.ok;
+      khat = sw.khat;
       if constexpr (kAdapt) {
-        adapted = adapted || (ok && best > 0);
-        if (adapt != nullptr && lane == 0) {
-          double* ar = adapt + (t * 3 + row) * 4;
-          ar[mapadapt::kKhat0] = k0;
-          ar[mapadapt::kEss0] = ess0;
-          ar[mapadapt::kBestRound] = ok ? (double)best : NAN;
-          ar[mapadapt::kRoundsTried] = ok ? (double)tried : NAN;
-        }
+        adapted = adapted || (ok && sw.best > 0);
+        adapt_row(adapt, t, row, sw);
       }
       if (ok) {
         double s2 = 0.0;
@@ -473,7 +402,7 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
           const int nc = ncols - c0 < tc ? ncols - c0 : tc;
           unsigned badm = 0u;
           for (int r = lane; r < R; r += 64) {
-            const ThetaD th = mappsis::psis_theta(mappsis::psis_draw(P, st, s_idx[r]));
+            const ThetaD th = psis_theta(psis_draw(P, st, s_idx[r]));
             const double phi = th.delta + 2.0;
 #pragma unroll 1
             for (int j = 0; j < nc; ++j) {
@@ -514,7 +443,7 @@ __global__ __launch_bounds__(64) void map_pred_kernel(const uint32_t* __restrict
       }
     }
     if constexpr (kAdapt)
-      if (P[kPValid] == 0.0 && adapt != nullptr && lane < 4) adapt[(t * 3 + row) * 4 + lane] = NAN;
+      if (P[kPValid] == 0.0) adapt_row_nan(adapt, t, row);
     if (lane == 0) {
       s_row[row][0] = khat;
       s_row[row][1] = ess;

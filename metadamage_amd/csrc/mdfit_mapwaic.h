@@ -2,7 +2,7 @@
 // reference's WAIC comparisons (n_sigma, n_sigma_forward, n_sigma_reverse,
 // asymmetry; fits.py:147-227) of a MAP fit from importance-weighted draws.  The
 // three PMD sub-fits are importance-sampled exactly as mdfit_mappsis.h does it
-// (the same device functions, so the same bits); the three null sub-fits get a
+// (the same functions, mdfit_mapis.h, so the same bits); the three null sub-fits get a
 // bivariate Student-t (nu = 4) proposal on (logit q, log delta) from one
 // evaluation of the fit kernel's null objective at their mode.  Per sub-fit the
 // Pareto-smoothed, normalised weights w_s and the pointwise log-pmf l_si give
@@ -190,66 +190,11 @@ inline double waic_row_host(const double* lppd, const double* p, int n, const do
 }  // namespace mdfit::mapwaic
 
 #if defined(__HIPCC__)
+#include "mdfit_mapis.h"  // (the importance sampler's device core)
+
 namespace mdfit::mapwaic {
 
-using mappsis::DrawU;
-using mappsis::kNPar;
-using mappsis::kPCHeld;
-using mappsis::kPD;
-using mappsis::kPGc;
-using mappsis::kPK;
-using mappsis::kPM;
-using mappsis::kPMask;
-using mappsis::kPU;
-using mappsis::kPValid;
-using mappsis::PsisWave;
-using mappsis::Stream;
-using mappsis::ThetaD;
-
-// the constrained parameters of a null draw and log prior(q, delta) + log[q(1-q) delta]
-// (A = c = 0; every draw is feasible)
-__device__ __noinline__ ThetaD null_theta(DrawU r) {
-#pragma clang fp contract(off)
-  ThetaD th;
-  double lq, l1mq;
-  logit_parts(r.u0, th.q, th.omq, lq, l1mq);
-  th.A = 0.0;
-  th.c = 0.0;
-  th.delta = exp(r.u3);
-  th.feasible = true;
-  // Beta(2, 3) on q, Exponential(1000) on delta (§3.1), then the Jacobian
-  th.lj = (2.0 * lq + 3.0 * l1mq) - th.delta / 1000.0 + r.u3;
-  return th;
-}
-
-// a draw ready for its points: D(k) = fma(A, w^k, c) -- a null draw has A = 0,
-// w = 1 and c = q, so D = q exactly
-struct DrawPt {
-  double A, w, c, ph, lj;
-  bool feasible;
-};
-
-__device__ __forceinline__ DrawPt draw_point(bool pmd, DrawU r) {
-  DrawPt d;
-  if (pmd) {
-    const ThetaD th = mappsis::psis_theta(r);
-    d.A = th.A;
-    d.w = th.omq;
-    d.c = th.c;
-    d.ph = th.delta + 2.0;
-    d.lj = th.lj;
-    d.feasible = th.feasible;
-  } else {
-    const ThetaD th = null_theta(r);
-    d.A = 0.0;
-    d.w = 1.0;
-    d.c = th.q;
-    d.ph = th.delta + 2.0;
-    d.lj = th.lj;
-    d.feasible = true;
-  }
-  return d;
-}
+using namespace mapis;
 
 // the kernel's draws for waic_points: regenerated from the stream; column lo +
 // c of the counts in LDS is point c of the sub-fit
@@ -259,7 +204,7 @@ struct StreamSource {
   bool pmd;
   int lo;
   const double *s_y, *s_N;
-  __device__ __forceinline__ DrawPt draw(int t) const { return draw_point(pmd, mappsis::psis_draw(P, st, t)); }
+  __device__ __forceinline__ DrawPt draw(int t) const { return draw_point(pmd, psis_draw(P, st, t)); }
   __device__ __forceinline__ void fill(const DrawPt& d, int c0, int nc, double* dst, int ld) const {
 #pragma unroll 1
     for (int c = 0; c < nc; ++c) {
@@ -271,220 +216,19 @@ struct StreamSource {
   }
 };
 
-// Phase 1 of map_psis_kernel (laplace_kernel's evaluation in its row layout),
-// for the PMD sub-fits (kPmd: rows 0-1 diag slot 0, row 2 slot 2, row 3 slot 3;
-// map_psis_kernel's statements, so its bits) or the null ones (slots 1, 4, 5:
-// the fit kernel's null objective, the binding rule on q and delta alone, the
-// 2x2 factorisation through the same 4x4 routines with A and c held).  The
-// writer lane of each sub-fit leaves the proposal in s_par[slot].
-template <bool kPmd>
-__device__ __forceinline__ void proposals(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN,
-                                          const double* __restrict__ out, int64_t t, double (*s_par)[kNPar]) {
-  const int lane = threadIdx.x;
-  const int row = lane >> 4, k = lane & 15;
-  const int slot = kPmd ? (row < 2 ? 0 : row) : (row < 2 ? 1 : row + 2);
-  const bool writer = k == 0 && row != 1;
-  const double* dg = out + t * MDFIT_NOUT + MDFIT_F_DIAG + MDFIT_DIAG_STRIDE * slot;
-  const double q = dg[0], A = kPmd ? dg[1] : 0.5, c = kPmd ? dg[2] : 0.0, phi = dg[3];
-  const double x = k == 0 ? q : (k == 1 ? A : phi - 2.0);
-  const double lx = flog(x), l1mx = flog1p(k < 2 ? -x : 0.0);
-  const double v = lx - l1mx;
-  double u[4] = {rowb<0>(v), rowb<1>(v), c, rowb<2>(v)};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) u[j] = clampd(u[j], kULo[j], kUHi[j]);
-  PointData pd;
-  pd.pmd = kPmd ? 1 : 0;
-  pd.valid = k < kNHalf;
-  pd.k = pd.valid ? k : 0;
-  const int col = pd.valid ? (row & 1) * kNHalf + k : 0;
-  pd.y = pd.valid ? (double)gy[t * kLD + col] : 0.0;
-  pd.N = pd.valid ? (double)gN[t * kLD + col] : 0.0;
-  const Theta th = make_theta<16>(kPmd, u);
-  double acc[mdfit::kNAcc];
-#pragma unroll
-  for (int j = 0; j < mdfit::kNAcc; ++j) acc[j] = 0.0;
-  point_accum<true>(pd, th, acc);
-#pragma unroll
-  for (int j = 2; j < mdfit::kNAcc; ++j) {
-    const double s16 = gsum<16>(acc[j]);
-    const double s32 = s16 + xrow(s16);
-    acc[j] = row < 2 ? s32 : s16;
-  }
-  acc[0] = acc[1] = 0.0;
-  Eval e;
-  finish_eval(kPmd, th, acc, e);
-  bool fr[4];
-  double dbind[4];
-  free_set(kPmd, u, e.g, e.H, INFINITY, fr, dbind);
-  const unsigned mask = (fr[0] ? 1u : 0u) | (fr[1] ? 2u : 0u) | (fr[2] ? 4u : 0u) | (fr[3] ? 8u : 0u);
-  double C[4][4];
-  const bool lap_ok = laplace::free_covariance(e.H, mask, C);
-  double d[4], M[4][4];
-  mappsis::scaled_factor(e.H, mask, d, M);
-  // supported: PMD -- q, A and phi free, c free or held on its lower bound;
-  // null -- q and delta free
-  const bool cheld = kPmd && !fr[2];
-  const bool c_low = u[2] - kULo[2] <= kEpsBind[2];
-  const bool ok = lap_ok && fr[0] && (!kPmd || fr[1]) && fr[3] && (!cheld || c_low);
-  if (writer) {
-    double* P = s_par[slot];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      P[kPU + j] = u[j];
-      P[kPD + j] = d[j];
-      // the free block's centre moves with a held c: -C_ff H_fc
-      double kj = 0.0;
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-        if (m != 2) kj -= C[j][m] * e.H[m < 2 ? hidx(m, 2) : hidx(2, m)];
-      P[kPK + j] = (cheld && j != 2) ? kj : 0.0;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) P[kPM + 4 * j + m] = M[j][m];
-    }
-    P[kPGc] = e.g[2];
-    P[kPMask] = (double)mask;
-    P[kPValid] = ok ? 1.0 : 0.0;
-    P[kPCHeld] = cheld ? 1.0 : 0.0;
-  }
-}
-
-// What phases 2-3 leave of one sub-fit: ok, khat and n_inf are psis_weights'
-// of the pass whose weights stand in s_w (the best round's), shift and total
-// its level (psis_weights_level); k0, ess0, best and tried the adapt record.
-struct SubfitWeights {
-  bool ok;
-  double khat, n_inf, shift, total, k0, ess0;
-  int best, tried;
-};
-
-// Phases 2-3 of one sub-fit whose proposal P = s_par[s] is valid, shared by
-// map_waic_kernel and map_evidence_kernel (mdfit_mapevid.h).  Phase 2 -- lanes
-// over draws, the raw log-weight into s_w (map_psis_kernel's statements for a
-// PMD row), u and the log-weight into dr when it is given; with kShift the
-// log-pmf at the proposal's centre into s_l0 (waic_points' shift).  Phase 3 --
-// psis_weights.  kAdapt: the rounds of MDFIT-ADAPT v1 for a PMD row (one pass
-// otherwise): a round's proposal is written over the best one in P, which lane
-// j < 32 keeps word j of in `keep` and puts back when the round is dropped.
-template <bool kAdapt, bool kShift>
-__device__ __forceinline__ SubfitWeights subfit_weights(const PsisWave& w, bool pmd, int lo, int hi, double* P,
-                                                        Stream st, int S, double tau, int adapt_rounds,
-                                                        const double* s_y, const double* s_N, double* s_w,
-                                                        double* s_l0, double* dr) {
-  const int lane = threadIdx.x;
-  const int n = hi - lo;
-  bool ok;
-  double khat, n_inf, shift, total;
-  double k0 = NAN, ess0 = NAN, k_best = NAN, keep = 0.0;
-  int best = 0, tried = 0;
-  bool rerun = false;
-  for (int rnd = 0;;) {
-    // ---- phase 2: lanes over draws ----
-    for (int i = lane; i < S; i += 64) {
-      const DrawU r = mappsis::psis_draw(P, st, i);
-      double lw = -INFINITY;
-      if (pmd) {
-        const ThetaD th = mappsis::psis_theta(r);
-        if (th.feasible) {
-          const double ph = th.delta + 2.0;
-          double ll = 0.0;
-#pragma unroll 1
-          for (int col = lo; col < hi; ++col) {
-            const int kk = col < kNHalf ? col : col - kNHalf;
-            const double D = fma(th.A, powk(th.omq, kk), th.c);
-            ll += bb_logpmf(s_y[col], s_N[col], D, ph);
-          }
-          lw = (ll + th.lj) - r.lg;
-        }
-      } else {
-        const ThetaD th = null_theta(r);
-        const double ph = th.delta + 2.0;
-        double ll = 0.0;
-#pragma unroll 1
-        for (int col = lo; col < hi; ++col) ll += bb_logpmf(s_y[col], s_N[col], th.q, ph);
-        lw = (ll + th.lj) - r.lg;
-      }
-      s_w[i] = lw;
-      if (dr != nullptr) {
-        dr[i * 6 + 0] = r.u0;
-        dr[i * 6 + 1] = r.u1;
-        dr[i * 6 + 2] = r.u2;
-        dr[i * 6 + 3] = r.u3;
-        dr[i * 6 + 4] = lw;
-      }
-    }
-    if constexpr (kShift) {
-      // the shift of the second moments: the log-pmf at the mode (lanes over points)
-      if (lane < n) {
-        DrawU m;
-        m.u0 = P[kPU + 0];
-        m.u1 = P[kPU + 1];
-        m.u2 = P[kPU + 2];
-        m.u3 = P[kPU + 3];
-        m.lg = 0.0;
-        const DrawPt d = draw_point(pmd, m);
-        const int col = lo + lane;
-        const int kk = col < kNHalf ? col : col - kNHalf;
-        const double l = bb_logpmf(s_y[col], s_N[col], fma(d.A, powk(d.w, kk), d.c), d.ph);
-        s_l0[lane] = isfinite(l) ? l : 0.0;
-      }
-    }
-    // ---- phase 3: the smoothed weights ----
-    ok = mappsis::psis_weights_level(w, s_w, S, khat, n_inf, shift, total);
-    if constexpr (!kAdapt) {
-      break;
-    } else {
-      if (!pmd || rerun) break;  // (rerun: the best round's weights are back in s_w, khat and n_inf its own)
-      if (rnd == 0) {
-        if (!ok) break;
-        k0 = khat;
-        ess0 = mapadapt::weights_ess(w, s_w, S);
-      } else {
-        tried = rnd;
-        if (!(ok && isfinite(khat) && khat < k_best)) {  // 6. the round is dropped: the best one once more
-          if (lane < kNPar) P[lane] = keep;
-          __syncthreads();
-          rerun = true;
-          continue;
-        }
-        best = rnd;
-      }
-      k_best = khat;
-      if (rnd == adapt_rounds || k_best <= tau) break;      // 1. the stop test
-      if (lane < kNPar) keep = P[lane];
-      if (!mapadapt::next_proposal(s_w, S, P, st)) break;  // 2-4. the refitted proposal, in place
-      ++rnd;
-    }
-  }
-  SubfitWeights r;
-  r.ok = ok;
-  r.khat = khat;
-  r.n_inf = n_inf;
-  r.shift = shift;
-  r.total = total;
-  r.k0 = k0;
-  r.ess0 = ess0;
-  r.best = best;
-  r.tried = tried;
-  return r;
-}
-
 // One wave per taxon, its six sub-fits one after another in diagnostic-slot
-// order.  Phase 1 twice (proposals<true>, proposals<false>).  Per sub-fit
-// (phases 2-3: subfit_weights above, shared with map_evidence_kernel):
-// phase 2 -- lanes over draws, the raw log-weight into LDS (map_psis_kernel's
-// statements for a PMD row); phase 3 -- psis_weights; phase 4 -- waic_points
-// with the draws regenerated from the stream, 64 at a time through a tile of
-// 15 columns that overlays the work buffer behind the weights (as the points'
-// accumulators do), lane i < 15
-// walking point i's accumulators over the tile's draws in ascending order;
-// then waic_row.  Row 6 is nutsloo::n_sigma on the waic_i columns, as
-// nuts_loo_kernel's.  Dynamic LDS: lds_len(S) doubles (22,016 B at S = 1024,
-// 11,048 B at S = 256); static: 4,448 B.  Reads y, N, out and status only.
-//
-// kAdapt (mdfit_map_waic_adapt, MDFIT-ADAPT v1): the PMD rows'
-// phases 2-3 run in map_psis_kernel<true>'s rounds, statement for statement, so
-// their khat, ess, n_infeasible, flags and adapt record are its bits; the null
-// rows take one pass.  The shift s_l0 is the log-pmf at the best round's centre.
+// order.  Phases 1-3 are the core's (mdfit_mapis.h): proposals<true> and
+// proposals<false>, then per sub-fit subfit_weights with the shift s_l0, the
+// log-pmf at the centre of the proposal whose weights stand (with kAdapt,
+// mdfit_map_waic_adapt, the PMD rows in the rounds of MDFIT-ADAPT v1, DESIGN.md
+// §3.12; the null rows take one pass).  Phase 4 -- waic_points with the draws
+// regenerated from the stream, 64 at a time through a tile of 15 columns that
+// overlays the work buffer behind the weights (as the points' accumulators
+// do), lane i < 15 walking point i's accumulators over the tile's draws in
+// ascending order; then waic_row.  Row 6 is nutsloo::n_sigma on the waic_i
+// columns, as nuts_loo_kernel's.  Dynamic LDS: lds_len(S) doubles (22,016 B at
+// S = 1024, 11,048 B at S = 256); static: 4,448 B.  Reads y, N, out and status
+// only.
 template <bool kAdapt>
 __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict__ gy,
                                                       const uint32_t* __restrict__ gN,
@@ -510,16 +254,10 @@ __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict
     if (lane < MDFIT_NSUBFIT + 1) invalid_row(rec + lane * MDFIT_NMAPWAIC, 0u);
     if (pw != nullptr)
       for (int i = lane; i < MDFIT_NSUBFIT * kMaxPts * 2; i += 64) pw[i] = NAN;
-    if (dr0 != nullptr)
-      for (int64_t i = lane; i < (int64_t)MDFIT_NSUBFIT * S * 6; i += 64) dr0[i] = NAN;
-    if constexpr (kAdapt)
-      if (adapt != nullptr && lane < 12) adapt[t * 12 + lane] = NAN;
+    bad_status_fills<kAdapt>(dr0, (int64_t)MDFIT_NSUBFIT * S * 6, adapt, t);
     return;
   }
-  if (lane < kLD) {
-    s_y[lane] = (double)gy[t * kLD + lane];
-    s_N[lane] = (double)gN[t * kLD + lane];
-  }
+  load_counts(gy, gN, t, s_y, s_N);
   for (int x = lane; x < (MDFIT_NSUBFIT + 1) * kMaxPts; x += 64) (&s_col[0][0])[x] = NAN;
 
   // ---- phase 1: the modes, g and H there, the held sets ----
@@ -541,28 +279,17 @@ __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict
     const unsigned mask = (unsigned)P[kPMask];
     double* dr = dr0 != nullptr ? dr0 + (int64_t)s * S * 6 : nullptr;
     bool ok = P[kPValid] != 0.0;  // (wave-uniform)
+    const int arow = s == 0 ? 0 : s - 1;  // a PMD sub-fit's row of the adapt record
     if (ok) {
-      Stream st;
-      st.k0 = (uint32_t)seed;
-      st.k1 = (uint32_t)(seed >> 32);
-      st.c0 = (uint32_t)gtaxon;
-      st.c1 = (uint32_t)(gtaxon >> 32) + ((uint32_t)s << 24);  // the chain's sub-fit index
+      const Stream st = subfit_stream(seed, gtaxon, s);
       const SubfitWeights sw = subfit_weights<kAdapt, true>(w, pmd, lo, hi, s_par[s], st, S, tau, adapt_rounds, s_y,
                                                             s_N, s_w, s_l0, dr);
       ok = sw.ok;
-      const double khat = sw.khat, n_inf = sw.n_inf, k0 = sw.k0, ess0 = sw.ess0;
-      const int best = sw.best, tried = sw.tried;
-      if constexpr (kAdapt) {
-        if (pmd && adapt != nullptr && lane == 0) {
-          double* ar = adapt + (t * 3 + (s == 0 ? 0 : s - 1)) * 4;
-          ar[mapadapt::kKhat0] = k0;
-          ar[mapadapt::kEss0] = ess0;
-          ar[mapadapt::kBestRound] = ok ? (double)best : NAN;
-          ar[mapadapt::kRoundsTried] = ok ? (double)tried : NAN;
-        }
-      }
-      if (dr != nullptr)
-        for (int i = lane; i < S; i += 64) dr[i * 6 + 5] = ok ? s_w[i] : NAN;
+      const double khat = sw.khat, n_inf = sw.n_inf;
+      const int best = sw.best;
+      if constexpr (kAdapt)
+        if (pmd) adapt_row(adapt, t, arow, sw);
+      draws_weights(dr, s_w, S, ok);
       if (ok) {
         // ---- phase 4: the pointwise statistics, the row ----
         waic_points(w, s_w, S, n, StreamSource{P, st, pmd, lo, s_y, s_N}, s_l0, tile, s_acc, s_pt[0], s_pt[1]);
@@ -579,10 +306,10 @@ __global__ __launch_bounds__(64) void map_waic_kernel(const uint32_t* __restrict
         }
       }
     } else if (dr != nullptr) {
-      for (int i = lane; i < S * 6; i += 64) dr[i] = NAN;
+      nan_fill(dr, (int64_t)S * 6);
     }
     if constexpr (kAdapt)
-      if (!ok && pmd && adapt != nullptr && lane < 4) adapt[(t * 3 + (s == 0 ? 0 : s - 1)) * 4 + lane] = NAN;
+      if (!ok && pmd) adapt_row_nan(adapt, t, arow);
     if (!ok) {
       all_ok = false;
       if (lane == 0) invalid_row(rec + s * MDFIT_NMAPWAIC, mask);
