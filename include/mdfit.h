@@ -826,6 +826,74 @@ int mdfit_map_pred_adapt(const uint32_t* y, const uint32_t* N, const double* out
                          uint64_t seed, int64_t index_base, float* ppred, double* rec, double* adapt,
                          int32_t* index, uint32_t* counts, void* hip_stream);
 
+/* Posterior predictive check record: double rec[T][MDFIT_NMAPPPC]: p_outlier,
+ * p_strand, t_outlier, t_strand, worst_pos (column 0..29), p_worst, n_low,
+ * n_points, khat, ess, n_distinct, flags (an integer stored as double: bit 0
+ * valid, bit 1 khat <= min(1 - 1 / log10 S, 0.7), bit 3 some replicated draw
+ * was no count, MDFIT_FLAG_ADAPTED as in the sibling records). */
+#define MDFIT_NMAPPPC 12
+#define MDFIT_PPC_VALID 1
+#define MDFIT_PPC_RELIABLE 2
+#define MDFIT_PPC_NONCOUNT 8
+
+/*
+ * Posterior predictive check of the PMD fit on all positions of a finished
+ * MODE_MAP call (MDFIT-PPC v1).  Row 0 (stream sub-fit 0) is
+ * importance-sampled and resampled exactly as mdfit_map_pred does it, so
+ * khat, ess, n_distinct, index and the counts of jobs 0..29 are that entry's
+ * row-0 bits at the same (seed, index_base + taxon, num_draws, num_pred).
+ * Draw r holds the observed count y_i and the replicated count of every column
+ * i with N_i > 0 against theta = (q, A, c, phi) of importance draw s(r): D =
+ * clamp(A (1 - q)^k + c, 0, 1), mu = N D, v = N D (1 - D)(phi + N) / (phi + 1),
+ * residual (count - mu) / sqrt(v), a column with v not > 0 skipped on both
+ * sides.  T_out = max_i r_i^2 (0 without a column), T_str = sum_{i<15} r_i -
+ * sum_{i>=15} r_i.  p_outlier = #{T_out(rep) >= T_out(obs)} / R, p_strand =
+ * #{|T_str(rep)| >= |T_str(obs)|} / R (NaN when a strand has no column with
+ * N > 0), t_outlier and t_strand the means over r of T_out(obs) and the signed
+ * T_str(obs).  ppos[i] = (2 #{rep_i > y_i} + #{rep_i = y_i}) / (2 R), the upper
+ * mid-p, NaN where N_i = 0; worst_pos the column with the smallest 2 min(p, 1 -
+ * p) (the lowest index among equals), p_worst that value, n_low the number of
+ * columns where it is < 0.05, n_points the number of columns with N > 0.  When
+ * a replicated draw is no count in [0, N], bit 3 is set, bit 0 is clear and
+ * p_outlier, p_strand, worst_pos, p_worst, n_low and ppos are NaN.  A row with
+ * no valid proposal or no weights, or a taxon with status != MDFIT_OK, gives
+ * NaN everywhere and flags 0.
+ *   y, N, out, status : those of the MODE_MAP call (device; read only)
+ *   num_draws  : S in [25, 1024] (else MDFIT_E_ARG)
+ *   num_pred   : R in [25, 1024] (else MDFIT_E_ARG)
+ *   seed, index_base : as mdfit_map_pred's
+ *   ppos       : float[n_taxa][30]                                  (device)
+ *   rec        : double[n_taxa][MDFIT_NMAPPPC]                      (device)
+ *   index      : int32[n_taxa][num_pred] = s(r), -1 where the taxon has no
+ *                weights; or NULL (parity tests)                    (device)
+ *   counts     : uint32[n_taxa][30][num_pred], the replicated counts,
+ *                0xFFFFFFFF for no count or a column not run; or NULL (device)
+ *   disc       : double[n_taxa][num_pred][4] = T_out(obs), T_out(rep),
+ *                T_str(obs), T_str(rep) of each draw, NaN where the taxon has
+ *                no weights; or NULL (parity tests)                 (device)
+ * One launch on hip_stream, one wave per taxon; no workspace, no allocation,
+ * no side stream, no host synchronisation, no atomics; capturable in a graph.
+ * Every count is an integer count, so the records do not depend on the grid,
+ * the chunking or index_base's split.  n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_ppc(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                  int64_t n_taxa, int32_t num_draws, int32_t num_pred, uint64_t seed, int64_t index_base,
+                  float* ppos, double* rec, int32_t* index, uint32_t* counts, double* disc, void* hip_stream);
+
+/*
+ * mdfit_map_ppc with the moment-matched proposal rounds of mdfit_map_psis_adapt
+ * on row 0 (as mdfit_map_pred_adapt): khat, ess, the flag bits and row 0 of
+ * adapt are mdfit_map_pred_adapt's bit for bit; rows 1 and 2 of adapt, which
+ * the check does not run, are NaN.  With adapt_rounds = 0 every output is
+ * mdfit_map_ppc's bit for bit.
+ *   adapt_rounds : in [0, MDFIT_ADAPT_MAX_ROUNDS] (else MDFIT_E_ARG)
+ *   adapt      : double[n_taxa][3][MDFIT_NMAPADAPT], or NULL       (device)
+ */
+int mdfit_map_ppc_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                        int64_t n_taxa, int32_t num_draws, int32_t num_pred, int32_t adapt_rounds,
+                        uint64_t seed, int64_t index_base, float* ppos, double* rec, double* adapt,
+                        int32_t* index, uint32_t* counts, double* disc, void* hip_stream);
+
 /* Test helper: mdfit_map_pred's resampling of given weights w[n_series][S]
  * (>= 0, not all 0), one wave per series: idx[n_series][R] = s(r) and
  * n_distinct[n_series] (device pointers).  S, R in [25, 1024]. */

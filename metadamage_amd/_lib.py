@@ -140,6 +140,16 @@ MAPPRED_VALID, MAPPRED_RELIABLE = 1, 2  # flags: bit 0 all rows valid, bit 1 and
 NPREDJOB = 32  # the sampler's predictive jobs: columns 0..29 of PMD-all, column 0 under PMD-forward and PMD-reverse
 PRED_DRAWS_MIN, PRED_DRAWS_MAX = 25, 1024
 
+# posterior predictive check record (mdfit_map_ppc): float64 [T][NMAPPPC]; worst_pos is a column 0..29
+NMAPPPC = 12
+MAPPPC_FIELDS = ["p_outlier", "p_strand", "t_outlier", "t_strand", "worst_pos", "p_worst", "n_low", "n_points", "khat",
+                 "ess", "n_distinct", "flags"]
+# flags: bit 0 valid, bit 1 khat <= threshold, bit 3 some replicated draw was no count (then bit 0 is clear), bit 6
+# (MAPPSIS_ADAPTED) the best round is > 0
+MAPPPC_VALID, MAPPPC_RELIABLE, MAPPPC_NONCOUNT = 1, 2, 8
+# the ppc block that leaves the device (ChunkedFitter ppc): float32 [T][NPPCOUT] = ppos[30] | rec[NMAPPPC]
+NPPCOUT = 30 + NMAPPPC
+
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
     "mdfit_default_opts",
@@ -167,6 +177,8 @@ EXPORTED_SYMBOLS = [
     "mdfit_adapt_proposal",
     "mdfit_map_pred",
     "mdfit_map_pred_adapt",
+    "mdfit_map_ppc",
+    "mdfit_map_ppc_adapt",
     "mdfit_resample",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
@@ -282,6 +294,12 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.mdfit_map_pred_adapt.restype = ctypes.c_int
         lib.mdfit_auto_route_pred.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
         lib.mdfit_auto_route_pred.restype = ctypes.c_int
+    if hasattr(lib, "mdfit_map_ppc"):  # (absent from the parent builds loaded by tools/ for A/B)
+        lib.mdfit_map_ppc.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp, vp]
+        lib.mdfit_map_ppc.restype = ctypes.c_int
+        lib.mdfit_map_ppc_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp,
+                                            vp, vp, vp]
+        lib.mdfit_map_ppc_adapt.restype = ctypes.c_int
     lib.mdfit_resample.argtypes = [vp, i64, i32, i32, vp, vp, vp]
     lib.mdfit_resample.restype = ctypes.c_int
     lib.mdfit_psis_weights.argtypes = [vp, i64, i32, vp, vp, vp]

@@ -5,8 +5,10 @@ gather record's layout) and fits (the frames' keywords) read every per-block
 fact from BLOCKS; a new block is one more entry here, one launch function in
 engine and its columns in fits.make_df_fit_results.  In the gather record and
 in the returned tuples the block follows the base record (out, pred, status);
-behind it come the tail blocks, which are no entries: auto-pred (f32 [2], only
-with auto), then adapt (f32 [2], psis_adapt > 0 with a `sampled` block).
+behind it come the tail blocks, which are no entries: ppc (f32 [42], only with
+ppred: the posterior predictive check rides with the predictive it checks),
+auto-pred (f32 [2], only with auto), then adapt (f32 [2], psis_adapt > 0 with a
+`sampled` block).
 """
 
 from __future__ import annotations

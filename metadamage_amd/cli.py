@@ -73,6 +73,9 @@ def cli_fit(
     auto_pred: bool = typer.Option(False, "--auto-pred", help="auto: D_max, its 68 % interval and the fit_predictions "
                                    "rows of a taxon that is not sampled from the importance-weighted posterior "
                                    "predictive (--pred-draws draws per position)"),
+    ppc: bool = typer.Option(False, "--ppc", help="map-pred: the posterior predictive check of the damage model -- "
+                             "p-values for an outlying position and for a strand difference, the worst position, "
+                             "and a per-position p-value in fit_predictions"),
 ):
     """Fitting Ancient Damage.
 
@@ -97,6 +100,7 @@ def cli_fit(
         "pred_draws": pred_draws,
         "psis_adapt": psis_adapt,
         "auto_pred": auto_pred,
+        "ppc": ppc,
     }
     if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "map-evidence", "nuts-diag",
                          "nuts-summary", "nuts-loo", "auto"):
@@ -112,6 +116,8 @@ def cli_fit(
         raise typer.BadParameter("--psis-adapt goes with --inference map-psis, map-waic, map-evidence or auto")
     if auto_pred and inference != "auto":
         raise typer.BadParameter("--auto-pred goes with --inference auto")
+    if ppc and inference != "map-pred":
+        raise typer.BadParameter("--ppc goes with --inference map-pred")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

@@ -1864,6 +1864,20 @@ int launch_map_pred(const uint32_t* y, const uint32_t* N, const double* out, con
   }
 }
 
+// (both instantiations of map_ppc_kernel are launched from their own unit, mdfit_mapppc.hip)
+template <bool kAdapt>
+int launch_map_ppc(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                   int32_t num_draws, int32_t num_pred, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
+                   float* ppos, double* rec, double* adapt, int32_t* index, uint32_t* counts, double* disc,
+                   void* hip_stream) {
+  const int rc =
+      check_is_args(false, n_taxa, num_draws, &num_pred, &adapt_rounds, y && N && out && status && ppos && rec);
+  if (rc <= 0) return rc;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  return mdfit::mapppc::launch(kAdapt, y, N, out, status, n_taxa, (int)num_draws, (int)num_pred, (int)adapt_rounds,
+                               seed, index_base, ppos, rec, adapt, index, counts, disc, (hipStream_t)hip_stream);
+}
+
 // mdfit_nuts_diag, _summary, _loo and _post: the checks on n_taxa and on the
 // options of the NUTS call, in their order.  needs_mode: the entry's message
 // for any other mode; ptrs: the required pointers are all there.  Returns as
@@ -2278,6 +2292,21 @@ int mdfit_map_pred_adapt(const uint32_t* y, const uint32_t* N, const double* out
                          uint32_t* counts, void* hip_stream) {
   return launch_map_pred<true>(y, N, out, status, n_taxa, num_draws, num_pred, adapt_rounds, seed, index_base, ppred,
                                rec, adapt, index, counts, hip_stream);
+}
+
+int mdfit_map_ppc(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                  int32_t num_draws, int32_t num_pred, uint64_t seed, int64_t index_base, float* ppos, double* rec,
+                  int32_t* index, uint32_t* counts, double* disc, void* hip_stream) {
+  return launch_map_ppc<false>(y, N, out, status, n_taxa, num_draws, num_pred, 0, seed, index_base, ppos, rec, nullptr,
+                               index, counts, disc, hip_stream);
+}
+
+int mdfit_map_ppc_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                        int32_t num_draws, int32_t num_pred, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
+                        float* ppos, double* rec, double* adapt, int32_t* index, uint32_t* counts, double* disc,
+                        void* hip_stream) {
+  return launch_map_ppc<true>(y, N, out, status, n_taxa, num_draws, num_pred, adapt_rounds, seed, index_base, ppos,
+                              rec, adapt, index, counts, disc, hip_stream);
 }
 
 int mdfit_log_mean_weight(const double* lw, int64_t n_series, int32_t S, double* logz, double* se, double* khat,

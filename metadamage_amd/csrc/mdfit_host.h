@@ -1,6 +1,7 @@
 // mdfit_host.h — host-side helpers shared by the translation units of
 // libmdfit.so (mdfit.hip: C-ABI + MAP kernels, mdfit_nuts.hip: sampling mode,
-// mdfit_mappred_adapt.hip: the adapting predictive kernel).
+// mdfit_mappred_adapt.hip: the adapting predictive kernel, mdfit_mapppc.hip:
+// the posterior predictive check).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -72,6 +73,14 @@ int launch_adapt(const uint32_t* y, const uint32_t* N, const double* out, const 
                  int R, int adapt_rounds, uint64_t seed, int64_t index_base, float* ppred, double* rec, double* adapt,
                  int32_t* index, uint32_t* counts, hipStream_t s);
 }  // namespace mdfit::mappred
+
+namespace mdfit::mapppc {
+// mdfit_map_ppc's and mdfit_map_ppc_adapt's launch (mdfit_mapppc.hip: both
+// instantiations of map_ppc_kernel); the arguments are checked by the caller
+int launch(bool adapting, const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+           int64_t n_taxa, int S, int R, int adapt_rounds, uint64_t seed, int64_t index_base, float* ppos, double* rec,
+           double* adapt, int32_t* index, uint32_t* counts, double* disc, hipStream_t s);
+}  // namespace mdfit::mapppc
 
 namespace mdfit::nuts {
 // sampling mode (mdfit_nuts.hip): workspace = 256 B of queue counters, then

@@ -42,43 +42,50 @@ REC_LAP, REC_DIAG, REC_SUMM, REC_LOO, REC_PSIS, REC_WAIC, REC_EVID, REC_PPRED, R
     _OUT_BYTES[name] for name in ("laplace", "diag", "summary", "loo", "psis", "waic", "evidence", "ppred", "auto"))
 # The tail blocks behind it.  auto_pred (with the auto block: with_auto_pred): one more f32 block [n, NAUTOPRED] =
 # pred_ess_min, pred_distinct_min, 8 B per taxon.  Then psis_adapt > 0 (with a sampled block: with_adapt; with the
-# ppred block, its own switch: with_ppred_adapt): one more f32 block [n, 2], 8 B per taxon
+# ppred block, its own switch: with_ppred_adapt): one more f32 block [n, 2], 8 B per taxon.  The posterior predictive
+# check (with the ppred block: with_ppc) rides directly behind its block, before the other tails: one more f32 block
+# [n, NPPCOUT] = ppos | rec, 168 B per taxon
 REC_AUTO_PRED = _lib.NAUTOPRED * 4
 REC_ADAPT = _lib.NADAPTOUT * 4
+REC_PPC = _lib.NPPCOUT * 4
 
 
-def _check_adapt(block, with_adapt: bool, with_auto_pred: bool, with_ppred_adapt: bool) -> None:
+def _check_adapt(block, with_adapt: bool, with_auto_pred: bool, with_ppred_adapt: bool,
+                 with_ppc: bool = False) -> None:
     """The tail switches go with their blocks: with_adapt with a sampled block other than ppred, which has
-    with_ppred_adapt; with_auto_pred with auto."""
+    with_ppred_adapt and with_ppc; with_auto_pred with auto."""
     name = block.name if block is not None else None
     if with_adapt and (name == "ppred" or not (block is not None and block.sampled)):
         raise ValueError("with_adapt goes with with_psis, with_waic or with_auto")
     if with_ppred_adapt and name != "ppred":
         raise ValueError("with_ppred_adapt goes with with_ppred")
+    if with_ppc and name != "ppred":
+        raise ValueError("with_ppc goes with with_ppred")
     if with_auto_pred and name != "auto":
         raise ValueError("with_auto_pred goes with with_auto")
 
 
 def _layout(switches: dict):
-    """(block, with_auto_pred, with_adapt, bytes per taxon) of a gather record from the keywords of Records and
-    unpack_gathered: one with_* of blocks.BLOCKS (blocks.select) and the tail switches (_check_adapt)."""
+    """(block, (with_ppc, with_auto_pred, with_adapt), bytes per taxon) of a gather record from the keywords of
+    Records and unpack_gathered: one with_* of blocks.BLOCKS (blocks.select) and the tail switches (_check_adapt)."""
     switches = dict(switches)
-    with_adapt, with_auto_pred, with_ppred_adapt = (
-        bool(switches.pop(k, False)) for k in ("with_adapt", "with_auto_pred", "with_ppred_adapt"))
+    with_adapt, with_auto_pred, with_ppred_adapt, with_ppc = (
+        bool(switches.pop(k, False)) for k in ("with_adapt", "with_auto_pred", "with_ppred_adapt", "with_ppc"))
     block = blocks.select(**switches)
-    _check_adapt(block, with_adapt, with_auto_pred, with_ppred_adapt)
+    _check_adapt(block, with_adapt, with_auto_pred, with_ppred_adapt, with_ppc)
     with_adapt = with_adapt or with_ppred_adapt
-    rec_bytes = (REC_BYTES + (block.out_bytes if block is not None else 0)
+    rec_bytes = (REC_BYTES + (block.out_bytes if block is not None else 0) + (REC_PPC if with_ppc else 0)
                  + (REC_AUTO_PRED if with_auto_pred else 0) + (REC_ADAPT if with_adapt else 0))
-    return block, with_auto_pred, with_adapt, rec_bytes
+    return block, (with_ppc, with_auto_pred, with_adapt), rec_bytes
 
 
-def _extra_views(buf, n: int, block, with_auto_pred: bool, with_adapt: bool):
-    """[block, auto_pred, adapt]: the f32 views [n, *shape] behind the n base records of the uint8 buffer, in the
-    record's order; None where the record has none."""
+def _extra_views(buf, n: int, block, tails=(False, False, False)):
+    """[block, ppc, auto_pred, adapt]: the f32 views [n, *shape] behind the n base records of the uint8 buffer, in
+    the record's order; None where the record has none.  tails: (with_ppc, with_auto_pred, with_adapt)."""
+    with_ppc, with_auto_pred, with_adapt = tails
     views, lo = [], n * REC_BYTES
-    for shape in (block.shape if block is not None else None, (_lib.NAUTOPRED,) if with_auto_pred else None,
-                  (_lib.NADAPTOUT,) if with_adapt else None):
+    for shape in (block.shape if block is not None else None, (_lib.NPPCOUT,) if with_ppc else None,
+                  (_lib.NAUTOPRED,) if with_auto_pred else None, (_lib.NADAPTOUT,) if with_adapt else None):
         if shape is None:
             views.append(None)
             continue
@@ -113,20 +120,20 @@ class Records:
     copies, the second rounding to f32) before the gather.  switches (_layout):
     the buffer is longer by the run's extra block, f32[n, *shape] after the
     status under the block's attr (written in place by the chunked dispatch;
-    every other block's attr is None), and by the tail blocks `auto_pred` and
-    `adapt` behind it."""
+    every other block's attr is None), and by the tail blocks `ppc`,
+    `auto_pred` and `adapt` behind it."""
 
     def __init__(self, n: int, device, **switches):
         import torch
 
-        block, with_auto_pred, with_adapt, rec_bytes = _layout(switches)
+        block, tails, rec_bytes = _layout(switches)
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
         self.buf = torch.empty(n * rec_bytes, dtype=torch.uint8, device=device)
         self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
         for b in blocks.BLOCKS:
             setattr(self, b.attr, None)
-        extra, self.auto_pred, self.adapt = _extra_views(self.buf, n, block, with_auto_pred, with_adapt)
+        extra, self.ppc, self.auto_pred, self.adapt = _extra_views(self.buf, n, block, tails)
         if block is not None:
             setattr(self, block.attr, extra)
         self._fidx = torch.as_tensor(FLOAT_COLS, device=device)
@@ -154,7 +161,7 @@ def packed_views(buf, n: int, **switches):
     status = buf[o3 : o3 + 4 * n].view(dtype=_torch_dtype("int32"))
     if block is None:
         return pred, status, ints, floats
-    return pred, status, ints, floats, _extra_views(buf, n, block, False, False)[0]
+    return pred, status, ints, floats, _extra_views(buf, n, block)[0]
 
 
 def round_like_gather(out: np.ndarray) -> np.ndarray:
@@ -280,13 +287,13 @@ def run_distributed(fn, *args, **kwargs):
 def unpack_gathered(parts, n_taxa: int, world: int, **switches):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  Returns (out, pred,
-    status[, block][, auto_pred][, adapt]): switches (Records') say which of the
-    extra block, f32 [T, *shape], and the tail blocks, f32 [T, 2] each, the
-    parts carry."""
+    status[, block][, ppc][, auto_pred][, adapt]): switches (Records') say which
+    of the extra block, f32 [T, *shape], and the tail blocks, f32 [T, NPPCOUT]
+    and f32 [T, 2] each, the parts carry."""
     import torch
 
-    block, with_auto_pred, with_adapt, rec_bytes = _layout(switches)
-    outs, preds, sts, extras = [], [], [], ([], [], [])
+    block, tails, rec_bytes = _layout(switches)
+    outs, preds, sts, extras = [], [], [], ([], [], [], [])
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)
@@ -304,7 +311,7 @@ def unpack_gathered(parts, n_taxa: int, world: int, **switches):
         lo, hi = shard_range(n_taxa, r, world)
         n_cap = part.numel() // rec_bytes
         p, s, ints, floats = packed_views(part, n_cap)
-        for got, view in zip(extras, _extra_views(part, n_cap, block, with_auto_pred, with_adapt)):
+        for got, view in zip(extras, _extra_views(part, n_cap, block, tails)):
             if view is not None:
                 got.append(view[: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)

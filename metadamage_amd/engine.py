@@ -40,7 +40,8 @@ class FitBatch:
     # the run's one optional block, float32 [T, *shape] of its blocks.BLOCKS entry, under the entry's attr (ppred:
     # split_ppred; auto: fit_auto_chunks), and the tail blocks behind it:
     # adapt float32 [T, NADAPTOUT], largest round-0 khat, largest best round (psis_adapt > 0);
-    # auto_pred float32 [T, NAUTOPRED], pred_ess_min, pred_distinct_min (auto with auto_pred)
+    # auto_pred float32 [T, NAUTOPRED], pred_ess_min, pred_distinct_min (auto with auto_pred);
+    # ppc float32 [T, NPPCOUT] = ppos | rec, the posterior predictive check (ppred with ppc; split_ppc)
     lap: "object" = None
     diag: "object" = None
     summ: "object" = None
@@ -52,6 +53,7 @@ class FitBatch:
     adapt: "object" = None
     auto_pred: "object" = None
     evid: "object" = None
+    ppc: "object" = None
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -696,6 +698,71 @@ def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int =
     return (ppred, rec) + tuple(x for x in (index, counts) if x is not None)
 
 
+def map_ppc_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int = 1000, seed: int = 0,
+                   index_base: int = 0, ppos=None, rec=None, index=None, counts=None, disc=None, stream=None,
+                   adapt_rounds: int = 0, adapt=None):
+    """Launch mdfit_map_ppc on the records of a finished MAP call (asynchronous
+    on `stream`): the posterior predictive check of the PMD fit on all positions
+    (MDFIT-PPC v1): float32 ppos[T, 30], the upper mid-p of each column, and
+    float64 rec[T, NMAPPPC] (_lib.MAPPPC_FIELDS).  The streams, the importance
+    draws and the replicated counts are map_pred_device's row 0 at the same
+    (seed, index_base, num_draws, num_pred).  index: None, True (allocated) or
+    an int32 tensor [T, num_pred]; counts: None, True or an int32 tensor [T, 30,
+    num_pred] holding the replicated counts as uint32 (0xFFFFFFFF: no count);
+    disc: None, True or a float64 tensor [T, num_pred, 4] = T_out(obs),
+    T_out(rep), T_str(obs), T_str(rep).  Returns (ppos, rec[, index][, counts]
+    [, disc]).
+
+    adapt_rounds > 0, or adapt given (True, or a float64 tensor [T, 3,
+    NMAPADAPT]): mdfit_map_ppc_adapt; the adapt block (rows 1 and 2 NaN) is then
+    the last element of the returned tuple.  adapt=False: the rounds without
+    their record (the chunked dispatch, whose map_pred launch has written it)."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S, R = int(ty.shape[0]), int(num_draws), int(num_pred)
+    no_record = adapt is False
+    adapt = None if no_record else adapt
+    use_adapt = int(adapt_rounds) != 0 or adapt is not None
+    if use_adapt and not no_record and (adapt is None or adapt is True):
+        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
+    if ppos is None:
+        ppos = torch.empty((T, _lib.NPOS), dtype=torch.float32, device=ty.device)
+    if rec is None:
+        rec = torch.empty((T, _lib.NMAPPPC), dtype=torch.float64, device=ty.device)
+    if index is True:
+        index = torch.empty((T, R), dtype=torch.int32, device=ty.device)
+    if counts is True:
+        counts = torch.empty((T, _lib.NPOS, R), dtype=torch.int32, device=ty.device)
+    if disc is True:
+        disc = torch.empty((T, R, 4), dtype=torch.float64, device=ty.device)
+    for name, t, n, dt in (("ppos", ppos, T * _lib.NPOS, torch.float32),
+                           ("rec", rec, T * _lib.NMAPPPC, torch.float64),
+                           ("index", index, T * R, torch.int32),
+                           ("counts", counts, T * _lib.NPOS * R, torch.int32),
+                           ("disc", disc, T * R * 4, torch.float64),
+                           ("adapt", adapt, T * 3 * _lib.NMAPADAPT, torch.float64)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of {n} elements")
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    head = [ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
+            ctypes.c_void_p(res.status.data_ptr()), T, S, R]
+    taps = [ctypes.c_void_p(x.data_ptr()) if x is not None else None for x in (index, counts, disc)]
+    got = (ppos, rec) + tuple(x for x in (index, counts, disc) if x is not None)
+    if use_adapt:
+        _lib.check(lib.mdfit_map_ppc_adapt(*head, int(adapt_rounds), int(seed), int(index_base),
+                                           ctypes.c_void_p(ppos.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+                                           ctypes.c_void_p(adapt.data_ptr()) if adapt is not None else None, *taps,
+                                           _stream_handle(torch, stream)))
+        return got + ((adapt,) if adapt is not None else ())
+    _lib.check(lib.mdfit_map_ppc(*head, int(seed), int(index_base), ctypes.c_void_p(ppos.data_ptr()),
+                                 ctypes.c_void_p(rec.data_ptr()), *taps, _stream_handle(torch, stream)))
+    return got
+
+
 def resample(w, num_pred: int, device="cuda"):
     """(idx[n, R] int32, n_distinct[n] int32) host arrays of the weight series
     w[n, S] by the device's midpoint systematic resampling (MDFIT-PPRED v1,
@@ -943,6 +1010,22 @@ def split_ppred(block):
     return block[:, :n].reshape(-1, _lib.NPRED, _lib.NPOS), block[:, n:]
 
 
+PPC_BYTES = _lib.NPPCOUT * 4  # one taxon's posterior predictive check as it leaves the device (f32 ppos | rec)
+_PPC_DEVICE_BYTES = _lib.NPOS * 4 + _lib.NMAPPPC * 8  # ... and as the launch computes it (f32 ppos, f64 rec)
+
+
+def split_ppc(block):
+    """(ppos[T, 30], rec[T, NMAPPPC]) views of a posterior predictive check block [T, NPPCOUT]."""
+    return block[:, :_lib.NPOS], block[:, _lib.NPOS:]
+
+
+def _check_ppc(ppc: bool, block) -> bool:
+    """ppc (the posterior predictive check, a tail of the ppred block) goes with with_ppred."""
+    if ppc and (block is None or block.name != "ppred"):
+        raise ValueError("ppc needs with_ppred: the check is of the predictive that mdfit_map_pred forms")
+    return bool(ppc)
+
+
 def _chunked_block(opts, switches):
     """blocks.resolve for the chunked dispatch: the run's one block, or None."""
     block = blocks.resolve(opts, **switches)
@@ -963,7 +1046,7 @@ def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
 
 
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
-                 dest_on_device: bool = False, **switches) -> int:
+                 dest_on_device: bool = False, ppc: bool = False, **switches) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -971,29 +1054,33 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     ~4.9 KB from 60k, NUTS 6 x num_samples x 32 B, the draws).  switches (one
     with_* of blocks.BLOCKS, checked by blocks.resolve): the run's block as the
     launch computes it and -- unless it goes to the caller's device buffer --
-    as it leaves, rounded to f32."""
+    as it leaves, rounded to f32.  ppc (with with_ppred): the check's block in
+    the same two forms."""
     C = int(C)
     block = _chunked_block(opts, switches)
+    ppc = _check_ppc(ppc, block)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
     if block is not None:
         b += C * (block.device_bytes + (0 if dest_on_device else block.out_bytes))
+    if ppc:
+        b += C * (_PPC_DEVICE_BYTES + (0 if dest_on_device else PPC_BYTES))
     return b + workspace_bytes(C, opts)
 
 
 def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | None = None, *,
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
-                dest_on_device: bool = False, **switches) -> list[tuple[int, int]]:
+                dest_on_device: bool = False, ppc: bool = False, **switches) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk (device_bytes, with the run's block of
-    switches) fit in budget_bytes (None: no memory bound), no chunk exceeds the
+    switches and ppc) fit in budget_bytes (None: no memory bound), no chunk exceeds the
     per-call limit (2^25 taxa) or chunk_taxa (> 0; env MDFIT_CHUNK_TAXA when 0).
     Taxa are independent and the sampler's streams are keyed by the global taxon
     index (opts.index_base + lo), so any split gives the records of one call bit
     for bit."""
     T = int(T)
-    _chunked_block(opts, switches)
+    _check_ppc(ppc, _chunked_block(opts, switches))
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -1002,7 +1089,10 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     if chunk_taxa > 0:
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
-        per = lambda c: n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, **switches)  # noqa: E731
+        def per(c):
+            return n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, ppc, **switches)
+
+
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
         if per(cap) > budget_bytes:  # largest c with per(c) <= budget (per is monotone in c)
@@ -1034,7 +1124,7 @@ class _Set:
     run one after another on the compute stream)."""
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
-                 block: blocks.Block | None = None, with_adapt: bool = False):
+                 block: blocks.Block | None = None, with_adapt: bool = False, ppc: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -1055,6 +1145,12 @@ class _Set:
             self.adapt64 = torch.empty((C, 3, _lib.NMAPADAPT), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.adapt = torch.empty((C, _lib.NADAPTOUT), dtype=torch.float32, device=device)
+        self.ppc_computed = self.ppc = None
+        if ppc:  # as mdfit_map_ppc writes it (f32 ppos, f64 rec), and as one f32 block for the way out
+            self.ppc_computed = (torch.empty((C, _lib.NPOS), dtype=torch.float32, device=device),
+                                 torch.empty((C, _lib.NMAPPPC), dtype=torch.float64, device=device))
+            if not dest_on_device:
+                self.ppc = torch.empty((C, _lib.NPPCOUT), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -1141,12 +1237,19 @@ class ChunkedFitter:
     moment-matched proposal rounds per PMD row (MDFIT-ADAPT v1), and one more
     f32 block [T, 2] = (largest round-0 khat over the PMD rows, largest best
     round), reduced on the device (adapt_summary), leaves behind the block
-    (run's fifth array; dest.adapt)."""
+    (run's fifth array; dest.adapt).
+
+    ppc (with with_ppred): mdfit_map_ppc (mdfit_map_ppc_adapt with the same
+    rounds when psis_adapt > 0) follows the chunk's map_pred launch on the
+    compute stream -- no further stream --, and one more f32 block [T, NPPCOUT]
+    = ppos | rec (split_ppc), rounded on the device, leaves behind the block and
+    before adapt (run; dest.ppc)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, psis_draws: int = PSIS_DRAWS,
-                 pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, **switches):
+                 pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, **switches):
         self.block = _chunked_block(opts, switches)
+        self.ppc = _check_ppc(ppc, self.block)
         torch = _torch()
         self.psis_adapt = _check_psis_adapt(psis_adapt, self.block is not None and self.block.sampled)
         self.pred_draws = int(pred_draws)
@@ -1155,14 +1258,14 @@ class ChunkedFitter:
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.block,
-                          self.psis_adapt > 0)
+                          self.psis_adapt > 0, self.ppc)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = None
-        self.h_block = self.h_adapt = None
+        self.h_block = self.h_adapt = self.h_ppc = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -1182,6 +1285,8 @@ class ChunkedFitter:
                 self.h_block = torch.empty((cap, *self.block.shape), dtype=torch.float32).pin_memory()
             if self.psis_adapt > 0:
                 self.h_adapt = torch.empty((cap, _lib.NADAPTOUT), dtype=torch.float32).pin_memory()
+            if self.ppc:
+                self.h_ppc = torch.empty((cap, _lib.NPPCOUT), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -1215,6 +1320,8 @@ class ChunkedFitter:
                 raise ValueError(f"{block.switch}: dest.{block.attr} (float32 [T, {shape}]) required")
         if self.psis_adapt > 0 and dest is not None and dest.adapt is None:
             raise ValueError("psis_adapt: dest.adapt (float32 [T, NADAPTOUT]) required")
+        if self.ppc and dest is not None and getattr(dest, "ppc", None) is None:
+            raise ValueError("ppc: dest.ppc (float32 [T, NPPCOUT]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -1257,7 +1364,7 @@ class ChunkedFitter:
                 _lib.check(lib.mdfit_noise(ctypes.c_void_p(st.d_y.data_ptr()), ctypes.c_void_p(st.d_N.data_ptr()),
                                            ctypes.c_void_p(st.d_mm.data_ptr()), n, ctypes.c_void_p(res.out.data_ptr()),
                                            h_s))
-            block32 = adapt32 = None
+            block32 = adapt32 = ppc32 = None
             if block is not None:  # the records are final: the block's launch, then one f32 block for the way out
                 ad_kw = {"adapt_rounds": self.psis_adapt, "adapt": st.adapt64[:n]} if self.psis_adapt > 0 else {}
                 _LAUNCH[block.name](self, st, n, res, o, comp, ad_kw)
@@ -1272,6 +1379,14 @@ class ChunkedFitter:
                         # slot 7, not among the columns that leave the device): valid + 2 * divergences
                         div = torch.nan_to_num(res.out[:, _lib.F_DIAG + 7::_lib.DIAG_STRIDE], nan=0.0)
                         block32[:, :, _lib.NNUTSDIAG - 1] += (2.0 * div).to(torch.float32)
+            if self.ppc:  # the check of the predictive just formed: the same draws, rounds and stream
+                map_ppc_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, self.pred_draws, int(o.seed),
+                               int(o.index_base), ppos=st.ppc_computed[0][:n], rec=st.ppc_computed[1][:n], stream=comp,
+                               **({"adapt_rounds": self.psis_adapt, "adapt": False} if self.psis_adapt > 0 else {}))
+                ppc32 = dest.ppc[lo:hi] if dest is not None else st.ppc[:n]
+                with torch.cuda.stream(comp):
+                    for view, computed in zip(split_ppc(ppc32), st.ppc_computed):
+                        view.copy_(computed[:n])
             if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
                 adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
                 with torch.cuda.stream(comp):
@@ -1288,6 +1403,8 @@ class ChunkedFitter:
                     self.h_status[lo:hi].copy_(res.status, non_blocking=True)
                     if block32 is not None:
                         self.h_block[lo:hi].copy_(block32, non_blocking=True)
+                    if ppc32 is not None:
+                        self.h_ppc[lo:hi].copy_(ppc32, non_blocking=True)
                     if adapt32 is not None:
                         self.h_adapt[lo:hi].copy_(adapt32, non_blocking=True)
                 last_d2h = cp
@@ -1299,7 +1416,7 @@ class ChunkedFitter:
     def run(self, y, N, mm=None, opts: _lib.MdfitOpts | None = None, sync: bool = True,
             pinned: PinnedPack | None = None, chunks=None):
         """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status[, the
-        run's block f32 [T, *shape]][, adapt f32 [T, 2]]) of the pinned buffers
+        run's block f32 [T, *shape]][, ppc f32 [T, NPPCOUT]][, adapt f32 [T, 2]]) of the pinned buffers
         (valid until the next run).  pinned: y, N, mm are that PinnedPack's
         views.  chunks: the split (default plan_chunks at this staging's
         chunk_cap)."""
@@ -1316,6 +1433,8 @@ class ChunkedFitter:
                self.h_status[:T].numpy())
         if self.block is not None:
             got += (self.h_block[:T].numpy(),)
+        if self.ppc:
+            got += (self.h_ppc[:T].numpy(),)
         if self.psis_adapt > 0:
             got += (self.h_adapt[:T].numpy(),)
         return got
@@ -1323,7 +1442,7 @@ class ChunkedFitter:
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
         (out[T, NOUT], pred, status -- and the run's block under its attribute,
-        adapt when psis_adapt > 0: rows written in place), ordered on the
+        ppc with ppc, adapt when psis_adapt > 0: rows written in place), ordered on the
         caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
@@ -1391,10 +1510,10 @@ _STAGING_LOCK = __import__("threading").Lock()
 
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
             dest_on_device: bool = False, budget_bytes: int | None = None, psis_draws: int = PSIS_DRAWS,
-            pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, **switches) -> ChunkedFitter:
+            pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, **switches) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind, sampler length and the run's block
-    of switches with the draw counts it uses and psis_adapt): the
+    of switches with the draw counts it uses, psis_adapt and ppc): the
     multi-file pipeline fits one file after another, and pinned + device
     buffers allocated per file cost more host time than the fit.  Its chunk
     capacity is the largest chunk N_SETS buffer sets of which fit the device
@@ -1412,7 +1531,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
            block.name if block is not None else None,
            int(psis_draws) if block is not None and block.sampled else 0,
-           int(pred_draws) if block is not None and block.name == "ppred" else 0, int(psis_adapt))
+           int(pred_draws) if block is not None and block.name == "ppred" else 0, int(psis_adapt),
+           _check_ppc(ppc, block))
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1429,10 +1549,10 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     if T < _lib.STREAM_MAX_TAXA:
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
-                      **switches)[0]
+                      ppc=ppc, **switches)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
-                       psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, **switches)
+                       psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, **switches)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1441,20 +1561,22 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, psis_draws: int = PSIS_DRAWS, pred_draws: int = PRED_DRAWS,
-                   psis_adapt: int = 0, **named):
+                   psis_adapt: int = 0, ppc: bool = False, **named):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     named (one chunked block of blocks.BLOCKS by its name, e.g. laplace=True), a
     fourth array, the block's f32 [T, *shape] --, chunked through the device
     budget (ChunkedFitter, which documents psis_draws, pred_draws and
     psis_adapt; psis_adapt > 0 returns a fifth array adapt[T, 2] f32,
-    _lib.ADAPTOUT_FIELDS).  mm goes to the device (the assembly computes the
+    _lib.ADAPTOUT_FIELDS; ppc, with ppred=True, the check's f32 [T, NPPCOUT]
+    behind the block and before adapt).  mm goes to the device (the assembly computes the
     noise columns); without it, `noise` (float64[T][3], ingest.noise) fills them
     when given.  pinned: y, N, mm are views of that PinnedPack (copied to the
     device from there)."""
     T = int(y.shape[0])
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, psis_draws=psis_draws,
-                     pred_draws=pred_draws, psis_adapt=psis_adapt, **{"with_" + k: v for k, v in named.items()})
+                     pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
+                     **{"with_" + k: v for k, v in named.items()})
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         got = tuple(a.copy() for a in got)
     out, status = got[0], got[2]

@@ -137,6 +137,14 @@ _MAP_PRED_PICKS = [("D_max_predictive", "D_max"), ("D_max_predictive_lower_hpdi"
 MAP_PRED_COLUMNS = [name for name, _ in _MAP_PRED_PICKS] + ["pareto_k_pred", "pred_ess_min"]
 MAP_PRED_UINT_COLUMNS = ["pred_distinct_min", "map_pred_valid", "map_pred_reliable"]
 MAP_PRED_PREDICTION_COLUMNS = ["median_posterior", "hdpi_lower_posterior", "hdpi_upper_posterior"]
+# "map-pred" with ppc (mdfit_map_ppc, MDFIT-PPC v1): behind map-pred's columns the posterior
+# predictive check of the PMD fit -- the two p-values and the mean observed discrepancies (float32), the reference's
+# z (+1..+15, -1..-15; 0: none) of the column with the smallest two-sided mid-p (int8), that mid-p (float32), the
+# number of columns where it is below 0.05 (uint8) and the record's valid bit (bool); ppc_p in the predictions frame
+_PPC_PICKS = [("ppc_p_outlier", "p_outlier"), ("ppc_p_strand", "p_strand"), ("ppc_t_outlier", "t_outlier"),
+              ("ppc_t_strand", "t_strand")]
+PPC_COLUMNS = [name for name, _ in _PPC_PICKS] + ["ppc_worst_position", "ppc_p_worst", "ppc_n_low", "ppc_valid"]
+PPC_PREDICTION_COLUMNS = ["ppc_p"]
 # "auto": the auto block appended after shortname -- uint32
 # auto_route (the mdfit_auto_route bits) and auto_sampled (1: the row is the
 # sampler's), then float32 pareto_k_max and psis_ess_min (row 6 of the waic
@@ -338,7 +346,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, pred_draws: int = 1000,
-               psis_adapt: int = 0, auto_pred: bool = False, **named):
+               psis_adapt: int = 0, auto_pred: bool = False, ppc: bool = False, **named):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -356,7 +364,10 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, 
     last.  auto_pred (with auto; MDFIT-AUTO v1.1): a settled taxon's
     predictive columns and prediction rows are the importance-weighted posterior
     predictive from pred_draws draws per job, and auto_pred[T, 2] f32 =
-    (pred_ess_min, pred_distinct_min) is returned behind the auto block."""
+    (pred_ess_min, pred_distinct_min) is returned behind the auto block.  ppc
+    (with ppred; MDFIT-PPC v1): mdfit_map_ppc follows each chunk's map_pred
+    launch and ppc[T, 42] f32 = ppos | rec is returned directly behind the
+    ppred block."""
     import torch
 
     from . import engine
@@ -383,20 +394,22 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, 
     psis_adapt = engine._check_psis_adapt(psis_adapt, block is not None and block.sampled)
     if auto_pred and not auto:
         raise ValueError("auto_pred goes with the auto inference")
+    ppc = engine._check_ppc(ppc, block)
     try:
         if grouped:
-            return _fit_sharded(p, opts, dev, rank, world, block, psis_draws, pred_draws, psis_adapt, auto_pred)
+            return _fit_sharded(p, opts, dev, rank, world, block, psis_draws, pred_draws, psis_adapt, auto_pred, ppc)
         if auto:
             return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt,
                                           auto_pred=auto_pred, pred_draws=pred_draws)
         return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, psis_draws=psis_draws,
-                                     pred_draws=pred_draws, psis_adapt=psis_adapt, **named)
+                                     pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, **named)
     finally:
         p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Block | None = None,
-                 psis_draws: int = 256, pred_draws: int = 1000, psis_adapt: int = 0, auto_pred: bool = False):
+                 psis_draws: int = 256, pred_draws: int = 1000, psis_adapt: int = 0, auto_pred: bool = False,
+                 ppc: bool = False):
     import torch
 
     from . import engine
@@ -410,12 +423,13 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
     switch = {block.switch: True} if block is not None else {}
     ppred = block is not None and block.name == "ppred"  # (its adapt tail has a switch of its own)
     layout = dict(switch, with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                  with_auto_pred=auto_pred)
+                  with_auto_pred=auto_pred, with_ppc=ppc)
     rec = alloc_records(cap, dev, **layout)
     # the rows are written in place into the gather buffers
     dest = engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                            adapt=rec.adapt[: hi - lo] if psis_adapt > 0 else None,
                            auto_pred=rec.auto_pred[: hi - lo] if auto_pred else None,
+                           ppc=rec.ppc[: hi - lo] if ppc else None,
                            **({block.attr: getattr(rec, block.attr)[: hi - lo]} if block is not None else {}))
     if hi > lo and block is not None and not block.chunked:  # each rank runs auto on its shard
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
@@ -425,7 +439,8 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
     elif hi > lo:  # the shard through the bounded-memory chunked dispatch
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
-                                psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, **switch)
+                                psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
+                                **switch)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, dest)
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
@@ -492,7 +507,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
                         psis=None, waic=None, auto=None, ppred=None, adapt=None, auto_pred=None,
-                        evid=None) -> pd.DataFrame:
+                        evid=None, ppc=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -515,7 +530,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     [T, 106] of a "map-pred" run): the MAP_PRED_COLUMNS follow as float32, then
     the MAP_PRED_UINT_COLUMNS.  auto_pred (the auto-pred block [T, 2] of an
     "auto" run with auto_pred): pred_ess_min (float32) and pred_distinct_min
-    (uint32) follow the auto columns.  adapt (the adapt block [T, 2] of a run with
+    (uint32) follow the auto columns.  ppc (the posterior predictive check's
+    block [T, 42] of a "map-pred" run with ppc): the PPC_COLUMNS follow
+    map-pred's, in their own dtypes.  adapt (the adapt block [T, 2] of a run with
     psis_adapt > 0): pareto_k_initial (float32) and psis_adapt_rounds (uint32)
     are the last two columns."""
     n = int(keep.sum())
@@ -622,6 +639,20 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["map_pred_valid"] = ((flags & _lib.MAPPRED_VALID) != 0).astype(np.uint32)
         data["map_pred_reliable"] = ((flags & _lib.MAPPRED_RELIABLE) != 0).astype(np.uint32)
         columns += MAP_PRED_COLUMNS + MAP_PRED_UINT_COLUMNS
+    if ppc is not None:
+        kc = np.asarray(ppc)[:, _lib.NPOS:]
+        kc = kc if keep is None else kc[keep]
+        f = _lib.MAPPPC_FIELDS.index
+        for name, field in _PPC_PICKS:
+            data[name] = np.ascontiguousarray(kc[:, f(field)], dtype=np.float32)
+        worst = kc[:, f("worst_pos")]
+        col = np.nan_to_num(worst, nan=0.0).astype(np.int64)
+        data["ppc_worst_position"] = np.where(np.isnan(worst), 0, POSITIONS[col]).astype(np.int8)
+        data["ppc_p_worst"] = np.ascontiguousarray(kc[:, f("p_worst")], dtype=np.float32)
+        data["ppc_n_low"] = np.nan_to_num(kc[:, f("n_low")]).astype(np.uint8)
+        flags = np.nan_to_num(kc[:, f("flags")]).astype(np.int64)
+        data["ppc_valid"] = (flags & _lib.MAPPPC_VALID) != 0
+        columns += PPC_COLUMNS
     if adapt is not None:
         kd = np.asarray(adapt) if keep is None else np.asarray(adapt)[keep]
         data["pareto_k_initial"] = np.ascontiguousarray(kd[:, 0], dtype=np.float32)
@@ -630,10 +661,12 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     return pd.DataFrame({c: data[c] for c in columns}, copy=False)
 
 
-def make_df_fit_predictions(p: Packed, pred, keep, cfg, ppred=None) -> pd.DataFrame:
+def make_df_fit_predictions(p: Packed, pred, keep, cfg, ppred=None, ppc=None) -> pd.DataFrame:
     """fits.py:632-665: 30 rows per fitted taxon (z = 1..15, -1..-15).  ppred
     (the posterior predictive block [T, 106] of a "map-pred" run): the
-    MAP_PRED_PREDICTION_COLUMNS follow as float32."""
+    MAP_PRED_PREDICTION_COLUMNS follow as float32.  ppc (the posterior
+    predictive check's block [T, 42]): ppc_p, the upper mid-p of the position's
+    observed count, follows as float32."""
     n = int(keep.sum())
     kp = pred if n == len(keep) else pred[keep]
     data = {
@@ -649,6 +682,10 @@ def make_df_fit_predictions(p: Packed, pred, keep, cfg, ppred=None) -> pd.DataFr
         pp = pp if n == len(keep) else pp[keep]
         for j, name in enumerate(MAP_PRED_PREDICTION_COLUMNS):
             data[name] = np.ascontiguousarray(pp[:, j, :], dtype=np.float32).reshape(-1)
+    if ppc is not None:
+        pc = np.asarray(ppc)[:, :_lib.NPOS]
+        pc = pc if n == len(keep) else pc[keep]
+        data["ppc_p"] = np.ascontiguousarray(pc, dtype=np.float32).reshape(-1)
     return pd.DataFrame(data, copy=False)
 
 
@@ -753,6 +790,15 @@ def auto_pred_of(cfg) -> bool:
     return on
 
 
+def ppc_of(cfg) -> bool:
+    """cfg.ppc (default False): a "map-pred" run adds the posterior predictive check of the PMD fit (MDFIT-PPC v1);
+    with any other inference a ValueError naming the option."""
+    on = bool(getattr(cfg, "ppc", False))
+    if on and not wants_pred(cfg):
+        raise ValueError("ppc goes with inference 'map-pred'")
+    return on
+
+
 def _split_rest(cfg, rest):
     """The optional arrays behind (out, pred, status) of fit_packed: (the run's extra block or None, auto_pred or
     None, adapt or None) -- the auto-pred block follows the extra block, the adapt block is last."""
@@ -774,13 +820,16 @@ def _fit_for_frames(p: Packed, cfg, opts, shard: bool):
     inference = getattr(cfg, "inference", "nuts")
     block = next((b for b in blocks.BLOCKS if b.inference == inference), None)
     res = fit_packed(p, opts, shard=shard, psis_draws=psis_draws_of(cfg), pred_draws=pred_draws_of(cfg),
-                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg),
+                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg), ppc=ppc_of(cfg),
                      **({block.name: True} if block is not None else {}))
     if res is None:
         return None
     out, pred, status, *rest = res
+    ppc = rest.pop(1) if ppc_of(cfg) else None  # (directly behind the ppred block)
     extra, auto_pred, adapt = _split_rest(cfg, rest)
     kw = {"adapt": adapt, "auto_pred": auto_pred}
+    if ppc is not None:
+        kw["ppc"] = ppc
     if block is not None:
         kw[block.attr] = extra
     keep = status == _lib.OK
@@ -802,7 +851,7 @@ def compute_fits(df_counts, cfg, mcmc_kwargs=None, opts=None, shard=True):
         return None, None
     out, pred, keep, kw = res
     return (make_df_fit_results(p, out, keep, cfg, **kw),
-            make_df_fit_predictions(p, pred, keep, cfg, ppred=kw.get("ppred")))
+            make_df_fit_predictions(p, pred, keep, cfg, ppred=kw.get("ppred"), ppc=kw.get("ppc")))
 
 
 def extract_top_max_fits(df_counts, max_fits):
@@ -849,7 +898,8 @@ def _rank() -> int:
 
 
 CACHE_KEYS = ["min_alignments", "min_y_sum", "substitution_bases_forward", "substitution_bases_reverse",
-              "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws", "psis_adapt", "auto_pred"]
+              "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws", "psis_adapt", "auto_pred",
+              "ppc"]
 
 
 def _cache_hit(cfg) -> bool:
@@ -905,7 +955,7 @@ def get_fits(df_counts, cfg, opts=None, shard=True, writer=None, packed=None, de
         from .counts import _save
 
         df_fit_results = make_df_fit_results(p, out, keep, cfg, **kw)
-        df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=kw.get("ppred"))
+        df_fit_predictions = make_df_fit_predictions(p, pred, keep, cfg, ppred=kw.get("ppred"), ppc=kw.get("ppc"))
         _save(writer, parquet_fit_results, df_fit_results, cfg.to_dict())
         _save(writer, parquet_fit_predictions, df_fit_predictions, cfg.to_dict())
         return df_fit_results, df_fit_predictions

@@ -74,9 +74,14 @@ class Config:
     # "auto": a settled taxon's predictive columns and prediction rows from the importance-weighted posterior
     # predictive (MDFIT-AUTO v1.1; pred_draws then applies); in the metadata and the cache key only when set
     auto_pred: bool = False
+    # "map-pred": the posterior predictive check of the PMD fit (MDFIT-PPC v1) beside the predictive; in the metadata
+    # and the cache key only when set
+    ppc: bool = False
     N_cores: int = field(init=False)
 
     def __post_init__(self):
+        if self.ppc and self.inference != "map-pred":
+            raise ValueError("ppc goes with inference 'map-pred'")
         self._set_N_cores()
 
     def _set_N_cores(self):
@@ -147,6 +152,8 @@ class Config:
             del d_out["psis_adapt"]
         if not self.auto_pred:
             del d_out["auto_pred"]
+        if not self.ppc:
+            del d_out["ppc"]
         for key, val in d_out.items():
             if isinstance(val, Path):
                 d_out[key] = str(val)
