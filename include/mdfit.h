@@ -894,6 +894,76 @@ int mdfit_map_ppc_adapt(const uint32_t* y, const uint32_t* N, const double* out,
                         uint64_t seed, int64_t index_base, float* ppos, double* rec, double* adapt,
                         int32_t* index, uint32_t* counts, double* disc, void* hip_stream);
 
+/* Weighted order statistics record: double quant[T][3][MDFIT_NMAPQUANT], rows
+ * PMD-all, forward, reverse: D_max_median, D_max_lo, D_max_hi, D_max_q05,
+ * D_max_q95, D_max_p_above, q_median, q_lo, q_hi, A_median, c_median,
+ * phi_median, khat, ess, n_window (of D_max), flags (mdfit_map_psis's: an
+ * integer stored as double, MDFIT_PSIS_* and MDFIT_FLAG_ADAPTED). */
+#define MDFIT_NMAPQUANT 16
+
+/*
+ * The median, 68 % highest-posterior-density interval and quantiles of the
+ * importance-weighted posterior of a finished MODE_MAP call (MDFIT-QUANT v1,
+ * DESIGN.md §3.17).  Each PMD sub-fit is drawn, weighted and smoothed exactly
+ * as mdfit_map_psis does it, so khat, ess and flags are that entry's bit for
+ * bit at the same (seed, index_base + taxon, num_draws).  The smoothed weight
+ * w_s of draw s becomes the integer mass k_s = rint(w_s 2^52), K = sum k_s;
+ * a draw with k_s = 0 takes no part.  The draws are ordered ascending by
+ * (value, draw index) and cum_j is the mass up to sorted draw j; every
+ * comparison of masses is an integer comparison:
+ *   median  : the mean of the first draw with 2 cum_j >= K and the first with
+ *             2 cum_j > K
+ *   q05, q95: the first draw with 100 cum_j >= 5 K, >= 95 K
+ *   lo, hi  : over every first draw i, the window [i, j(i)] ending at the
+ *             first j >= i with 100 (cum_j - cum_{i-1}) > 68 K; the narrowest
+ *             window hi - lo, the lowest i among equals; n_window its draws
+ *   p_above : sum of k_s over the draws with value > d0 (strictly), over K
+ * With equal weights these are mdfit_nuts_summary's median and window of
+ * int(0.68 S) + 1 sorted draws.  D_max = A + c gets all of them, q its median
+ * and interval, A, c and phi their medians.  A row that mdfit_map_psis gives
+ * as invalid is NaN with the free bits alone in flags; a taxon with status !=
+ * MDFIT_OK is NaN with flags 0.
+ *   y, N, out, status : those of the MODE_MAP call (device; read only)
+ *   num_draws  : S in [25, 1024] (else MDFIT_E_ARG)
+ *   seed, index_base : as mdfit_map_psis's
+ *   d0         : the threshold of p_above; finite and in [0, 1] (else
+ *                MDFIT_E_ARG)
+ *   quant      : double[n_taxa][3][MDFIT_NMAPQUANT]                (device)
+ *   values     : double[n_taxa][3][num_draws][6] = D_max, q, A, c, phi of draw
+ *                s and its smoothed weight, NaN in an invalid row; or NULL
+ *                (parity tests)                                    (device)
+ * One launch on hip_stream, one wave per taxon; no workspace, no allocation,
+ * no side stream, no host synchronisation, no atomics; capturable in a graph.
+ * The records do not depend on the grid, the chunking or index_base's split.
+ * n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_quant(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                    int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base, double d0,
+                    double* quant, double* values, void* hip_stream);
+
+/*
+ * mdfit_map_quant with the moment-matched proposal rounds of
+ * mdfit_map_psis_adapt: khat, ess, flags (MDFIT_FLAG_ADAPTED included) and
+ * adapt are that entry's bit for bit, and the statistics are those of the best
+ * round's draws and weights.  With adapt_rounds = 0 every output is
+ * mdfit_map_quant's bit for bit.
+ *   adapt_rounds : in [0, MDFIT_ADAPT_MAX_ROUNDS] (else MDFIT_E_ARG)
+ *   adapt      : double[n_taxa][3][MDFIT_NMAPADAPT], or NULL       (device)
+ */
+int mdfit_map_quant_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                          int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed,
+                          int64_t index_base, double d0, double* quant, double* adapt, double* values,
+                          void* hip_stream);
+
+/* Test helper: the weighted order statistics of MDFIT-QUANT v1 on given
+ * series v[n_series][S] and weights w[n_series][S] (each in [0, 1]), one wave
+ * per series: res[n_series][8] = median, lo, hi, q05, q95, p_above, n_window,
+ * ok (device pointers).  ok = 0 and NaN statistics when the masses sum to 0,
+ * when a draw with mass is not finite, or when a weight is NaN or outside
+ * [0, 1].  S in [25, 1024]; d0 finite and in [0, 1]. */
+int mdfit_weighted_order_stats(const double* v, const double* w, int64_t n_series, int32_t S, double d0,
+                               double* res, void* hip_stream);
+
 /* Test helper: mdfit_map_pred's resampling of given weights w[n_series][S]
  * (>= 0, not all 0), one wave per series: idx[n_series][R] = s(r) and
  * n_distinct[n_series] (device pointers).  S, R in [25, 1024]. */

@@ -150,6 +150,15 @@ MAPPPC_VALID, MAPPPC_RELIABLE, MAPPPC_NONCOUNT = 1, 2, 8
 # the ppc block that leaves the device (ChunkedFitter ppc): float32 [T][NPPCOUT] = ppos[30] | rec[NMAPPPC]
 NPPCOUT = 30 + NMAPPPC
 
+# weighted order statistics record (mdfit_map_quant): float64 [T][3][NMAPQUANT], rows PMD-all, forward, reverse;
+# khat, ess and flags are the psis record's (MAPPSIS_* bits)
+NMAPQUANT = 16
+MAPQUANT_FIELDS = ["D_max_median", "D_max_lo", "D_max_hi", "D_max_q05", "D_max_q95", "D_max_p_above", "q_median",
+                   "q_lo", "q_hi", "A_median", "c_median", "phi_median", "khat", "ess", "n_window", "flags"]
+# the quant block that leaves the device (ChunkedFitter quantiles): float32 [T][NQUANTOUT] = the three rows
+NQUANTOUT = 3 * NMAPQUANT
+NQUANTRES = 8  # mdfit_weighted_order_stats: median, lo, hi, q05, q95, p_above, n_window, ok
+
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
     "mdfit_default_opts",
@@ -179,6 +188,9 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_pred_adapt",
     "mdfit_map_ppc",
     "mdfit_map_ppc_adapt",
+    "mdfit_map_quant",
+    "mdfit_map_quant_adapt",
+    "mdfit_weighted_order_stats",
     "mdfit_resample",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
@@ -300,6 +312,14 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.mdfit_map_ppc_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp,
                                             vp, vp, vp]
         lib.mdfit_map_ppc_adapt.restype = ctypes.c_int
+    if hasattr(lib, "mdfit_map_quant"):  # (absent from the parent builds loaded by tools/ for A/B)
+        f64 = ctypes.c_double
+        lib.mdfit_map_quant.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, f64, vp, vp, vp]
+        lib.mdfit_map_quant.restype = ctypes.c_int
+        lib.mdfit_map_quant_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, f64, vp, vp, vp, vp]
+        lib.mdfit_map_quant_adapt.restype = ctypes.c_int
+        lib.mdfit_weighted_order_stats.argtypes = [vp, vp, i64, i32, f64, vp, vp]
+        lib.mdfit_weighted_order_stats.restype = ctypes.c_int
     lib.mdfit_resample.argtypes = [vp, i64, i32, i32, vp, vp, vp]
     lib.mdfit_resample.restype = ctypes.c_int
     lib.mdfit_psis_weights.argtypes = [vp, i64, i32, vp, vp, vp]

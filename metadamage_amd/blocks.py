@@ -7,6 +7,8 @@ engine and its columns in fits.make_df_fit_results.  In the gather record and
 in the returned tuples the block follows the base record (out, pred, status);
 behind it come the tail blocks, which are no entries: ppc (f32 [42], only with
 ppred: the posterior predictive check rides with the predictive it checks),
+quant (f32 [48], only with psis: the weighted order statistics ride with the
+posterior they summarise),
 auto-pred (f32 [2], only with auto), then adapt (f32 [2], psis_adapt > 0 with a
 `sampled` block).
 """

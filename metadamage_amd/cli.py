@@ -76,6 +76,11 @@ def cli_fit(
     ppc: bool = typer.Option(False, "--ppc", help="map-pred: the posterior predictive check of the damage model -- "
                              "p-values for an outlying position and for a strand difference, the worst position, "
                              "and a per-position p-value in fit_predictions"),
+    quantiles: bool = typer.Option(False, "--quantiles", help="map-psis: the importance-weighted posterior median, "
+                                   "68 % HPDI and 5 % / 95 % quantiles of D_max, the median and HPDI of q, the "
+                                   "medians of A, c and the concentration, and P(D_max > --dmax-threshold)"),
+    dmax_threshold: float = typer.Option(0.01, help="map-psis with --quantiles: the threshold of D_max_prob_above, "
+                                         "0 to 1"),
 ):
     """Fitting Ancient Damage.
 
@@ -101,6 +106,8 @@ def cli_fit(
         "psis_adapt": psis_adapt,
         "auto_pred": auto_pred,
         "ppc": ppc,
+        "quantiles": quantiles,
+        "dmax_threshold": dmax_threshold,
     }
     if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "map-evidence", "nuts-diag",
                          "nuts-summary", "nuts-loo", "auto"):
@@ -118,6 +125,10 @@ def cli_fit(
         raise typer.BadParameter("--auto-pred goes with --inference auto")
     if ppc and inference != "map-pred":
         raise typer.BadParameter("--ppc goes with --inference map-pred")
+    if quantiles and inference != "map-psis":
+        raise typer.BadParameter("--quantiles goes with --inference map-psis")
+    if not 0.0 <= dmax_threshold <= 1.0:
+        raise typer.BadParameter("--dmax-threshold must be in [0, 1]")
     cfg = utils.Config(**d_cfg)
     cfg.add_filenames(filenames)
     # launched by torchrun (WORLD_SIZE > 1): one rank per GPU, the rank's GPU

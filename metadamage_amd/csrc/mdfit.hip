@@ -1878,6 +1878,22 @@ int launch_map_ppc(const uint32_t* y, const uint32_t* N, const double* out, cons
                                seed, index_base, ppos, rec, adapt, index, counts, disc, (hipStream_t)hip_stream);
 }
 
+// (both instantiations of map_quant_kernel are launched from their own unit, mdfit_mapquant.hip)
+// d0: the exceedance threshold, finite and in [0, 1]
+bool quant_d0_ok(double d0) { return d0 >= 0.0 && d0 <= 1.0; }
+
+template <bool kAdapt>
+int launch_map_quant(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                     int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base, double d0,
+                     double* quant, double* adapt, double* values, void* hip_stream) {
+  if (!quant_d0_ok(d0)) return set_err(MDFIT_E_ARG, "d0 must be in [0, 1]");
+  const int rc = check_is_args(false, n_taxa, num_draws, nullptr, &adapt_rounds, y && N && out && status && quant);
+  if (rc <= 0) return rc;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  return mdfit::mapquant::launch(kAdapt, y, N, out, status, n_taxa, (int)num_draws, (int)adapt_rounds, seed,
+                                 index_base, d0, quant, adapt, values, (hipStream_t)hip_stream);
+}
+
 // mdfit_nuts_diag, _summary, _loo and _post: the checks on n_taxa and on the
 // options of the NUTS call, in their order.  needs_mode: the entry's message
 // for any other mode; ptrs: the required pointers are all there.  Returns as
@@ -2307,6 +2323,29 @@ int mdfit_map_ppc_adapt(const uint32_t* y, const uint32_t* N, const double* out,
                         void* hip_stream) {
   return launch_map_ppc<true>(y, N, out, status, n_taxa, num_draws, num_pred, adapt_rounds, seed, index_base, ppos,
                               rec, adapt, index, counts, disc, hip_stream);
+}
+
+int mdfit_map_quant(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status, int64_t n_taxa,
+                    int32_t num_draws, uint64_t seed, int64_t index_base, double d0, double* quant, double* values,
+                    void* hip_stream) {
+  return launch_map_quant<false>(y, N, out, status, n_taxa, num_draws, 0, seed, index_base, d0, quant, nullptr, values,
+                                 hip_stream);
+}
+
+int mdfit_map_quant_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                          int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed, int64_t index_base,
+                          double d0, double* quant, double* adapt, double* values, void* hip_stream) {
+  return launch_map_quant<true>(y, N, out, status, n_taxa, num_draws, adapt_rounds, seed, index_base, d0, quant, adapt,
+                                values, hip_stream);
+}
+
+int mdfit_weighted_order_stats(const double* v, const double* w, int64_t n_series, int32_t S, double d0, double* res,
+                               void* hip_stream) {
+  if (!quant_d0_ok(d0)) return set_err(MDFIT_E_ARG, "d0 must be in [0, 1]");
+  const int rc = check_is_args(true, n_series, S, nullptr, nullptr, v && w && res);
+  if (rc <= 0) return rc;
+  mdfit::host::debug_poison((hipStream_t)hip_stream);
+  return mdfit::mapquant::launch_series(v, w, n_series, (int)S, d0, res, (hipStream_t)hip_stream);
 }
 
 int mdfit_log_mean_weight(const double* lw, int64_t n_series, int32_t S, double* logz, double* se, double* khat,

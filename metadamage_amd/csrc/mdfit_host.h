@@ -1,7 +1,8 @@
 // mdfit_host.h — host-side helpers shared by the translation units of
 // libmdfit.so (mdfit.hip: C-ABI + MAP kernels, mdfit_nuts.hip: sampling mode,
 // mdfit_mappred_adapt.hip: the adapting predictive kernel, mdfit_mapppc.hip:
-// the posterior predictive check).
+// the posterior predictive check, mdfit_mapquant.hip: the weighted order
+// statistics).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -81,6 +82,16 @@ int launch(bool adapting, const uint32_t* y, const uint32_t* N, const double* ou
            int64_t n_taxa, int S, int R, int adapt_rounds, uint64_t seed, int64_t index_base, float* ppos, double* rec,
            double* adapt, int32_t* index, uint32_t* counts, double* disc, hipStream_t s);
 }  // namespace mdfit::mapppc
+
+namespace mdfit::mapquant {
+// mdfit_map_quant's and mdfit_map_quant_adapt's launch (mdfit_mapquant.hip:
+// both instantiations of map_quant_kernel) and mdfit_weighted_order_stats';
+// the arguments are checked by the caller
+int launch(bool adapting, const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+           int64_t n_taxa, int S, int adapt_rounds, uint64_t seed, int64_t index_base, double d0, double* quant,
+           double* adapt, double* values, hipStream_t s);
+int launch_series(const double* v, const double* w, int64_t n_series, int S, double d0, double* res, hipStream_t s);
+}  // namespace mdfit::mapquant
 
 namespace mdfit::nuts {
 // sampling mode (mdfit_nuts.hip): workspace = 256 B of queue counters, then

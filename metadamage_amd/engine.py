@@ -41,7 +41,8 @@ class FitBatch:
     # split_ppred; auto: fit_auto_chunks), and the tail blocks behind it:
     # adapt float32 [T, NADAPTOUT], largest round-0 khat, largest best round (psis_adapt > 0);
     # auto_pred float32 [T, NAUTOPRED], pred_ess_min, pred_distinct_min (auto with auto_pred);
-    # ppc float32 [T, NPPCOUT] = ppos | rec, the posterior predictive check (ppred with ppc; split_ppc)
+    # ppc float32 [T, NPPCOUT] = ppos | rec, the posterior predictive check (ppred with ppc; split_ppc);
+    # quant float32 [T, NQUANTOUT], the three rows of the weighted order statistics (psis with quantiles)
     lap: "object" = None
     diag: "object" = None
     summ: "object" = None
@@ -54,6 +55,7 @@ class FitBatch:
     auto_pred: "object" = None
     evid: "object" = None
     ppc: "object" = None
+    quant: "object" = None
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -213,6 +215,77 @@ def map_psis_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
                                   ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
                                   _stream_handle(torch, stream)))
     return psis if draws is None else (psis, draws)
+
+
+def map_quant_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0,
+                     d0: float = 0.01, quant=None, values=None, stream=None, adapt_rounds: int = 0, adapt=None):
+    """Launch mdfit_map_quant on the records of a finished MAP call (asynchronous
+    on `stream`): the weighted median, 68 % HPDI, quantiles and P(D_max > d0) of
+    the importance-sampled posterior of the three PMD sub-fits (MDFIT-QUANT v1),
+    float64 quant[T, 3, NMAPQUANT] (_lib.MAPQUANT_FIELDS).  The draws, weights,
+    khat, ess and flags are map_psis_device's at the same (seed, index_base,
+    num_draws, adapt_rounds).  values: None, True (allocated) or a float64
+    tensor [T, 3, num_draws, 6] = D_max, q, A, c, phi and the smoothed weight of
+    each draw.  Returns quant, or (quant, values) when values is asked for.
+
+    adapt_rounds > 0, or adapt given (True, or a float64 tensor [T, 3,
+    NMAPADAPT]): mdfit_map_quant_adapt; the adapt block is then the last element
+    of the returned tuple.  adapt=False: the rounds without their record (the
+    chunked dispatch, whose map_psis launch has written it)."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
+    no_record = adapt is False
+    adapt = None if no_record else adapt
+    use_adapt = R != 0 or adapt is not None
+    if use_adapt and not no_record and (adapt is None or adapt is True):
+        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
+    if quant is None:
+        quant = torch.empty((T, 3, _lib.NMAPQUANT), dtype=torch.float64, device=ty.device)
+    if values is True:
+        values = torch.empty((T, 3, S, 6), dtype=torch.float64, device=ty.device)
+    for name, t, n in (("quant", quant, T * 3 * _lib.NMAPQUANT), ("values", values, T * 3 * S * 6),
+                       ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    head = [ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
+            ctypes.c_void_p(res.status.data_ptr()), T, S]
+    tap = ctypes.c_void_p(values.data_ptr()) if values is not None else None
+    got = quant if values is None else (quant, values)
+    if use_adapt:
+        _lib.check(lib.mdfit_map_quant_adapt(*head, R, int(seed), int(index_base), float(d0),
+                                             ctypes.c_void_p(quant.data_ptr()),
+                                             ctypes.c_void_p(adapt.data_ptr()) if adapt is not None else None, tap,
+                                             _stream_handle(torch, stream)))
+        if adapt is None:
+            return got
+        return (quant, adapt) if values is None else (quant, values, adapt)
+    _lib.check(lib.mdfit_map_quant(*head, int(seed), int(index_base), float(d0), ctypes.c_void_p(quant.data_ptr()),
+                                   tap, _stream_handle(torch, stream)))
+    return got
+
+
+def weighted_order_stats(v, w, d0: float = 0.01, device="cuda"):
+    """res[n, 8] float64 (host) = median, lo, hi, q05, q95, p_above, n_window, ok
+    of the series v[n, S] under the weights w[n, S] by the device's weighted
+    order statistics (MDFIT-QUANT v1, mdfit_weighted_order_stats)."""
+    torch = _torch()
+    lib = _lib.load()
+    tv = torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64), device=device)
+    tw = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64), device=device)
+    n, S = int(tv.shape[0]), int(tv.shape[1])
+    if tuple(tw.shape) != (n, S):
+        raise ValueError("v and w must have one shape [n, S]")
+    res = torch.empty((n, _lib.NQUANTRES), dtype=torch.float64, device=device)
+    _lib.check(lib.mdfit_weighted_order_stats(ctypes.c_void_p(tv.data_ptr()), ctypes.c_void_p(tw.data_ptr()), n, S,
+                                              float(d0), ctypes.c_void_p(res.data_ptr()),
+                                              _stream_handle(torch, None)))
+    return res.cpu().numpy()
 
 
 def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, waic=None,
@@ -1026,6 +1099,20 @@ def _check_ppc(ppc: bool, block) -> bool:
     return bool(ppc)
 
 
+QUANT_BYTES = _lib.NQUANTOUT * 4  # one taxon's weighted order statistics as they leave the device (f32) ...
+_QUANT_DEVICE_BYTES = _lib.NQUANTOUT * 8  # ... and as the launch computes them (f64)
+
+
+def _check_quant(quantiles: bool, block, dmax_threshold: float = 0.01) -> bool:
+    """quantiles (the weighted order statistics, a tail of the psis block) goes with with_psis; dmax_threshold, the
+    exceedance threshold, is finite and in [0, 1]."""
+    if quantiles and (block is None or block.name != "psis"):
+        raise ValueError("quantiles needs with_psis: the order statistics are of the posterior mdfit_map_psis forms")
+    if quantiles and not 0.0 <= float(dmax_threshold) <= 1.0:
+        raise ValueError("dmax_threshold must be in [0, 1]")
+    return bool(quantiles)
+
+
 def _chunked_block(opts, switches):
     """blocks.resolve for the chunked dispatch: the run's one block, or None."""
     block = blocks.resolve(opts, **switches)
@@ -1046,7 +1133,8 @@ def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
 
 
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
-                 dest_on_device: bool = False, ppc: bool = False, **switches) -> int:
+                 dest_on_device: bool = False, ppc: bool = False, quantiles: bool = False,
+                 dmax_threshold: float = 0.01, **switches) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -1055,10 +1143,12 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     with_* of blocks.BLOCKS, checked by blocks.resolve): the run's block as the
     launch computes it and -- unless it goes to the caller's device buffer --
     as it leaves, rounded to f32.  ppc (with with_ppred): the check's block in
-    the same two forms."""
+    the same two forms; quantiles (with with_psis): the weighted order
+    statistics' block in the same two forms."""
     C = int(C)
     block = _chunked_block(opts, switches)
     ppc = _check_ppc(ppc, block)
+    quantiles = _check_quant(quantiles, block, dmax_threshold)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
@@ -1066,21 +1156,26 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
         b += C * (block.device_bytes + (0 if dest_on_device else block.out_bytes))
     if ppc:
         b += C * (_PPC_DEVICE_BYTES + (0 if dest_on_device else PPC_BYTES))
+    if quantiles:
+        b += C * (_QUANT_DEVICE_BYTES + (0 if dest_on_device else QUANT_BYTES))
     return b + workspace_bytes(C, opts)
 
 
 def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | None = None, *,
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
-                dest_on_device: bool = False, ppc: bool = False, **switches) -> list[tuple[int, int]]:
+                dest_on_device: bool = False, ppc: bool = False, quantiles: bool = False,
+                dmax_threshold: float = 0.01, **switches) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk (device_bytes, with the run's block of
-    switches and ppc) fit in budget_bytes (None: no memory bound), no chunk exceeds the
+    switches, ppc and quantiles) fit in budget_bytes (None: no memory bound), no chunk exceeds the
     per-call limit (2^25 taxa) or chunk_taxa (> 0; env MDFIT_CHUNK_TAXA when 0).
     Taxa are independent and the sampler's streams are keyed by the global taxon
     index (opts.index_base + lo), so any split gives the records of one call bit
     for bit."""
     T = int(T)
-    _check_ppc(ppc, _chunked_block(opts, switches))
+    block = _chunked_block(opts, switches)
+    _check_ppc(ppc, block)
+    _check_quant(quantiles, block, dmax_threshold)
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -1090,7 +1185,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
         def per(c):
-            return n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, ppc, **switches)
+            return n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, ppc, quantiles, **switches)
 
 
         if per(1) > budget_bytes:
@@ -1124,7 +1219,8 @@ class _Set:
     run one after another on the compute stream)."""
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
-                 block: blocks.Block | None = None, with_adapt: bool = False, ppc: bool = False):
+                 block: blocks.Block | None = None, with_adapt: bool = False, ppc: bool = False,
+                 quantiles: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -1151,6 +1247,11 @@ class _Set:
                                  torch.empty((C, _lib.NMAPPPC), dtype=torch.float64, device=device))
             if not dest_on_device:
                 self.ppc = torch.empty((C, _lib.NPPCOUT), dtype=torch.float32, device=device)
+        self.quant_computed = self.quant = None
+        if quantiles:  # as mdfit_map_quant writes it (f64), and as one f32 block for the way out
+            self.quant_computed = torch.empty((C, 3, _lib.NMAPQUANT), dtype=torch.float64, device=device)
+            if not dest_on_device:
+                self.quant = torch.empty((C, _lib.NQUANTOUT), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -1243,13 +1344,23 @@ class ChunkedFitter:
     rounds when psis_adapt > 0) follows the chunk's map_pred launch on the
     compute stream -- no further stream --, and one more f32 block [T, NPPCOUT]
     = ppos | rec (split_ppc), rounded on the device, leaves behind the block and
-    before adapt (run; dest.ppc)."""
+    before adapt (run; dest.ppc).
+
+    quantiles (with with_psis): mdfit_map_quant (mdfit_map_quant_adapt with the
+    same rounds when psis_adapt > 0) follows the chunk's map_psis launch on the
+    compute stream with the same draws, seed and index_base and the exceedance
+    threshold dmax_threshold, and one more f32 block [T, NQUANTOUT] = the three
+    rows of _lib.MAPQUANT_FIELDS, rounded on the device, leaves behind the block
+    and before adapt (run; dest.quant)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, psis_draws: int = PSIS_DRAWS,
-                 pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, **switches):
+                 pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False,
+                 dmax_threshold: float = 0.01, **switches):
         self.block = _chunked_block(opts, switches)
         self.ppc = _check_ppc(ppc, self.block)
+        self.quantiles = _check_quant(quantiles, self.block, dmax_threshold)
+        self.dmax_threshold = float(dmax_threshold)
         torch = _torch()
         self.psis_adapt = _check_psis_adapt(psis_adapt, self.block is not None and self.block.sampled)
         self.pred_draws = int(pred_draws)
@@ -1258,14 +1369,14 @@ class ChunkedFitter:
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.block,
-                          self.psis_adapt > 0, self.ppc)
+                          self.psis_adapt > 0, self.ppc, self.quantiles)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = None
-        self.h_block = self.h_adapt = self.h_ppc = None
+        self.h_block = self.h_adapt = self.h_ppc = self.h_quant = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -1287,6 +1398,8 @@ class ChunkedFitter:
                 self.h_adapt = torch.empty((cap, _lib.NADAPTOUT), dtype=torch.float32).pin_memory()
             if self.ppc:
                 self.h_ppc = torch.empty((cap, _lib.NPPCOUT), dtype=torch.float32).pin_memory()
+            if self.quantiles:
+                self.h_quant = torch.empty((cap, _lib.NQUANTOUT), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -1322,6 +1435,8 @@ class ChunkedFitter:
             raise ValueError("psis_adapt: dest.adapt (float32 [T, NADAPTOUT]) required")
         if self.ppc and dest is not None and getattr(dest, "ppc", None) is None:
             raise ValueError("ppc: dest.ppc (float32 [T, NPPCOUT]) required")
+        if self.quantiles and dest is not None and getattr(dest, "quant", None) is None:
+            raise ValueError("quantiles: dest.quant (float32 [T, NQUANTOUT]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -1364,7 +1479,7 @@ class ChunkedFitter:
                 _lib.check(lib.mdfit_noise(ctypes.c_void_p(st.d_y.data_ptr()), ctypes.c_void_p(st.d_N.data_ptr()),
                                            ctypes.c_void_p(st.d_mm.data_ptr()), n, ctypes.c_void_p(res.out.data_ptr()),
                                            h_s))
-            block32 = adapt32 = ppc32 = None
+            block32 = adapt32 = ppc32 = quant32 = None
             if block is not None:  # the records are final: the block's launch, then one f32 block for the way out
                 ad_kw = {"adapt_rounds": self.psis_adapt, "adapt": st.adapt64[:n]} if self.psis_adapt > 0 else {}
                 _LAUNCH[block.name](self, st, n, res, o, comp, ad_kw)
@@ -1387,6 +1502,13 @@ class ChunkedFitter:
                 with torch.cuda.stream(comp):
                     for view, computed in zip(split_ppc(ppc32), st.ppc_computed):
                         view.copy_(computed[:n])
+            if self.quantiles:  # the order statistics of the posterior just formed: the same draws, rounds and stream
+                map_quant_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
+                                 self.dmax_threshold, quant=st.quant_computed[:n], stream=comp,
+                                 **({"adapt_rounds": self.psis_adapt, "adapt": False} if self.psis_adapt > 0 else {}))
+                quant32 = dest.quant[lo:hi] if dest is not None else st.quant[:n]
+                with torch.cuda.stream(comp):
+                    quant32.copy_(st.quant_computed[:n].reshape(n, _lib.NQUANTOUT))
             if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
                 adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
                 with torch.cuda.stream(comp):
@@ -1405,6 +1527,8 @@ class ChunkedFitter:
                         self.h_block[lo:hi].copy_(block32, non_blocking=True)
                     if ppc32 is not None:
                         self.h_ppc[lo:hi].copy_(ppc32, non_blocking=True)
+                    if quant32 is not None:
+                        self.h_quant[lo:hi].copy_(quant32, non_blocking=True)
                     if adapt32 is not None:
                         self.h_adapt[lo:hi].copy_(adapt32, non_blocking=True)
                 last_d2h = cp
@@ -1416,7 +1540,8 @@ class ChunkedFitter:
     def run(self, y, N, mm=None, opts: _lib.MdfitOpts | None = None, sync: bool = True,
             pinned: PinnedPack | None = None, chunks=None):
         """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status[, the
-        run's block f32 [T, *shape]][, ppc f32 [T, NPPCOUT]][, adapt f32 [T, 2]]) of the pinned buffers
+        run's block f32 [T, *shape]][, ppc f32 [T, NPPCOUT]][, quant f32 [T, NQUANTOUT]][, adapt f32 [T, 2]]) of the
+        pinned buffers
         (valid until the next run).  pinned: y, N, mm are that PinnedPack's
         views.  chunks: the split (default plan_chunks at this staging's
         chunk_cap)."""
@@ -1435,6 +1560,8 @@ class ChunkedFitter:
             got += (self.h_block[:T].numpy(),)
         if self.ppc:
             got += (self.h_ppc[:T].numpy(),)
+        if self.quantiles:
+            got += (self.h_quant[:T].numpy(),)
         if self.psis_adapt > 0:
             got += (self.h_adapt[:T].numpy(),)
         return got
@@ -1442,7 +1569,7 @@ class ChunkedFitter:
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
         (out[T, NOUT], pred, status -- and the run's block under its attribute,
-        ppc with ppc, adapt when psis_adapt > 0: rows written in place), ordered on the
+        ppc with ppc, quant with quantiles, adapt when psis_adapt > 0: rows written in place), ordered on the
         caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
@@ -1510,10 +1637,12 @@ _STAGING_LOCK = __import__("threading").Lock()
 
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
             dest_on_device: bool = False, budget_bytes: int | None = None, psis_draws: int = PSIS_DRAWS,
-            pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, **switches) -> ChunkedFitter:
+            pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False,
+            dmax_threshold: float = 0.01, **switches) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind, sampler length and the run's block
-    of switches with the draw counts it uses, psis_adapt and ppc): the
+    of switches with the draw counts it uses, psis_adapt, ppc and quantiles
+    with its threshold): the
     multi-file pipeline fits one file after another, and pinned + device
     buffers allocated per file cost more host time than the fit.  Its chunk
     capacity is the largest chunk N_SETS buffer sets of which fit the device
@@ -1532,7 +1661,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
            block.name if block is not None else None,
            int(psis_draws) if block is not None and block.sampled else 0,
            int(pred_draws) if block is not None and block.name == "ppred" else 0, int(psis_adapt),
-           _check_ppc(ppc, block))
+           _check_ppc(ppc, block),
+           float(dmax_threshold) if _check_quant(quantiles, block, dmax_threshold) else None)
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1549,10 +1679,11 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     if T < _lib.STREAM_MAX_TAXA:
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
-                      ppc=ppc, **switches)[0]
+                      ppc=ppc, quantiles=quantiles, dmax_threshold=dmax_threshold, **switches)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
-                       psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, **switches)
+                       psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
+                       quantiles=quantiles, dmax_threshold=dmax_threshold, **switches)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1561,22 +1692,25 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, psis_draws: int = PSIS_DRAWS, pred_draws: int = PRED_DRAWS,
-                   psis_adapt: int = 0, ppc: bool = False, **named):
+                   psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False, dmax_threshold: float = 0.01,
+                   **named):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     named (one chunked block of blocks.BLOCKS by its name, e.g. laplace=True), a
     fourth array, the block's f32 [T, *shape] --, chunked through the device
     budget (ChunkedFitter, which documents psis_draws, pred_draws and
     psis_adapt; psis_adapt > 0 returns a fifth array adapt[T, 2] f32,
     _lib.ADAPTOUT_FIELDS; ppc, with ppred=True, the check's f32 [T, NPPCOUT]
-    behind the block and before adapt).  mm goes to the device (the assembly computes the
+    behind the block and before adapt; quantiles, with psis=True, the weighted
+    order statistics' f32 [T, NQUANTOUT] in the same place, P(D_max >
+    dmax_threshold) among them).  mm goes to the device (the assembly computes the
     noise columns); without it, `noise` (float64[T][3], ingest.noise) fills them
     when given.  pinned: y, N, mm are views of that PinnedPack (copied to the
     device from there)."""
     T = int(y.shape[0])
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, psis_draws=psis_draws,
-                     pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
-                     **{"with_" + k: v for k, v in named.items()})
+                     pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, quantiles=quantiles,
+                     dmax_threshold=dmax_threshold, **{"with_" + k: v for k, v in named.items()})
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         got = tuple(a.copy() for a in got)
     out, status = got[0], got[2]

@@ -106,6 +106,21 @@ MAP_PSIS_COLUMNS = [name for name, _, _ in _MAP_PSIS_PICKS]
 # ... then uint32 map_psis_valid (all three rows valid) and map_psis_reliable
 # (valid, and all three khat at or below the threshold)
 MAP_PSIS_UINT_COLUMNS = ["map_psis_valid", "map_psis_reliable"]
+# "map-psis" with quantiles (mdfit_map_quant, MDFIT-QUANT v1): behind map-psis's columns the weighted
+# order statistics of that posterior, float32 -- (column, row of the record, its field).  The first seven are
+# "nuts-summary"'s names in its order
+_MAP_QUANT_PICKS = [("D_max_posterior_median", 0, "D_max_median"), ("D_max_posterior_lower_hpdi", 0, "D_max_lo"),
+                    ("D_max_posterior_upper_hpdi", 0, "D_max_hi"), ("q_median", 0, "q_median"),
+                    ("q_lower_hpdi", 0, "q_lo"), ("q_upper_hpdi", 0, "q_hi"),
+                    ("concentration_median", 0, "phi_median"), ("A_median", 0, "A_median"),
+                    ("c_median", 0, "c_median"), ("D_max_posterior_q05", 0, "D_max_q05"),
+                    ("D_max_posterior_q95", 0, "D_max_q95"), ("D_max_prob_above", 0, "D_max_p_above"),
+                    ("D_max_posterior_median_forward", 1, "D_max_median"),
+                    ("D_max_posterior_median_reverse", 2, "D_max_median")]
+MAP_QUANT_COLUMNS = [name for name, _, _ in _MAP_QUANT_PICKS]
+# ... then uint32 quant_window_min (the least number of draws in D_max's interval over the three rows; 0 when a row
+# has none) and map_quant_valid (all three rows valid)
+MAP_QUANT_UINT_COLUMNS = ["quant_window_min", "map_quant_valid"]
 # "map-waic": the importance-weighted WAIC comparison appended after shortname
 # (DESIGN.md §3.9), float32 -- (column, row of the record: 0 PMD-all, 1 null-all,
 # 6 the comparisons, its field index) ...
@@ -346,7 +361,8 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # the device call (single GPU or sharded over torch.distributed ranks)
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, pred_draws: int = 1000,
-               psis_adapt: int = 0, auto_pred: bool = False, ppc: bool = False, **named):
+               psis_adapt: int = 0, auto_pred: bool = False, ppc: bool = False, quantiles: bool = False,
+               dmax_threshold: float = 0.01, **named):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -367,7 +383,10 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, 
     (pred_ess_min, pred_distinct_min) is returned behind the auto block.  ppc
     (with ppred; MDFIT-PPC v1): mdfit_map_ppc follows each chunk's map_pred
     launch and ppc[T, 42] f32 = ppos | rec is returned directly behind the
-    ppred block."""
+    ppred block.  quantiles (with psis; MDFIT-QUANT v1): mdfit_map_quant follows
+    each chunk's map_psis launch and quant[T, 48] f32, the three rows of
+    _lib.MAPQUANT_FIELDS with P(D_max > dmax_threshold), is returned directly
+    behind the psis block."""
     import torch
 
     from . import engine
@@ -395,21 +414,24 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, 
     if auto_pred and not auto:
         raise ValueError("auto_pred goes with the auto inference")
     ppc = engine._check_ppc(ppc, block)
+    quantiles = engine._check_quant(quantiles, block, dmax_threshold)
     try:
         if grouped:
-            return _fit_sharded(p, opts, dev, rank, world, block, psis_draws, pred_draws, psis_adapt, auto_pred, ppc)
+            return _fit_sharded(p, opts, dev, rank, world, block, psis_draws, pred_draws, psis_adapt, auto_pred, ppc,
+                                quantiles, dmax_threshold)
         if auto:
             return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt,
                                           auto_pred=auto_pred, pred_draws=pred_draws)
         return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, psis_draws=psis_draws,
-                                     pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, **named)
+                                     pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, quantiles=quantiles,
+                                     dmax_threshold=dmax_threshold, **named)
     finally:
         p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Block | None = None,
                  psis_draws: int = 256, pred_draws: int = 1000, psis_adapt: int = 0, auto_pred: bool = False,
-                 ppc: bool = False):
+                 ppc: bool = False, quantiles: bool = False, dmax_threshold: float = 0.01):
     import torch
 
     from . import engine
@@ -423,13 +445,14 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
     switch = {block.switch: True} if block is not None else {}
     ppred = block is not None and block.name == "ppred"  # (its adapt tail has a switch of its own)
     layout = dict(switch, with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                  with_auto_pred=auto_pred, with_ppc=ppc)
+                  with_auto_pred=auto_pred, with_ppc=ppc, with_quant=quantiles)
     rec = alloc_records(cap, dev, **layout)
     # the rows are written in place into the gather buffers
     dest = engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
                            adapt=rec.adapt[: hi - lo] if psis_adapt > 0 else None,
                            auto_pred=rec.auto_pred[: hi - lo] if auto_pred else None,
                            ppc=rec.ppc[: hi - lo] if ppc else None,
+                           quant=rec.quant[: hi - lo] if quantiles else None,
                            **({block.attr: getattr(rec, block.attr)[: hi - lo]} if block is not None else {}))
     if hi > lo and block is not None and not block.chunked:  # each rank runs auto on its shard
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
@@ -440,7 +463,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
                                 psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
-                                **switch)
+                                quantiles=quantiles, dmax_threshold=dmax_threshold, **switch)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, dest)
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
@@ -507,7 +530,7 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
 
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
                         psis=None, waic=None, auto=None, ppred=None, adapt=None, auto_pred=None,
-                        evid=None, ppc=None) -> pd.DataFrame:
+                        evid=None, ppc=None, quant=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -532,7 +555,9 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     "auto" run with auto_pred): pred_ess_min (float32) and pred_distinct_min
     (uint32) follow the auto columns.  ppc (the posterior predictive check's
     block [T, 42] of a "map-pred" run with ppc): the PPC_COLUMNS follow
-    map-pred's, in their own dtypes.  adapt (the adapt block [T, 2] of a run with
+    map-pred's, in their own dtypes.  quant (the weighted order statistics'
+    block [T, 48] of a "map-psis" run with quantiles): the MAP_QUANT_COLUMNS
+    follow map-psis's as float32, then the MAP_QUANT_UINT_COLUMNS.  adapt (the adapt block [T, 2] of a run with
     psis_adapt > 0): pareto_k_initial (float32) and psis_adapt_rounds (uint32)
     are the last two columns."""
     n = int(keep.sum())
@@ -593,6 +618,16 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["map_psis_valid"] = valid.astype(np.uint32)
         data["map_psis_reliable"] = (valid & ((flags & _lib.MAPPSIS_RELIABLE) != 0).all(axis=1)).astype(np.uint32)
         columns += MAP_PSIS_COLUMNS + MAP_PSIS_UINT_COLUMNS
+    if quant is not None:
+        kq = np.asarray(quant).reshape(-1, 3, _lib.NMAPQUANT)
+        kq = kq if keep is None else kq[keep]
+        f = _lib.MAPQUANT_FIELDS.index
+        for name, row, field in _MAP_QUANT_PICKS:
+            data[name] = np.ascontiguousarray(kq[:, row, f(field)], dtype=np.float32)
+        data["quant_window_min"] = np.nan_to_num(kq[:, :, f("n_window")], nan=0.0).min(axis=1).astype(np.uint32)
+        flags = np.nan_to_num(kq[:, :, f("flags")]).astype(np.int64)
+        data["map_quant_valid"] = ((flags & _lib.MAPPSIS_VALID) != 0).all(axis=1).astype(np.uint32)
+        columns += MAP_QUANT_COLUMNS + MAP_QUANT_UINT_COLUMNS
     if waic is not None:
         kw = np.asarray(waic) if keep is None else np.asarray(waic)[keep]
         for name, row, field in _MAP_WAIC_PICKS:
@@ -799,6 +834,22 @@ def ppc_of(cfg) -> bool:
     return on
 
 
+def quantiles_of(cfg) -> bool:
+    """cfg.quantiles (default False): a "map-psis" run adds the weighted median, 68 % HPDI and quantiles of its
+    posterior (MDFIT-QUANT v1); with any other inference a ValueError naming the option."""
+    on = bool(getattr(cfg, "quantiles", False))
+    if on and not wants_psis(cfg):
+        raise ValueError("quantiles goes with inference 'map-psis'")
+    return on
+
+
+def dmax_threshold_of(cfg) -> float:
+    """The threshold d0 of D_max_prob_above = P(D_max > d0) of a run with quantiles (cfg.dmax_threshold, default
+    0.01)."""
+    v = getattr(cfg, "dmax_threshold", 0.01)
+    return 0.01 if v is None else float(v)
+
+
 def _split_rest(cfg, rest):
     """The optional arrays behind (out, pred, status) of fit_packed: (the run's extra block or None, auto_pred or
     None, adapt or None) -- the auto-pred block follows the extra block, the adapt block is last."""
@@ -821,15 +872,19 @@ def _fit_for_frames(p: Packed, cfg, opts, shard: bool):
     block = next((b for b in blocks.BLOCKS if b.inference == inference), None)
     res = fit_packed(p, opts, shard=shard, psis_draws=psis_draws_of(cfg), pred_draws=pred_draws_of(cfg),
                      psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg), ppc=ppc_of(cfg),
+                     quantiles=quantiles_of(cfg), dmax_threshold=dmax_threshold_of(cfg),
                      **({block.name: True} if block is not None else {}))
     if res is None:
         return None
     out, pred, status, *rest = res
     ppc = rest.pop(1) if ppc_of(cfg) else None  # (directly behind the ppred block)
+    quant = rest.pop(1) if quantiles_of(cfg) else None  # (directly behind the psis block)
     extra, auto_pred, adapt = _split_rest(cfg, rest)
     kw = {"adapt": adapt, "auto_pred": auto_pred}
     if ppc is not None:
         kw["ppc"] = ppc
+    if quant is not None:
+        kw["quant"] = quant
     if block is not None:
         kw[block.attr] = extra
     keep = status == _lib.OK
@@ -899,7 +954,7 @@ def _rank() -> int:
 
 CACHE_KEYS = ["min_alignments", "min_y_sum", "substitution_bases_forward", "substitution_bases_reverse",
               "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws", "psis_adapt", "auto_pred",
-              "ppc"]
+              "ppc", "quantiles", "dmax_threshold"]
 
 
 def _cache_hit(cfg) -> bool:

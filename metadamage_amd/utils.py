@@ -77,11 +77,19 @@ class Config:
     # "map-pred": the posterior predictive check of the PMD fit (MDFIT-PPC v1) beside the predictive; in the metadata
     # and the cache key only when set
     ppc: bool = False
+    # "map-psis": the weighted median, 68 % HPDI and quantiles of the importance-sampled posterior (MDFIT-QUANT v1)
+    # and P(D_max > dmax_threshold); both in the metadata and the cache key only when quantiles is set
+    quantiles: bool = False
+    dmax_threshold: float = 0.01
     N_cores: int = field(init=False)
 
     def __post_init__(self):
         if self.ppc and self.inference != "map-pred":
             raise ValueError("ppc goes with inference 'map-pred'")
+        if self.quantiles and self.inference != "map-psis":
+            raise ValueError("quantiles goes with inference 'map-psis'")
+        if self.quantiles and not 0.0 <= float(self.dmax_threshold) <= 1.0:
+            raise ValueError("dmax_threshold must be in [0, 1]")
         self._set_N_cores()
 
     def _set_N_cores(self):
@@ -154,6 +162,9 @@ class Config:
             del d_out["auto_pred"]
         if not self.ppc:
             del d_out["ppc"]
+        if not self.quantiles:
+            del d_out["quantiles"]
+            del d_out["dmax_threshold"]
         for key, val in d_out.items():
             if isinstance(val, Path):
                 d_out[key] = str(val)
