@@ -964,6 +964,46 @@ int mdfit_map_quant_adapt(const uint32_t* y, const uint32_t* N, const double* ou
 int mdfit_weighted_order_stats(const double* v, const double* w, int64_t n_series, int32_t S, double d0,
                                double* res, void* hip_stream);
 
+/*
+ * The WAIC comparison, the evidence and the posterior of a finished MODE_MAP
+ * call from one launch.  Per sub-fit the proposal, draws,
+ * raw log-weights and Pareto smoothing are formed once, as mdfit_map_waic forms
+ * them, and the three records are taken from those weights by the row
+ * functions of the three entries.  At equal num_draws, seed and index_base
+ *   waic, pointwise and draws are mdfit_map_waic's,
+ *   evid is mdfit_map_evidence's,
+ *   psis is mdfit_map_psis's (rows PMD-all, PMD-forward, PMD-reverse from the
+ *        sub-fits 0, 2 and 3)
+ * bit for bit, NaN rows and flags included.
+ *   y, N, out, status : those of the MODE_MAP call (device; read only)
+ *   num_draws  : S in [25, 1024] (else MDFIT_E_ARG)
+ *   waic       : double[n_taxa][7][MDFIT_NMAPWAIC]                 (device)
+ *   evid       : double[n_taxa][7][MDFIT_NMAPEVID]                 (device)
+ *   psis       : double[n_taxa][3][MDFIT_NMAPPSIS]                 (device)
+ *   pointwise  : as mdfit_map_waic's, or NULL                      (device)
+ *   draws      : as mdfit_map_waic's, or NULL                      (device)
+ * One launch on hip_stream, one wave per taxon; no workspace, no allocation,
+ * no side stream, no host synchronisation, no atomics; capturable in a graph.
+ * n_taxa: at most 2^25 per call.
+ */
+int mdfit_map_joint(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                    int64_t n_taxa, int32_t num_draws, uint64_t seed, int64_t index_base, double* waic,
+                    double* evid, double* psis, double* pointwise, double* draws, void* hip_stream);
+
+/*
+ * mdfit_map_joint with the rounds of mdfit_map_psis_adapt on the PMD rows: at
+ * equal num_draws, adapt_rounds, seed and index_base waic, pointwise, draws and
+ * adapt are mdfit_map_waic_adapt's, evid is mdfit_map_evidence_adapt's and psis
+ * is mdfit_map_psis_adapt's bit for bit.  With adapt_rounds = 0 the records are
+ * mdfit_map_joint's bit for bit.
+ *   adapt_rounds : R in [0, MDFIT_ADAPT_MAX_ROUNDS] (else MDFIT_E_ARG)
+ *   adapt      : double[n_taxa][3][MDFIT_NMAPADAPT], or NULL       (device)
+ */
+int mdfit_map_joint_adapt(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,
+                          int64_t n_taxa, int32_t num_draws, int32_t adapt_rounds, uint64_t seed,
+                          int64_t index_base, double* waic, double* evid, double* psis, double* adapt,
+                          double* pointwise, double* draws, void* hip_stream);
+
 /* Test helper: mdfit_map_pred's resampling of given weights w[n_series][S]
  * (>= 0, not all 0), one wave per series: idx[n_series][R] = s(r) and
  * n_distinct[n_series] (device pointers).  S, R in [25, 1024]. */

@@ -159,6 +159,10 @@ MAPQUANT_FIELDS = ["D_max_median", "D_max_lo", "D_max_hi", "D_max_q05", "D_max_q
 NQUANTOUT = 3 * NMAPQUANT
 NQUANTRES = 8  # mdfit_weighted_order_stats: median, lo, hi, q05, q95, p_above, n_window, ok
 
+# the joint block that leaves the device (ChunkedFitter joint, mdfit_map_joint): float32 [T][NJOINTOUT] = the seven
+# rows of the evidence record | the three rows of the psis record
+NJOINTOUT = NEVIDROW * NMAPEVID + 3 * NMAPPSIS
+
 # C-ABI symbols declared in include/mdfit.h
 EXPORTED_SYMBOLS = [
     "mdfit_default_opts",
@@ -191,6 +195,8 @@ EXPORTED_SYMBOLS = [
     "mdfit_map_quant",
     "mdfit_map_quant_adapt",
     "mdfit_weighted_order_stats",
+    "mdfit_map_joint",
+    "mdfit_map_joint_adapt",
     "mdfit_resample",
     "mdfit_betabinom_logpmf",
     "mdfit_special",
@@ -320,6 +326,12 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.mdfit_map_quant_adapt.restype = ctypes.c_int
         lib.mdfit_weighted_order_stats.argtypes = [vp, vp, i64, i32, f64, vp, vp]
         lib.mdfit_weighted_order_stats.restype = ctypes.c_int
+    if hasattr(lib, "mdfit_map_joint"):  # (absent from the parent builds loaded by tools/ for A/B)
+        lib.mdfit_map_joint.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp, vp]
+        lib.mdfit_map_joint.restype = ctypes.c_int
+        lib.mdfit_map_joint_adapt.argtypes = [vp, vp, vp, vp, i64, i32, i32, ctypes.c_uint64, i64, vp, vp, vp, vp, vp,
+                                              vp, vp]
+        lib.mdfit_map_joint_adapt.restype = ctypes.c_int
     lib.mdfit_resample.argtypes = [vp, i64, i32, i32, vp, vp, vp]
     lib.mdfit_resample.restype = ctypes.c_int
     lib.mdfit_psis_weights.argtypes = [vp, i64, i32, vp, vp, vp]

@@ -9,6 +9,8 @@ behind it come the tail blocks, which are no entries: ppc (f32 [42], only with
 ppred: the posterior predictive check rides with the predictive it checks),
 quant (f32 [48], only with psis: the weighted order statistics ride with the
 posterior they summarise),
+joint (f32 [104] = evid | psis, only with waic: the fused launch's other two
+records ride with the waic record whose weights they share),
 auto-pred (f32 [2], only with auto), then adapt (f32 [2], psis_adapt > 0 with a
 `sampled` block).
 """

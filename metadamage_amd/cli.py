@@ -81,6 +81,9 @@ def cli_fit(
                                    "medians of A, c and the concentration, and P(D_max > --dmax-threshold)"),
     dmax_threshold: float = typer.Option(0.01, help="map-psis with --quantiles: the threshold of D_max_prob_above, "
                                          "0 to 1"),
+    joint: bool = typer.Option(False, "--joint", help="map-waic: the evidence and Bayes factors of map-evidence and "
+                               "the posterior mean and std of map-psis from the same importance weights, in the "
+                               "same launch and the same fit_results file"),
 ):
     """Fitting Ancient Damage.
 
@@ -108,6 +111,7 @@ def cli_fit(
         "ppc": ppc,
         "quantiles": quantiles,
         "dmax_threshold": dmax_threshold,
+        "joint": joint,
     }
     if inference not in ("nuts", "map", "map-laplace", "map-psis", "map-waic", "map-pred", "map-evidence", "nuts-diag",
                          "nuts-summary", "nuts-loo", "auto"):
@@ -127,6 +131,8 @@ def cli_fit(
         raise typer.BadParameter("--ppc goes with --inference map-pred")
     if quantiles and inference != "map-psis":
         raise typer.BadParameter("--quantiles goes with --inference map-psis")
+    if joint and inference != "map-waic":
+        raise typer.BadParameter("--joint goes with --inference map-waic")
     if not 0.0 <= dmax_threshold <= 1.0:
         raise typer.BadParameter("--dmax-threshold must be in [0, 1]")
     cfg = utils.Config(**d_cfg)

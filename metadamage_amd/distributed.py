@@ -46,17 +46,20 @@ REC_LAP, REC_DIAG, REC_SUMM, REC_LOO, REC_PSIS, REC_WAIC, REC_EVID, REC_PPRED, R
 # check (with the ppred block: with_ppc) rides directly behind its block, before the other tails: one more f32 block
 # [n, NPPCOUT] = ppos | rec, 168 B per taxon.  So do the weighted order statistics (with the psis block: with_quant):
 # one more f32 block [n, NQUANTOUT] = the three rows of _lib.MAPQUANT_FIELDS, 192 B per taxon, directly behind the
-# psis block and before adapt
+# psis block and before adapt.  And so do the evidence and psis records of the fused launch (with the waic block:
+# with_joint): one more f32 block [n, NJOINTOUT] = evid | psis, 416 B per taxon, directly behind the waic block and
+# before adapt
 REC_AUTO_PRED = _lib.NAUTOPRED * 4
 REC_ADAPT = _lib.NADAPTOUT * 4
 REC_PPC = _lib.NPPCOUT * 4
 REC_QUANT = _lib.NQUANTOUT * 4
+REC_JOINT = _lib.NJOINTOUT * 4
 
 
 def _check_adapt(block, with_adapt: bool, with_auto_pred: bool, with_ppred_adapt: bool,
-                 with_ppc: bool = False, with_quant: bool = False) -> None:
+                 with_ppc: bool = False, with_quant: bool = False, with_joint: bool = False) -> None:
     """The tail switches go with their blocks: with_adapt with a sampled block other than ppred, which has
-    with_ppred_adapt and with_ppc; with_quant with psis; with_auto_pred with auto."""
+    with_ppred_adapt and with_ppc; with_quant with psis; with_joint with waic; with_auto_pred with auto."""
     name = block.name if block is not None else None
     if with_adapt and (name == "ppred" or not (block is not None and block.sampled)):
         raise ValueError("with_adapt goes with with_psis, with_waic or with_auto")
@@ -66,33 +69,36 @@ def _check_adapt(block, with_adapt: bool, with_auto_pred: bool, with_ppred_adapt
         raise ValueError("with_ppc goes with with_ppred")
     if with_quant and name != "psis":
         raise ValueError("with_quant goes with with_psis")
+    if with_joint and name != "waic":
+        raise ValueError("with_joint goes with with_waic")
     if with_auto_pred and name != "auto":
         raise ValueError("with_auto_pred goes with with_auto")
 
 
 def _layout(switches: dict):
-    """(block, (with_ppc, with_quant, with_auto_pred, with_adapt), bytes per taxon) of a gather record from the keywords of
-    Records and unpack_gathered: one with_* of blocks.BLOCKS (blocks.select) and the tail switches (_check_adapt)."""
+    """(block, (with_ppc, with_quant, with_joint, with_auto_pred, with_adapt), bytes per taxon) of a gather record from
+    the keywords of Records and unpack_gathered: one with_* of blocks.BLOCKS (blocks.select) and the tail switches (_check_adapt)."""
     switches = dict(switches)
-    with_adapt, with_auto_pred, with_ppred_adapt, with_ppc, with_quant = (
+    with_adapt, with_auto_pred, with_ppred_adapt, with_ppc, with_quant, with_joint = (
         bool(switches.pop(k, False))
-        for k in ("with_adapt", "with_auto_pred", "with_ppred_adapt", "with_ppc", "with_quant"))
+        for k in ("with_adapt", "with_auto_pred", "with_ppred_adapt", "with_ppc", "with_quant", "with_joint"))
     block = blocks.select(**switches)
-    _check_adapt(block, with_adapt, with_auto_pred, with_ppred_adapt, with_ppc, with_quant)
+    _check_adapt(block, with_adapt, with_auto_pred, with_ppred_adapt, with_ppc, with_quant, with_joint)
     with_adapt = with_adapt or with_ppred_adapt
     rec_bytes = (REC_BYTES + (block.out_bytes if block is not None else 0) + (REC_PPC if with_ppc else 0)
-                 + (REC_QUANT if with_quant else 0) + (REC_AUTO_PRED if with_auto_pred else 0) + (REC_ADAPT if with_adapt else 0))
-    return block, (with_ppc, with_quant, with_auto_pred, with_adapt), rec_bytes
+                 + (REC_QUANT if with_quant else 0) + (REC_JOINT if with_joint else 0) + (REC_AUTO_PRED if with_auto_pred else 0) + (REC_ADAPT if with_adapt else 0))
+    return block, (with_ppc, with_quant, with_joint, with_auto_pred, with_adapt), rec_bytes
 
 
-def _extra_views(buf, n: int, block, tails=(False, False, False, False)):
-    """[block, ppc, quant, auto_pred, adapt]: the f32 views [n, *shape] behind the n base records of the uint8 buffer,
-    in the record's order; None where the record has none.  tails: (with_ppc, with_quant, with_auto_pred,
-    with_adapt)."""
-    with_ppc, with_quant, with_auto_pred, with_adapt = tails
+def _extra_views(buf, n: int, block, tails=(False, False, False, False, False)):
+    """[block, ppc, quant, joint, auto_pred, adapt]: the f32 views [n, *shape] behind the n base records of the uint8
+    buffer, in the record's order; None where the record has none.  tails: (with_ppc, with_quant, with_joint,
+    with_auto_pred, with_adapt)."""
+    with_ppc, with_quant, with_joint, with_auto_pred, with_adapt = tails
     views, lo = [], n * REC_BYTES
     for shape in (block.shape if block is not None else None, (_lib.NPPCOUT,) if with_ppc else None,
-                  (_lib.NQUANTOUT,) if with_quant else None, (_lib.NAUTOPRED,) if with_auto_pred else None, (_lib.NADAPTOUT,) if with_adapt else None):
+                  (_lib.NQUANTOUT,) if with_quant else None, (_lib.NJOINTOUT,) if with_joint else None,
+                  (_lib.NAUTOPRED,) if with_auto_pred else None, (_lib.NADAPTOUT,) if with_adapt else None):
         if shape is None:
             views.append(None)
             continue
@@ -128,7 +134,7 @@ class Records:
     the buffer is longer by the run's extra block, f32[n, *shape] after the
     status under the block's attr (written in place by the chunked dispatch;
     every other block's attr is None), and by the tail blocks `ppc`,
-    `quant`, `auto_pred` and `adapt` behind it."""
+    `quant`, `joint`, `auto_pred` and `adapt` behind it."""
 
     def __init__(self, n: int, device, **switches):
         import torch
@@ -140,7 +146,7 @@ class Records:
         self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
         for b in blocks.BLOCKS:
             setattr(self, b.attr, None)
-        extra, self.ppc, self.quant, self.auto_pred, self.adapt = _extra_views(self.buf, n, block, tails)
+        extra, self.ppc, self.quant, self.joint, self.auto_pred, self.adapt = _extra_views(self.buf, n, block, tails)
         if block is not None:
             setattr(self, block.attr, extra)
         self._fidx = torch.as_tensor(FLOAT_COLS, device=device)
@@ -294,13 +300,14 @@ def run_distributed(fn, *args, **kwargs):
 def unpack_gathered(parts, n_taxa: int, world: int, **switches):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  Returns (out, pred,
-    status[, block][, ppc][, quant][, auto_pred][, adapt]): switches (Records')
-    say which of the extra block, f32 [T, *shape], and the tail blocks, f32 [T,
-    NPPCOUT], f32 [T, NQUANTOUT] and f32 [T, 2] each, the parts carry."""
+    status[, block][, ppc][, quant][, joint][, auto_pred][, adapt]): switches
+    (Records') say which of the extra block, f32 [T, *shape], and the tail
+    blocks, f32 [T, NPPCOUT], f32 [T, NQUANTOUT], f32 [T, NJOINTOUT] and f32 [T,
+    2] each, the parts carry."""
     import torch
 
     block, tails, rec_bytes = _layout(switches)
-    outs, preds, sts, extras = [], [], [], ([], [], [], [], [])
+    outs, preds, sts, extras = [], [], [], ([], [], [], [], [], [])
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)

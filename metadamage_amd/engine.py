@@ -42,7 +42,8 @@ class FitBatch:
     # adapt float32 [T, NADAPTOUT], largest round-0 khat, largest best round (psis_adapt > 0);
     # auto_pred float32 [T, NAUTOPRED], pred_ess_min, pred_distinct_min (auto with auto_pred);
     # ppc float32 [T, NPPCOUT] = ppos | rec, the posterior predictive check (ppred with ppc; split_ppc);
-    # quant float32 [T, NQUANTOUT], the three rows of the weighted order statistics (psis with quantiles)
+    # quant float32 [T, NQUANTOUT], the three rows of the weighted order statistics (psis with quantiles);
+    # joint float32 [T, NJOINTOUT] = evid | psis, the fused launch's other two records (waic with joint; split_joint)
     lap: "object" = None
     diag: "object" = None
     summ: "object" = None
@@ -56,6 +57,7 @@ class FitBatch:
     evid: "object" = None
     ppc: "object" = None
     quant: "object" = None
+    joint: "object" = None
 
 
 def to_device_counts(y, N, mm=None, device="cuda"):
@@ -392,6 +394,62 @@ def map_evidence_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int =
                                       ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
                                       _stream_handle(torch, stream)))
     return evid if draws is None else (evid, draws)
+
+
+def map_joint_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, waic=None,
+                     evid=None, psis=None, pointwise=None, draws=None, stream=None, adapt_rounds: int = 0,
+                     adapt=None):
+    """Launch mdfit_map_joint on the records of a finished MAP call (asynchronous
+    on `stream`): one launch that forms each sub-fit's weights once and writes
+    float64 waic[T, 7, NMAPWAIC], evid[T, 7, NMAPEVID] and psis[T, 3, NMAPPSIS],
+    the records of map_waic_device, map_evidence_device and map_psis_device at
+    the same (num_draws, seed, index_base, adapt_rounds) bit for bit.  pointwise
+    and draws: as map_waic_device's.  Returns (waic, evid, psis[, pointwise][,
+    draws]).
+
+    adapt_rounds > 0, or adapt given (True, or a float64 tensor [T, 3,
+    NMAPADAPT]): mdfit_map_joint_adapt; the adapt block is then the last element
+    of the returned tuple."""
+    torch = _torch()
+    lib = _lib.load()
+    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
+    use_adapt = R != 0 or adapt is not None
+    if use_adapt and (adapt is None or adapt is True):
+        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
+    if waic is None:
+        waic = torch.empty((T, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=ty.device)
+    if evid is None:
+        evid = torch.empty((T, _lib.NEVIDROW, _lib.NMAPEVID), dtype=torch.float64, device=ty.device)
+    if psis is None:
+        psis = torch.empty((T, 3, _lib.NMAPPSIS), dtype=torch.float64, device=ty.device)
+    if pointwise is True:
+        pointwise = torch.empty((T, _lib.NSUBFIT, _lib.NPOS, 2), dtype=torch.float64, device=ty.device)
+    if draws is True:
+        draws = torch.empty((T, _lib.NSUBFIT, S, 6), dtype=torch.float64, device=ty.device)
+    for name, t, n in (("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC),
+                       ("evid", evid, T * _lib.NEVIDROW * _lib.NMAPEVID), ("psis", psis, T * 3 * _lib.NMAPPSIS),
+                       ("pointwise", pointwise, T * _lib.NSUBFIT * _lib.NPOS * 2),
+                       ("draws", draws, T * _lib.NSUBFIT * S * 6), ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
+        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    head = [ptr(ty), ptr(tN), ptr(res.out), ptr(res.status), T, S]
+    got = (waic, evid, psis) + tuple(x for x in (pointwise, draws) if x is not None)
+    if use_adapt:
+        _lib.check(lib.mdfit_map_joint_adapt(*head, R, int(seed), int(index_base), ptr(waic), ptr(evid), ptr(psis),
+                                             ptr(adapt), ptr(pointwise), ptr(draws), _stream_handle(torch, stream)))
+        return got + (adapt,)
+    _lib.check(lib.mdfit_map_joint(*head, int(seed), int(index_base), ptr(waic), ptr(evid), ptr(psis), ptr(pointwise),
+                                   ptr(draws), _stream_handle(torch, stream)))
+    return got
 
 
 def fit_batch_indexed_device(ty, tN, tm, taxon_index, opts: _lib.MdfitOpts, res: FitBatch | None = None,
@@ -1113,6 +1171,25 @@ def _check_quant(quantiles: bool, block, dmax_threshold: float = 0.01) -> bool:
     return bool(quantiles)
 
 
+JOINT_BYTES = _lib.NJOINTOUT * 4  # one taxon's evidence and psis records as they leave the device (f32 evid | psis)
+_JOINT_DEVICE_BYTES = _lib.NJOINTOUT * 8  # ... and as the fused launch computes them (f64)
+_JOINT_EVID = _lib.NEVIDROW * _lib.NMAPEVID  # the words of the evidence record in the block
+
+
+def split_joint(block):
+    """(evid[T, 7, NMAPEVID], psis[T, 3, NMAPPSIS]) views of a joint block [T, NJOINTOUT]."""
+    return (block[:, :_JOINT_EVID].reshape(-1, _lib.NEVIDROW, _lib.NMAPEVID),
+            block[:, _JOINT_EVID:].reshape(-1, 3, _lib.NMAPPSIS))
+
+
+def _check_joint(joint: bool, block) -> bool:
+    """joint (the evidence and psis records of the fused launch, a tail of the waic block) goes with with_waic."""
+    if joint and (block is None or block.name != "waic"):
+        raise ValueError("joint needs with_waic: mdfit_map_joint writes the evidence and the posterior beside the waic "
+                         "record")
+    return bool(joint)
+
+
 def _chunked_block(opts, switches):
     """blocks.resolve for the chunked dispatch: the run's one block, or None."""
     block = blocks.resolve(opts, **switches)
@@ -1134,7 +1211,7 @@ def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
 
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
                  dest_on_device: bool = False, ppc: bool = False, quantiles: bool = False,
-                 dmax_threshold: float = 0.01, **switches) -> int:
+                 dmax_threshold: float = 0.01, joint: bool = False, **switches) -> int:
     """Device bytes one buffer set of a C-taxon chunk takes: the inputs (y, N:
     256 B; mm: 1,440 B), the outputs (record 640 B, predictions 360 B, status 4
     B -- unless the chunk writes into the caller's device buffers) and the
@@ -1144,11 +1221,13 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     launch computes it and -- unless it goes to the caller's device buffer --
     as it leaves, rounded to f32.  ppc (with with_ppred): the check's block in
     the same two forms; quantiles (with with_psis): the weighted order
-    statistics' block in the same two forms."""
+    statistics' block in the same two forms; joint (with with_waic): the
+    evidence and psis records of the fused launch in the same two forms."""
     C = int(C)
     block = _chunked_block(opts, switches)
     ppc = _check_ppc(ppc, block)
     quantiles = _check_quant(quantiles, block, dmax_threshold)
+    joint = _check_joint(joint, block)
     b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
     if not dest_on_device:
         b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
@@ -1158,16 +1237,18 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
         b += C * (_PPC_DEVICE_BYTES + (0 if dest_on_device else PPC_BYTES))
     if quantiles:
         b += C * (_QUANT_DEVICE_BYTES + (0 if dest_on_device else QUANT_BYTES))
+    if joint:
+        b += C * (_JOINT_DEVICE_BYTES + (0 if dest_on_device else JOINT_BYTES))
     return b + workspace_bytes(C, opts)
 
 
 def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | None = None, *,
                 chunk_taxa: int = 0, n_sets: int = N_SETS, with_mm: bool = True, with_pred: bool = True,
                 dest_on_device: bool = False, ppc: bool = False, quantiles: bool = False,
-                dmax_threshold: float = 0.01, **switches) -> list[tuple[int, int]]:
+                dmax_threshold: float = 0.01, joint: bool = False, **switches) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
     buffer sets of the largest chunk (device_bytes, with the run's block of
-    switches, ppc and quantiles) fit in budget_bytes (None: no memory bound), no chunk exceeds the
+    switches, ppc, quantiles and joint) fit in budget_bytes (None: no memory bound), no chunk exceeds the
     per-call limit (2^25 taxa) or chunk_taxa (> 0; env MDFIT_CHUNK_TAXA when 0).
     Taxa are independent and the sampler's streams are keyed by the global taxon
     index (opts.index_base + lo), so any split gives the records of one call bit
@@ -1176,6 +1257,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
     block = _chunked_block(opts, switches)
     _check_ppc(ppc, block)
     _check_quant(quantiles, block, dmax_threshold)
+    _check_joint(joint, block)
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -1185,7 +1267,8 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
         def per(c):
-            return n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, ppc, quantiles, **switches)
+            return n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, ppc, quantiles, joint=joint,
+                                         **switches)
 
 
         if per(1) > budget_bytes:
@@ -1220,7 +1303,7 @@ class _Set:
 
     def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
                  block: blocks.Block | None = None, with_adapt: bool = False, ppc: bool = False,
-                 quantiles: bool = False):
+                 quantiles: bool = False, joint: bool = False):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -1252,6 +1335,12 @@ class _Set:
             self.quant_computed = torch.empty((C, 3, _lib.NMAPQUANT), dtype=torch.float64, device=device)
             if not dest_on_device:
                 self.quant = torch.empty((C, _lib.NQUANTOUT), dtype=torch.float32, device=device)
+        self.joint_computed = self.joint = None
+        if joint:  # as mdfit_map_joint writes them (f64 evid, psis), and as one f32 block for the way out
+            self.joint_computed = (torch.empty((C, _lib.NEVIDROW, _lib.NMAPEVID), dtype=torch.float64, device=device),
+                                   torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float64, device=device))
+            if not dest_on_device:
+                self.joint = torch.empty((C, _lib.NJOINTOUT), dtype=torch.float32, device=device)
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
@@ -1285,6 +1374,11 @@ def _launch_psis(f, st, n, res, o, comp, ad_kw):
 
 
 def _launch_waic(f, st, n, res, o, comp, ad_kw):
+    if f.joint:  # the fused launch: the same waic record, and the evidence and psis records beside it
+        map_joint_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
+                         waic=st.computed[0][:n], evid=st.joint_computed[0][:n], psis=st.joint_computed[1][:n],
+                         stream=comp, **ad_kw)
+        return
     map_waic_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
                     waic=st.computed[0][:n], stream=comp, **ad_kw)
 
@@ -1351,16 +1445,24 @@ class ChunkedFitter:
     compute stream with the same draws, seed and index_base and the exceedance
     threshold dmax_threshold, and one more f32 block [T, NQUANTOUT] = the three
     rows of _lib.MAPQUANT_FIELDS, rounded on the device, leaves behind the block
-    and before adapt (run; dest.quant)."""
+    and before adapt (run; dest.quant).
+
+    joint (with with_waic): the chunk's map_waic launch is replaced by the one
+    launch of mdfit_map_joint (mdfit_map_joint_adapt when psis_adapt > 0), which
+    writes the same waic record and, from the same weights, the records of
+    mdfit_map_evidence and mdfit_map_psis; those leave as one more f32 block [T,
+    NJOINTOUT] = evid | psis (split_joint), rounded on the device, behind the
+    waic block and before adapt (run; dest.joint)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, psis_draws: int = PSIS_DRAWS,
                  pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False,
-                 dmax_threshold: float = 0.01, **switches):
+                 dmax_threshold: float = 0.01, joint: bool = False, **switches):
         self.block = _chunked_block(opts, switches)
         self.ppc = _check_ppc(ppc, self.block)
         self.quantiles = _check_quant(quantiles, self.block, dmax_threshold)
         self.dmax_threshold = float(dmax_threshold)
+        self.joint = _check_joint(joint, self.block)
         torch = _torch()
         self.psis_adapt = _check_psis_adapt(psis_adapt, self.block is not None and self.block.sampled)
         self.pred_draws = int(pred_draws)
@@ -1369,14 +1471,14 @@ class ChunkedFitter:
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
         self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.block,
-                          self.psis_adapt > 0, self.ppc, self.quantiles)
+                          self.psis_adapt > 0, self.ppc, self.quantiles, self.joint)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = None
-        self.h_block = self.h_adapt = self.h_ppc = self.h_quant = None
+        self.h_block = self.h_adapt = self.h_ppc = self.h_quant = self.h_joint = None
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -1400,6 +1502,8 @@ class ChunkedFitter:
                 self.h_ppc = torch.empty((cap, _lib.NPPCOUT), dtype=torch.float32).pin_memory()
             if self.quantiles:
                 self.h_quant = torch.empty((cap, _lib.NQUANTOUT), dtype=torch.float32).pin_memory()
+            if self.joint:
+                self.h_joint = torch.empty((cap, _lib.NJOINTOUT), dtype=torch.float32).pin_memory()
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -1437,6 +1541,8 @@ class ChunkedFitter:
             raise ValueError("ppc: dest.ppc (float32 [T, NPPCOUT]) required")
         if self.quantiles and dest is not None and getattr(dest, "quant", None) is None:
             raise ValueError("quantiles: dest.quant (float32 [T, NQUANTOUT]) required")
+        if self.joint and dest is not None and getattr(dest, "joint", None) is None:
+            raise ValueError("joint: dest.joint (float32 [T, NJOINTOUT]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -1479,7 +1585,7 @@ class ChunkedFitter:
                 _lib.check(lib.mdfit_noise(ctypes.c_void_p(st.d_y.data_ptr()), ctypes.c_void_p(st.d_N.data_ptr()),
                                            ctypes.c_void_p(st.d_mm.data_ptr()), n, ctypes.c_void_p(res.out.data_ptr()),
                                            h_s))
-            block32 = adapt32 = ppc32 = quant32 = None
+            block32 = adapt32 = ppc32 = quant32 = joint32 = None
             if block is not None:  # the records are final: the block's launch, then one f32 block for the way out
                 ad_kw = {"adapt_rounds": self.psis_adapt, "adapt": st.adapt64[:n]} if self.psis_adapt > 0 else {}
                 _LAUNCH[block.name](self, st, n, res, o, comp, ad_kw)
@@ -1509,6 +1615,11 @@ class ChunkedFitter:
                 quant32 = dest.quant[lo:hi] if dest is not None else st.quant[:n]
                 with torch.cuda.stream(comp):
                     quant32.copy_(st.quant_computed[:n].reshape(n, _lib.NQUANTOUT))
+            if self.joint:  # the fused launch (_launch_waic) has written them: one f32 block for the way out
+                joint32 = dest.joint[lo:hi] if dest is not None else st.joint[:n]
+                with torch.cuda.stream(comp):
+                    for view, computed in zip(split_joint(joint32), st.joint_computed):
+                        view.copy_(computed[:n])
             if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
                 adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
                 with torch.cuda.stream(comp):
@@ -1529,6 +1640,8 @@ class ChunkedFitter:
                         self.h_ppc[lo:hi].copy_(ppc32, non_blocking=True)
                     if quant32 is not None:
                         self.h_quant[lo:hi].copy_(quant32, non_blocking=True)
+                    if joint32 is not None:
+                        self.h_joint[lo:hi].copy_(joint32, non_blocking=True)
                     if adapt32 is not None:
                         self.h_adapt[lo:hi].copy_(adapt32, non_blocking=True)
                 last_d2h = cp
@@ -1540,7 +1653,7 @@ class ChunkedFitter:
     def run(self, y, N, mm=None, opts: _lib.MdfitOpts | None = None, sync: bool = True,
             pinned: PinnedPack | None = None, chunks=None):
         """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status[, the
-        run's block f32 [T, *shape]][, ppc f32 [T, NPPCOUT]][, quant f32 [T, NQUANTOUT]][, adapt f32 [T, 2]]) of the
+        run's block f32 [T, *shape]][, ppc f32 [T, NPPCOUT]][, quant f32 [T, NQUANTOUT]][, joint f32 [T, NJOINTOUT]][, adapt f32 [T, 2]]) of the
         pinned buffers
         (valid until the next run).  pinned: y, N, mm are that PinnedPack's
         views.  chunks: the split (default plan_chunks at this staging's
@@ -1562,6 +1675,8 @@ class ChunkedFitter:
             got += (self.h_ppc[:T].numpy(),)
         if self.quantiles:
             got += (self.h_quant[:T].numpy(),)
+        if self.joint:
+            got += (self.h_joint[:T].numpy(),)
         if self.psis_adapt > 0:
             got += (self.h_adapt[:T].numpy(),)
         return got
@@ -1569,7 +1684,7 @@ class ChunkedFitter:
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
         (out[T, NOUT], pred, status -- and the run's block under its attribute,
-        ppc with ppc, quant with quantiles, adapt when psis_adapt > 0: rows written in place), ordered on the
+        ppc with ppc, quant with quantiles, joint with joint, adapt when psis_adapt > 0: rows written in place), ordered on the
         caller's current stream."""
         T = int(y.shape[0])
         if chunks is None:
@@ -1638,11 +1753,11 @@ _STAGING_LOCK = __import__("threading").Lock()
 def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_mm: bool = True,
             dest_on_device: bool = False, budget_bytes: int | None = None, psis_draws: int = PSIS_DRAWS,
             pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False,
-            dmax_threshold: float = 0.01, **switches) -> ChunkedFitter:
+            dmax_threshold: float = 0.01, joint: bool = False, **switches) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
     of this process (per device, buffer kind, sampler length and the run's block
-    of switches with the draw counts it uses, psis_adapt, ppc and quantiles
-    with its threshold): the
+    of switches with the draw counts it uses, psis_adapt, ppc, quantiles
+    with its threshold and joint): the
     multi-file pipeline fits one file after another, and pinned + device
     buffers allocated per file cost more host time than the fit.  Its chunk
     capacity is the largest chunk N_SETS buffer sets of which fit the device
@@ -1662,7 +1777,8 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
            int(psis_draws) if block is not None and block.sampled else 0,
            int(pred_draws) if block is not None and block.name == "ppred" else 0, int(psis_adapt),
            _check_ppc(ppc, block),
-           float(dmax_threshold) if _check_quant(quantiles, block, dmax_threshold) else None)
+           float(dmax_threshold) if _check_quant(quantiles, block, dmax_threshold) else None,
+           _check_joint(joint, block))
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1679,11 +1795,11 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     if T < _lib.STREAM_MAX_TAXA:
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
     cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
-                      ppc=ppc, quantiles=quantiles, dmax_threshold=dmax_threshold, **switches)[0]
+                      ppc=ppc, quantiles=quantiles, dmax_threshold=dmax_threshold, joint=joint, **switches)[0]
     cap = cap[1] - cap[0]
     st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
                        psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
-                       quantiles=quantiles, dmax_threshold=dmax_threshold, **switches)
+                       quantiles=quantiles, dmax_threshold=dmax_threshold, joint=joint, **switches)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1693,7 +1809,7 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
 def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None, device="cuda",
                    pinned: PinnedPack | None = None, psis_draws: int = PSIS_DRAWS, pred_draws: int = PRED_DRAWS,
                    psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False, dmax_threshold: float = 0.01,
-                   **named):
+                   joint: bool = False, **named):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     named (one chunked block of blocks.BLOCKS by its name, e.g. laplace=True), a
     fourth array, the block's f32 [T, *shape] --, chunked through the device
@@ -1702,7 +1818,8 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     _lib.ADAPTOUT_FIELDS; ppc, with ppred=True, the check's f32 [T, NPPCOUT]
     behind the block and before adapt; quantiles, with psis=True, the weighted
     order statistics' f32 [T, NQUANTOUT] in the same place, P(D_max >
-    dmax_threshold) among them).  mm goes to the device (the assembly computes the
+    dmax_threshold) among them; joint, with waic=True, the fused launch's f32
+    [T, NJOINTOUT] = evid | psis in the same place).  mm goes to the device (the assembly computes the
     noise columns); without it, `noise` (float64[T][3], ingest.noise) fills them
     when given.  pinned: y, N, mm are views of that PinnedPack (copied to the
     device from there)."""
@@ -1710,7 +1827,8 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
     with _STAGING_LOCK:
         st = staging(T, device=device, opts=opts, with_mm=mm is not None, psis_draws=psis_draws,
                      pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, quantiles=quantiles,
-                     dmax_threshold=dmax_threshold, **{"with_" + k: v for k, v in named.items()})
+                     dmax_threshold=dmax_threshold, joint=joint,
+                     **{"with_" + k: v for k, v in named.items()})
         got = st.run(y, N, mm, opts, pinned=pinned, chunks=plan_chunks(T, opts, chunk_taxa=st.chunk_cap))
         got = tuple(a.copy() for a in got)
     out, status = got[0], got[2]

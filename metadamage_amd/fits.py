@@ -362,7 +362,7 @@ def _pack_buffers(T: int, pinned: bool, zero: bool):
 # --------------------------------------------------------------------------
 def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, pred_draws: int = 1000,
                psis_adapt: int = 0, auto_pred: bool = False, ppc: bool = False, quantiles: bool = False,
-               dmax_threshold: float = 0.01, **named):
+               dmax_threshold: float = 0.01, joint: bool = False, **named):
     """Run mdfit_fit_batch on the packed taxa; returns host (out, pred, status)
     on rank 0 (None elsewhere in a multi-GPU job).  shard=False fits every
     taxon on this rank's GPU (main() shards whole files across ranks).
@@ -386,7 +386,9 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, 
     ppred block.  quantiles (with psis; MDFIT-QUANT v1): mdfit_map_quant follows
     each chunk's map_psis launch and quant[T, 48] f32, the three rows of
     _lib.MAPQUANT_FIELDS with P(D_max > dmax_threshold), is returned directly
-    behind the psis block."""
+    behind the psis block.  joint (with waic): each chunk's map_waic launch is
+    the fused mdfit_map_joint and joint[T, 104] f32 = evid | psis
+    (engine.split_joint) is returned directly behind the waic block."""
     import torch
 
     from . import engine
@@ -415,23 +417,24 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, 
         raise ValueError("auto_pred goes with the auto inference")
     ppc = engine._check_ppc(ppc, block)
     quantiles = engine._check_quant(quantiles, block, dmax_threshold)
+    joint = engine._check_joint(joint, block)
     try:
         if grouped:
             return _fit_sharded(p, opts, dev, rank, world, block, psis_draws, pred_draws, psis_adapt, auto_pred, ppc,
-                                quantiles, dmax_threshold)
+                                quantiles, dmax_threshold, joint)
         if auto:
             return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt,
                                           auto_pred=auto_pred, pred_draws=pred_draws)
         return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, psis_draws=psis_draws,
                                      pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, quantiles=quantiles,
-                                     dmax_threshold=dmax_threshold, **named)
+                                     dmax_threshold=dmax_threshold, joint=joint, **named)
     finally:
         p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
 
 
 def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Block | None = None,
                  psis_draws: int = 256, pred_draws: int = 1000, psis_adapt: int = 0, auto_pred: bool = False,
-                 ppc: bool = False, quantiles: bool = False, dmax_threshold: float = 0.01):
+                 ppc: bool = False, quantiles: bool = False, dmax_threshold: float = 0.01, joint: bool = False):
     import torch
 
     from . import engine
@@ -445,7 +448,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
     switch = {block.switch: True} if block is not None else {}
     ppred = block is not None and block.name == "ppred"  # (its adapt tail has a switch of its own)
     layout = dict(switch, with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                  with_auto_pred=auto_pred, with_ppc=ppc, with_quant=quantiles)
+                  with_auto_pred=auto_pred, with_ppc=ppc, with_quant=quantiles, with_joint=joint)
     rec = alloc_records(cap, dev, **layout)
     # the rows are written in place into the gather buffers
     dest = engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
@@ -453,6 +456,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
                            auto_pred=rec.auto_pred[: hi - lo] if auto_pred else None,
                            ppc=rec.ppc[: hi - lo] if ppc else None,
                            quant=rec.quant[: hi - lo] if quantiles else None,
+                           joint=rec.joint[: hi - lo] if joint else None,
                            **({block.attr: getattr(rec, block.attr)[: hi - lo]} if block is not None else {}))
     if hi > lo and block is not None and not block.chunked:  # each rank runs auto on its shard
         engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
@@ -463,7 +467,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
         with engine._STAGING_LOCK:
             st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
                                 psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
-                                quantiles=quantiles, dmax_threshold=dmax_threshold, **switch)
+                                quantiles=quantiles, dmax_threshold=dmax_threshold, joint=joint, **switch)
             st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, dest)
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
@@ -528,9 +532,33 @@ def _record_columns(out, keep, ncol: int, block: int = 2048) -> np.ndarray:
     return cols
 
 
+def _psis_columns(kp, data) -> list:
+    """The MAP_PSIS_COLUMNS and MAP_PSIS_UINT_COLUMNS of the kept psis records kp[n, 3, 16] into data; their names."""
+    for name, row, field in _MAP_PSIS_PICKS:
+        data[name] = np.ascontiguousarray(kp[:, row, _lib.MAPPSIS_FIELDS.index(field)], dtype=np.float32)
+    flags = np.nan_to_num(kp[:, :, _lib.MAPPSIS_FIELDS.index("flags")]).astype(np.int64)
+    valid = ((flags & _lib.MAPPSIS_VALID) != 0).all(axis=1)
+    data["map_psis_valid"] = valid.astype(np.uint32)
+    data["map_psis_reliable"] = (valid & ((flags & _lib.MAPPSIS_RELIABLE) != 0).all(axis=1)).astype(np.uint32)
+    return MAP_PSIS_COLUMNS + MAP_PSIS_UINT_COLUMNS
+
+
+def _evidence_columns(ke, data) -> list:
+    """The MAP_EVIDENCE_COLUMNS and MAP_EVIDENCE_UINT_COLUMNS of the kept evidence records ke[n, 7, 8] into data;
+    their names."""
+    for name, row, field in _MAP_EVIDENCE_PICKS:
+        data[name] = np.ascontiguousarray(ke[:, row, field], dtype=np.float32)
+    with np.errstate(over="ignore"):  # (exp(-log_bf) = inf: probability 0)
+        data["damage_probability"] = (1.0 / (1.0 + np.exp(-ke[:, 6, 0].astype(np.float64)))).astype(np.float32)
+    flags = np.nan_to_num(ke[:, 6, _lib.MAPEVID_COMPARE_FIELDS.index("flags")]).astype(np.int64)
+    data["map_evidence_valid"] = ((flags & _lib.MAPEVID_VALID) != 0).astype(np.uint32)
+    data["map_evidence_reliable"] = ((flags & _lib.MAPEVID_RELIABLE) != 0).astype(np.uint32)
+    return MAP_EVIDENCE_COLUMNS + MAP_EVIDENCE_UINT_COLUMNS
+
+
 def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=None, loo=None,
                         psis=None, waic=None, auto=None, ppred=None, adapt=None, auto_pred=None,
-                        evid=None, ppc=None, quant=None) -> pd.DataFrame:
+                        evid=None, ppc=None, quant=None, joint=None) -> pd.DataFrame:
     """One row per fitted taxon in FIT_RESULT_COLUMNS order with the dtypes of
     downcast_dataframe (fits.py:668-680 + utils.py:329-356): names
     categorical, integer fields uint32, the rest float32.  lap (the Laplace
@@ -557,7 +585,10 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
     block [T, 42] of a "map-pred" run with ppc): the PPC_COLUMNS follow
     map-pred's, in their own dtypes.  quant (the weighted order statistics'
     block [T, 48] of a "map-psis" run with quantiles): the MAP_QUANT_COLUMNS
-    follow map-psis's as float32, then the MAP_QUANT_UINT_COLUMNS.  adapt (the adapt block [T, 2] of a run with
+    follow map-psis's as float32, then the MAP_QUANT_UINT_COLUMNS.  joint (the
+    block [T, 104] = evid | psis of a "map-waic" run with joint): behind
+    map-waic's columns map-evidence's, then map-psis's, each formed as from
+    evid= and psis=.  adapt (the adapt block [T, 2] of a run with
     psis_adapt > 0): pareto_k_initial (float32) and psis_adapt_rounds (uint32)
     are the last two columns."""
     n = int(keep.sum())
@@ -610,14 +641,7 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["nuts_loo_valid"] = ((flags & _lib.NUTSLOO_VALID) != 0).astype(np.uint32)
         columns += NUTS_LOO_COLUMNS + NUTS_LOO_UINT_COLUMNS
     if psis is not None:
-        kp = np.asarray(psis) if keep is None else np.asarray(psis)[keep]
-        for name, row, field in _MAP_PSIS_PICKS:
-            data[name] = np.ascontiguousarray(kp[:, row, _lib.MAPPSIS_FIELDS.index(field)], dtype=np.float32)
-        flags = np.nan_to_num(kp[:, :, _lib.MAPPSIS_FIELDS.index("flags")]).astype(np.int64)
-        valid = ((flags & _lib.MAPPSIS_VALID) != 0).all(axis=1)
-        data["map_psis_valid"] = valid.astype(np.uint32)
-        data["map_psis_reliable"] = (valid & ((flags & _lib.MAPPSIS_RELIABLE) != 0).all(axis=1)).astype(np.uint32)
-        columns += MAP_PSIS_COLUMNS + MAP_PSIS_UINT_COLUMNS
+        columns += _psis_columns(np.asarray(psis) if keep is None else np.asarray(psis)[keep], data)
     if quant is not None:
         kq = np.asarray(quant).reshape(-1, 3, _lib.NMAPQUANT)
         kq = kq if keep is None else kq[keep]
@@ -636,16 +660,16 @@ def make_df_fit_results(p: Packed, out, keep, cfg, lap=None, diag=None, summ=Non
         data["map_waic_valid"] = ((flags & _lib.MAPWAIC_VALID) != 0).astype(np.uint32)
         data["map_waic_reliable"] = ((flags & _lib.MAPWAIC_RELIABLE) != 0).astype(np.uint32)
         columns += MAP_WAIC_COLUMNS + MAP_WAIC_UINT_COLUMNS
+    if joint is not None:
+        if waic is None or psis is not None or evid is not None:
+            raise ValueError("joint goes with waic, and neither psis nor evid beside it")
+        kj = np.asarray(joint).reshape(-1, _lib.NJOINTOUT)
+        kj = kj if keep is None else kj[keep]
+        n_ev = _lib.NEVIDROW * _lib.NMAPEVID
+        columns += _evidence_columns(kj[:, :n_ev].reshape(-1, _lib.NEVIDROW, _lib.NMAPEVID), data)
+        columns += _psis_columns(kj[:, n_ev:].reshape(-1, 3, _lib.NMAPPSIS), data)
     if evid is not None:
-        ke = np.asarray(evid) if keep is None else np.asarray(evid)[keep]
-        for name, row, field in _MAP_EVIDENCE_PICKS:
-            data[name] = np.ascontiguousarray(ke[:, row, field], dtype=np.float32)
-        with np.errstate(over="ignore"):  # (exp(-log_bf) = inf: probability 0)
-            data["damage_probability"] = (1.0 / (1.0 + np.exp(-ke[:, 6, 0].astype(np.float64)))).astype(np.float32)
-        flags = np.nan_to_num(ke[:, 6, _lib.MAPEVID_COMPARE_FIELDS.index("flags")]).astype(np.int64)
-        data["map_evidence_valid"] = ((flags & _lib.MAPEVID_VALID) != 0).astype(np.uint32)
-        data["map_evidence_reliable"] = ((flags & _lib.MAPEVID_RELIABLE) != 0).astype(np.uint32)
-        columns += MAP_EVIDENCE_COLUMNS + MAP_EVIDENCE_UINT_COLUMNS
+        columns += _evidence_columns(np.asarray(evid) if keep is None else np.asarray(evid)[keep], data)
     if auto is not None:
         ka = np.asarray(auto) if keep is None else np.asarray(auto)[keep]
         data["auto_route"] = _uint32(np.nan_to_num(ka[:, 0]).astype(np.int64))
@@ -843,6 +867,16 @@ def quantiles_of(cfg) -> bool:
     return on
 
 
+def joint_of(cfg) -> bool:
+    """cfg.joint (default False): a "map-waic" run forms the evidence and the posterior from the same weights in the
+    same launch (mdfit_map_joint) and adds map-evidence's and map-psis's columns; with any other inference a
+    ValueError naming the option."""
+    on = bool(getattr(cfg, "joint", False))
+    if on and not wants_waic(cfg):
+        raise ValueError("joint goes with inference 'map-waic'")
+    return on
+
+
 def dmax_threshold_of(cfg) -> float:
     """The threshold d0 of D_max_prob_above = P(D_max > d0) of a run with quantiles (cfg.dmax_threshold, default
     0.01)."""
@@ -872,19 +906,22 @@ def _fit_for_frames(p: Packed, cfg, opts, shard: bool):
     block = next((b for b in blocks.BLOCKS if b.inference == inference), None)
     res = fit_packed(p, opts, shard=shard, psis_draws=psis_draws_of(cfg), pred_draws=pred_draws_of(cfg),
                      psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg), ppc=ppc_of(cfg),
-                     quantiles=quantiles_of(cfg), dmax_threshold=dmax_threshold_of(cfg),
+                     quantiles=quantiles_of(cfg), dmax_threshold=dmax_threshold_of(cfg), joint=joint_of(cfg),
                      **({block.name: True} if block is not None else {}))
     if res is None:
         return None
     out, pred, status, *rest = res
     ppc = rest.pop(1) if ppc_of(cfg) else None  # (directly behind the ppred block)
     quant = rest.pop(1) if quantiles_of(cfg) else None  # (directly behind the psis block)
+    joint = rest.pop(1) if joint_of(cfg) else None  # (directly behind the waic block)
     extra, auto_pred, adapt = _split_rest(cfg, rest)
     kw = {"adapt": adapt, "auto_pred": auto_pred}
     if ppc is not None:
         kw["ppc"] = ppc
     if quant is not None:
         kw["quant"] = quant
+    if joint is not None:
+        kw["joint"] = joint
     if block is not None:
         kw[block.attr] = extra
     keep = status == _lib.OK
@@ -954,7 +991,7 @@ def _rank() -> int:
 
 CACHE_KEYS = ["min_alignments", "min_y_sum", "substitution_bases_forward", "substitution_bases_reverse",
               "N_fits", "shortname", "filename", "inference", "psis_draws", "pred_draws", "psis_adapt", "auto_pred",
-              "ppc", "quantiles", "dmax_threshold"]
+              "ppc", "quantiles", "dmax_threshold", "joint"]
 
 
 def _cache_hit(cfg) -> bool:

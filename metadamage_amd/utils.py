@@ -81,6 +81,9 @@ class Config:
     # and P(D_max > dmax_threshold); both in the metadata and the cache key only when quantiles is set
     quantiles: bool = False
     dmax_threshold: float = 0.01
+    # "map-waic": the evidence and the posterior from the same weights in the same launch (mdfit_map_joint), their
+    # columns behind map-waic's; in the metadata and the cache key only when set
+    joint: bool = False
     N_cores: int = field(init=False)
 
     def __post_init__(self):
@@ -90,6 +93,8 @@ class Config:
             raise ValueError("quantiles goes with inference 'map-psis'")
         if self.quantiles and not 0.0 <= float(self.dmax_threshold) <= 1.0:
             raise ValueError("dmax_threshold must be in [0, 1]")
+        if self.joint and self.inference != "map-waic":
+            raise ValueError("joint goes with inference 'map-waic'")
         self._set_N_cores()
 
     def _set_N_cores(self):
@@ -165,6 +170,8 @@ class Config:
         if not self.quantiles:
             del d_out["quantiles"]
             del d_out["dmax_threshold"]
+        if not self.joint:
+            del d_out["joint"]
         for key, val in d_out.items():
             if isinstance(val, Path):
                 d_out[key] = str(val)
