@@ -35,75 +35,31 @@ REC_PRED = _lib.NPRED * _lib.NPOS * 4
 REC_RES = REC_INT + REC_F32
 REC_BYTES = REC_RES + REC_PRED + 4
 REC_OUT = _lib.NOUT * 8  # the full record the kernel writes (rank-local)
-# The run's one extra block (blocks.BLOCKS; its with_* switch): one more f32 block [n, *shape] after the status, in
-# the same buffer and the same single gather.  Bytes per taxon:
-_OUT_BYTES = {b.name: b.out_bytes for b in blocks.BLOCKS}
-REC_LAP, REC_DIAG, REC_SUMM, REC_LOO, REC_PSIS, REC_WAIC, REC_EVID, REC_PPRED, REC_AUTO = (
-    _OUT_BYTES[name] for name in ("laplace", "diag", "summary", "loo", "psis", "waic", "evidence", "ppred", "auto"))
-# The tail blocks behind it.  auto_pred (with the auto block: with_auto_pred): one more f32 block [n, NAUTOPRED] =
-# pred_ess_min, pred_distinct_min, 8 B per taxon.  Then psis_adapt > 0 (with a sampled block: with_adapt; with the
-# ppred block, its own switch: with_ppred_adapt): one more f32 block [n, 2], 8 B per taxon.  The posterior predictive
-# check (with the ppred block: with_ppc) rides directly behind its block, before the other tails: one more f32 block
-# [n, NPPCOUT] = ppos | rec, 168 B per taxon.  So do the weighted order statistics (with the psis block: with_quant):
-# one more f32 block [n, NQUANTOUT] = the three rows of _lib.MAPQUANT_FIELDS, 192 B per taxon, directly behind the
-# psis block and before adapt.  And so do the evidence and psis records of the fused launch (with the waic block:
-# with_joint): one more f32 block [n, NJOINTOUT] = evid | psis, 416 B per taxon, directly behind the waic block and
-# before adapt
-REC_AUTO_PRED = _lib.NAUTOPRED * 4
-REC_ADAPT = _lib.NADAPTOUT * 4
-REC_PPC = _lib.NPPCOUT * 4
-REC_QUANT = _lib.NQUANTOUT * 4
-REC_JOINT = _lib.NJOINTOUT * 4
-
-
-def _check_adapt(block, with_adapt: bool, with_auto_pred: bool, with_ppred_adapt: bool,
-                 with_ppc: bool = False, with_quant: bool = False, with_joint: bool = False) -> None:
-    """The tail switches go with their blocks: with_adapt with a sampled block other than ppred, which has
-    with_ppred_adapt and with_ppc; with_quant with psis; with_joint with waic; with_auto_pred with auto."""
-    name = block.name if block is not None else None
-    if with_adapt and (name == "ppred" or not (block is not None and block.sampled)):
-        raise ValueError("with_adapt goes with with_psis, with_waic or with_auto")
-    if with_ppred_adapt and name != "ppred":
-        raise ValueError("with_ppred_adapt goes with with_ppred")
-    if with_ppc and name != "ppred":
-        raise ValueError("with_ppc goes with with_ppred")
-    if with_quant and name != "psis":
-        raise ValueError("with_quant goes with with_psis")
-    if with_joint and name != "waic":
-        raise ValueError("with_joint goes with with_waic")
-    if with_auto_pred and name != "auto":
-        raise ValueError("with_auto_pred goes with with_auto")
+# Behind the status, in the same buffer and the same single gather: the run's one extra block (blocks.BLOCKS; its
+# with_* switch), one more f32 block [n, *shape], and then the tails that ride it (blocks.TAILS, in its order; each
+# by its switch -- with_ppc, with_quant, with_joint, with_auto_pred, with_adapt and, with the ppred block,
+# with_ppred_adapt), one more f32 block [n, *shape] each.  Bytes per taxon:
+_OUT_BYTES = {p.name: p.out_bytes for p in (*blocks.BLOCKS, *blocks.TAILS)}
+(REC_LAP, REC_DIAG, REC_SUMM, REC_LOO, REC_PSIS, REC_WAIC, REC_EVID, REC_PPRED, REC_AUTO, REC_PPC, REC_QUANT,
+ REC_JOINT, REC_AUTO_PRED, REC_ADAPT) = (
+    _OUT_BYTES[name] for name in ("laplace", "diag", "summary", "loo", "psis", "waic", "evidence", "ppred", "auto",
+                                  "ppc", "quant", "joint", "auto_pred", "adapt"))
 
 
 def _layout(switches: dict):
-    """(block, (with_ppc, with_quant, with_joint, with_auto_pred, with_adapt), bytes per taxon) of a gather record from
-    the keywords of Records and unpack_gathered: one with_* of blocks.BLOCKS (blocks.select) and the tail switches (_check_adapt)."""
-    switches = dict(switches)
-    with_adapt, with_auto_pred, with_ppred_adapt, with_ppc, with_quant, with_joint = (
-        bool(switches.pop(k, False))
-        for k in ("with_adapt", "with_auto_pred", "with_ppred_adapt", "with_ppc", "with_quant", "with_joint"))
-    block = blocks.select(**switches)
-    _check_adapt(block, with_adapt, with_auto_pred, with_ppred_adapt, with_ppc, with_quant, with_joint)
-    with_adapt = with_adapt or with_ppred_adapt
-    rec_bytes = (REC_BYTES + (block.out_bytes if block is not None else 0) + (REC_PPC if with_ppc else 0)
-                 + (REC_QUANT if with_quant else 0) + (REC_JOINT if with_joint else 0) + (REC_AUTO_PRED if with_auto_pred else 0) + (REC_ADAPT if with_adapt else 0))
-    return block, (with_ppc, with_quant, with_joint, with_auto_pred, with_adapt), rec_bytes
+    """(parts, bytes per taxon) of a gather record from the keywords of Records and unpack_gathered: parts is
+    [block, *tails] of the run they describe (blocks.describe, which checks them)."""
+    parts = blocks.describe(by_switch=True, check_mode=False, **switches).parts
+    return parts, REC_BYTES + sum(p.out_bytes for p in parts)
 
 
-def _extra_views(buf, n: int, block, tails=(False, False, False, False, False)):
-    """[block, ppc, quant, joint, auto_pred, adapt]: the f32 views [n, *shape] behind the n base records of the uint8
-    buffer, in the record's order; None where the record has none.  tails: (with_ppc, with_quant, with_joint,
-    with_auto_pred, with_adapt)."""
-    with_ppc, with_quant, with_joint, with_auto_pred, with_adapt = tails
-    views, lo = [], n * REC_BYTES
-    for shape in (block.shape if block is not None else None, (_lib.NPPCOUT,) if with_ppc else None,
-                  (_lib.NQUANTOUT,) if with_quant else None, (_lib.NJOINTOUT,) if with_joint else None,
-                  (_lib.NAUTOPRED,) if with_auto_pred else None, (_lib.NADAPTOUT,) if with_adapt else None):
-        if shape is None:
-            views.append(None)
-            continue
-        hi = lo + 4 * n * int(np.prod(shape))
-        views.append(buf[lo:hi].view(dtype=_torch_dtype("float32")).view(n, *shape))
+def _extra_views(buf, n: int, parts) -> dict:
+    """By attr, in the record's order: the f32 view [n, *shape] of each of parts behind the n base records of the
+    uint8 buffer."""
+    views, lo = {}, n * REC_BYTES
+    for p in parts:
+        hi = lo + n * p.out_bytes
+        views[p.attr] = buf[lo:hi].view(dtype=_torch_dtype("float32")).view(n, *p.shape)
         lo = hi
     return views
 
@@ -133,22 +89,22 @@ class Records:
     copies, the second rounding to f32) before the gather.  switches (_layout):
     the buffer is longer by the run's extra block, f32[n, *shape] after the
     status under the block's attr (written in place by the chunked dispatch;
-    every other block's attr is None), and by the tail blocks `ppc`,
-    `quant`, `joint`, `auto_pred` and `adapt` behind it."""
+    every other block's attr is None), and by the tails behind it, each under
+    its name (blocks.TAILS: `ppc`, `quant`, `joint`, `auto_pred`, `adapt`; None
+    where the record has none)."""
 
     def __init__(self, n: int, device, **switches):
         import torch
 
-        block, tails, rec_bytes = _layout(switches)
+        parts, rec_bytes = _layout(switches)
         self.n = n
         self.out = torch.empty((n, _lib.NOUT), dtype=torch.float64, device=device)
         self.buf = torch.empty(n * rec_bytes, dtype=torch.uint8, device=device)
         self.pred, self.status, self.ints, self.floats = packed_views(self.buf, n)
-        for b in blocks.BLOCKS:
-            setattr(self, b.attr, None)
-        extra, self.ppc, self.quant, self.joint, self.auto_pred, self.adapt = _extra_views(self.buf, n, block, tails)
-        if block is not None:
-            setattr(self, block.attr, extra)
+        for p in (*blocks.BLOCKS, *blocks.TAILS):
+            setattr(self, p.attr, None)
+        for attr, view in _extra_views(self.buf, n, parts).items():
+            setattr(self, attr, view)
         self._fidx = torch.as_tensor(FLOAT_COLS, device=device)
 
     def stage(self):
@@ -174,7 +130,7 @@ def packed_views(buf, n: int, **switches):
     status = buf[o3 : o3 + 4 * n].view(dtype=_torch_dtype("int32"))
     if block is None:
         return pred, status, ints, floats
-    return pred, status, ints, floats, _extra_views(buf, n, block)[0]
+    return pred, status, ints, floats, _extra_views(buf, n, (block,))[block.attr]
 
 
 def round_like_gather(out: np.ndarray) -> np.ndarray:
@@ -301,13 +257,12 @@ def unpack_gathered(parts, n_taxa: int, world: int, **switches):
     """Concatenate gathered shards back into df_counts order (host numpy);
     the parts may be device (RCCL) or host (gloo) buffers.  Returns (out, pred,
     status[, block][, ppc][, quant][, joint][, auto_pred][, adapt]): switches
-    (Records') say which of the extra block, f32 [T, *shape], and the tail
-    blocks, f32 [T, NPPCOUT], f32 [T, NQUANTOUT], f32 [T, NJOINTOUT] and f32 [T,
-    2] each, the parts carry."""
+    (Records') say which of the extra block and the tails (blocks.TAILS), f32
+    [T, *shape] each, the parts carry."""
     import torch
 
-    block, tails, rec_bytes = _layout(switches)
-    outs, preds, sts, extras = [], [], [], ([], [], [], [], [], [])
+    layout, rec_bytes = _layout(switches)
+    outs, preds, sts, extras = [], [], [], {p.attr: [] for p in layout}
     if parts and parts[0].is_cuda:
         # every part's D2H copy queued at once into one pinned host buffer,
         # then one synchronisation (not a blocking copy per part)
@@ -325,16 +280,15 @@ def unpack_gathered(parts, n_taxa: int, world: int, **switches):
         lo, hi = shard_range(n_taxa, r, world)
         n_cap = part.numel() // rec_bytes
         p, s, ints, floats = packed_views(part, n_cap)
-        for got, view in zip(extras, _extra_views(part, n_cap, block, tails)):
-            if view is not None:
-                got.append(view[: hi - lo].numpy())
+        for attr, view in _extra_views(part, n_cap, layout).items():
+            extras[attr].append(view[: hi - lo].numpy())
         o = np.empty((hi - lo, NRES_GATHER), np.float64)
         o[:, INT_LO:INT_HI] = ints[: hi - lo].numpy()
         o[:, FLOAT_COLS] = floats[: hi - lo].numpy()
         outs.append(o)
         preds.append(p[: hi - lo].numpy())
         sts.append(s[: hi - lo].numpy())
-    return tuple(np.concatenate(a) for a in (outs, preds, sts, *extras) if a)  # (a block the parts lack: no array)
+    return tuple(np.concatenate(a) for a in (outs, preds, sts, *extras.values()) if a)
 
 
 def env_rank_world() -> tuple[int, int, int]:

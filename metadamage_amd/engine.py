@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
+from math import prod
 
 import numpy as np
 
@@ -27,6 +28,93 @@ def _torch():
 def _stream_handle(torch, stream=None) -> ctypes.c_void_p:
     s = stream if stream is not None else torch.cuda.current_stream()
     return ctypes.c_void_p(s.cuda_stream)
+
+
+# --------------------------------------------------------------------------
+# what every *_device wrapper shares: pointers, buffers, checks, the call
+# --------------------------------------------------------------------------
+def _ptr(t):
+    """A tensor's device pointer for ctypes; None stays None (NULL)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _buffer(torch, name: str, given, shape, dtype, device, required: bool = False):
+    """An entry's output or tap: None stays None (required: allocated), True is
+    allocated, a tensor must be contiguous, on the device, of dtype and of
+    shape's size."""
+    if given is True or (given is None and required):
+        return torch.empty(shape, dtype=dtype, device=device)
+    if given is not None and not (given.is_cuda and given.is_contiguous() and given.dtype == dtype
+                                  and given.numel() == prod(shape)):
+        kind = str(dtype).removeprefix("torch.")
+        raise ValueError(f"{name} must be a contiguous cuda {kind} tensor of {prod(shape)} elements")
+    return given
+
+
+def _check_fit_inputs(torch, ty, tN, tm, T: int) -> None:
+    """y, N (and mm, or None) as mdfit_fit_batch takes them."""
+    for name, t in (("y", ty), ("N", tN)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == (T, _lib.LD)):
+            raise ValueError(f"{name} must be a contiguous cuda int32/uint32 view of shape [T, {_lib.LD}]")
+    if tm is not None and not (tm.is_cuda and tm.is_contiguous() and tm.numel() == T * _lib.NPOS * _lib.NMM):
+        raise ValueError("mm must be a contiguous cuda tensor of T*30*12 uint32")
+
+
+def _check_counts(ty, tN, T: int) -> None:
+    """y, N as the post-fit entries read them: the finished call's counts."""
+    for name, a in (("y", ty), ("N", tN)):
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
+            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+
+
+def _check_records(res, T: int) -> None:
+    """res as the MAP post-fit entries read it: exactly these T taxa's records."""
+    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+
+
+def _check_map(ty, tN, res, T: int) -> None:
+    """The inputs of a MAP post-fit entry: (ty, tN, res, T)."""
+    _check_counts(ty, tN, T)
+    _check_records(res, T)
+
+
+def _check_nuts(res, T: int, opts) -> None:
+    """The inputs of a NUTS post-fit entry: the records of at least T taxa and,
+    in the sampling mode, a workspace that holds their draws under opts."""
+    if not (res.out.is_contiguous() and int(res.out.shape[0]) >= T):
+        raise ValueError("res must hold the contiguous records of these T taxa")
+    if int(opts.mode) == _lib.MODE_NUTS and (res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts)):
+        raise ValueError("res.workspace does not hold the draws of T taxa under opts")
+
+
+def _map_is(torch, stem: str, head, keys, outputs, taps, adapt_rounds, adapt, stream):
+    """Call a MAP importance-sampling entry, mdfit_map_<stem> or mdfit_map_<stem>_adapt.
+
+    head: (y, N, res, T, S[, R]); keys: (seed, index_base[, d0]); outputs: the
+    records; taps: the optional ones (None: NULL).  The _adapt entry runs when
+    adapt_rounds != 0 or adapt is given (True: allocated; False: the rounds
+    without their record, NULL); its argument list is the plain one with
+    adapt_rounds behind the head and adapt behind the outputs (include/mdfit.h).
+    Returns the outputs, the taps asked for and the adapt record -- the record
+    itself when it is all there is."""
+    ty, tN, res, T, *counts = head
+    no_record = adapt is False
+    adapt = None if no_record else adapt
+    use_adapt = int(adapt_rounds) != 0 or adapt is not None
+    if use_adapt and not no_record:
+        adapt = _buffer(torch, "adapt", adapt, (T, 3, _lib.NMAPADAPT), torch.float64, ty.device, required=True)
+    _check_map(ty, tN, res, T)
+    args = [_ptr(ty), _ptr(tN), _ptr(res.out), _ptr(res.status), T, *counts]
+    if use_adapt:
+        args.append(int(adapt_rounds))
+    args += [*keys, *map(_ptr, outputs)]
+    if use_adapt:
+        args.append(_ptr(adapt))
+    fn = getattr(_lib.load(), f"mdfit_map_{stem}_adapt" if use_adapt else f"mdfit_map_{stem}")
+    _lib.check(fn(*args, *map(_ptr, taps), _stream_handle(torch, stream)))
+    got = (*outputs, *(t for t in taps if t is not None), *((adapt,) if adapt is not None else ()))
+    return got[0] if len(got) == 1 else got
 
 
 @dataclass
@@ -116,30 +204,14 @@ def fit_batch_device(ty, tN, tm=None, opts: _lib.MdfitOpts | None = None, res: F
     torch = _torch()
     lib = _lib.load()
     T = int(ty.shape[0])
-    for name, t in (("y", ty), ("N", tN)):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == (T, _lib.LD)):
-            raise ValueError(f"{name} must be a contiguous cuda int32/uint32 view of shape [T, {_lib.LD}]")
-    if tm is not None and not (tm.is_cuda and tm.is_contiguous() and tm.numel() == T * _lib.NPOS * _lib.NMM):
-        raise ValueError("mm must be a contiguous cuda tensor of T*30*12 uint32")
+    _check_fit_inputs(torch, ty, tN, tm, T)
     if res is None:
         res = alloc_outputs(T, device=ty.device, opts=opts)
     o = opts if opts is not None else _lib.default_opts()
     if res.workspace is None or res.workspace.numel() < workspace_bytes(T, o):
         res.workspace = alloc_workspace(T, ty.device, o)
-    _lib.check(
-        lib.mdfit_fit_batch(
-            ctypes.c_void_p(ty.data_ptr()),
-            ctypes.c_void_p(tN.data_ptr()),
-            ctypes.c_void_p(tm.data_ptr()) if tm is not None else None,
-            T,
-            ctypes.byref(o),
-            ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.pred.data_ptr()) if res.pred is not None else None,
-            ctypes.c_void_p(res.status.data_ptr()),
-            ctypes.c_void_p(res.workspace.data_ptr()),
-            _stream_handle(torch, stream),
-        )
-    )
+    _lib.check(lib.mdfit_fit_batch(_ptr(ty), _ptr(tN), _ptr(tm), T, ctypes.byref(o), _ptr(res.out), _ptr(res.pred),
+                                   _ptr(res.status), _ptr(res.workspace), _stream_handle(torch, stream)))
     return res
 
 
@@ -153,18 +225,13 @@ def map_laplace_device(ty, tN, res: FitBatch, lap=None, gh=None, stream=None, u=
     torch = _torch()
     lib = _lib.load()
     T = int(ty.shape[0])
-    if lap is None:
-        lap = torch.empty((T, 3, _lib.NLAPLACE), dtype=torch.float64, device=ty.device)
-    for name, t, n in (("lap", lap, T * 3 * _lib.NLAPLACE), ("gh", gh, T * 3 * 20), ("u", u, T * 3 * 4)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    args = [ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.status.data_ptr()), T, ctypes.c_void_p(lap.data_ptr()),
-            ctypes.c_void_p(gh.data_ptr()) if gh is not None else None]
+    lap = _buffer(torch, "lap", lap, (T, 3, _lib.NLAPLACE), torch.float64, ty.device, required=True)
+    _buffer(torch, "gh", gh, (T, 3, 20), torch.float64, ty.device)
+    _buffer(torch, "u", u, (T, 3, 4), torch.float64, ty.device)
+    _check_records(res, T)
+    args = [_ptr(ty), _ptr(tN), _ptr(res.out), _ptr(res.status), T, _ptr(lap), _ptr(gh)]
     if u is not None:
-        _lib.check(lib.mdfit_map_laplace_u(*args, ctypes.c_void_p(u.data_ptr()), _stream_handle(torch, stream)))
+        _lib.check(lib.mdfit_map_laplace_u(*args, _ptr(u), _stream_handle(torch, stream)))
     else:
         _lib.check(lib.mdfit_map_laplace(*args, _stream_handle(torch, stream)))
     return lap
@@ -186,37 +253,11 @@ def map_psis_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
     is then the last element of the returned tuple, and draws are the best
     round's."""
     torch = _torch()
-    lib = _lib.load()
-    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
-    use_adapt = R != 0 or adapt is not None
-    if use_adapt and (adapt is None or adapt is True):
-        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
-    if psis is None:
-        psis = torch.empty((T, 3, _lib.NMAPPSIS), dtype=torch.float64, device=ty.device)
-    if draws is True:
-        draws = torch.empty((T, 3, S, 6), dtype=torch.float64, device=ty.device)
-    for name, t, n in (("psis", psis, T * 3 * _lib.NMAPPSIS), ("draws", draws, T * 3 * S * 6),
-                       ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
-    for name, a in (("y", ty), ("N", tN)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    if use_adapt:
-        _lib.check(lib.mdfit_map_psis_adapt(
-            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(seed), int(index_base),
-            ctypes.c_void_p(psis.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
-            ctypes.c_void_p(draws.data_ptr()) if draws is not None else None, _stream_handle(torch, stream)))
-        return (psis, adapt) if draws is None else (psis, draws, adapt)
-    _lib.check(lib.mdfit_map_psis(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
-                                  ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S,
-                                  int(seed), int(index_base), ctypes.c_void_p(psis.data_ptr()),
-                                  ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
-                                  _stream_handle(torch, stream)))
-    return psis if draws is None else (psis, draws)
+    T, S, dev = int(ty.shape[0]), int(num_draws), ty.device
+    psis = _buffer(torch, "psis", psis, (T, 3, _lib.NMAPPSIS), torch.float64, dev, required=True)
+    draws = _buffer(torch, "draws", draws, (T, 3, S, 6), torch.float64, dev)
+    return _map_is(torch, "psis", (ty, tN, res, T, S), (int(seed), int(index_base)), (psis,), (draws,),
+                   adapt_rounds, adapt, stream)
 
 
 def map_quant_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0,
@@ -235,41 +276,11 @@ def map_quant_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0,
     of the returned tuple.  adapt=False: the rounds without their record (the
     chunked dispatch, whose map_psis launch has written it)."""
     torch = _torch()
-    lib = _lib.load()
-    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
-    no_record = adapt is False
-    adapt = None if no_record else adapt
-    use_adapt = R != 0 or adapt is not None
-    if use_adapt and not no_record and (adapt is None or adapt is True):
-        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
-    if quant is None:
-        quant = torch.empty((T, 3, _lib.NMAPQUANT), dtype=torch.float64, device=ty.device)
-    if values is True:
-        values = torch.empty((T, 3, S, 6), dtype=torch.float64, device=ty.device)
-    for name, t, n in (("quant", quant, T * 3 * _lib.NMAPQUANT), ("values", values, T * 3 * S * 6),
-                       ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
-    for name, a in (("y", ty), ("N", tN)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    head = [ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.status.data_ptr()), T, S]
-    tap = ctypes.c_void_p(values.data_ptr()) if values is not None else None
-    got = quant if values is None else (quant, values)
-    if use_adapt:
-        _lib.check(lib.mdfit_map_quant_adapt(*head, R, int(seed), int(index_base), float(d0),
-                                             ctypes.c_void_p(quant.data_ptr()),
-                                             ctypes.c_void_p(adapt.data_ptr()) if adapt is not None else None, tap,
-                                             _stream_handle(torch, stream)))
-        if adapt is None:
-            return got
-        return (quant, adapt) if values is None else (quant, values, adapt)
-    _lib.check(lib.mdfit_map_quant(*head, int(seed), int(index_base), float(d0), ctypes.c_void_p(quant.data_ptr()),
-                                   tap, _stream_handle(torch, stream)))
-    return got
+    T, S, dev = int(ty.shape[0]), int(num_draws), ty.device
+    quant = _buffer(torch, "quant", quant, (T, 3, _lib.NMAPQUANT), torch.float64, dev, required=True)
+    values = _buffer(torch, "values", values, (T, 3, S, 6), torch.float64, dev)
+    return _map_is(torch, "quant", (ty, tN, res, T, S), (int(seed), int(index_base), float(d0)), (quant,), (values,),
+                   adapt_rounds, adapt, stream)
 
 
 def weighted_order_stats(v, w, d0: float = 0.01, device="cuda"):
@@ -306,43 +317,12 @@ def map_waic_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, 
     NMAPADAPT]): mdfit_map_waic_adapt, the PMD rows with mdfit_map_psis_adapt's
     rounds; the adapt block is then the last element of the returned tuple."""
     torch = _torch()
-    lib = _lib.load()
-    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
-    use_adapt = R != 0 or adapt is not None
-    if use_adapt and (adapt is None or adapt is True):
-        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
-    if waic is None:
-        waic = torch.empty((T, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=ty.device)
-    if pointwise is True:
-        pointwise = torch.empty((T, _lib.NSUBFIT, _lib.NPOS, 2), dtype=torch.float64, device=ty.device)
-    if draws is True:
-        draws = torch.empty((T, _lib.NSUBFIT, S, 6), dtype=torch.float64, device=ty.device)
-    for name, t, n in (("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC),
-                       ("pointwise", pointwise, T * _lib.NSUBFIT * _lib.NPOS * 2),
-                       ("draws", draws, T * _lib.NSUBFIT * S * 6), ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
-    for name, a in (("y", ty), ("N", tN)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    if use_adapt:
-        _lib.check(lib.mdfit_map_waic_adapt(
-            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(seed), int(index_base),
-            ctypes.c_void_p(waic.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
-            ctypes.c_void_p(pointwise.data_ptr()) if pointwise is not None else None,
-            ctypes.c_void_p(draws.data_ptr()) if draws is not None else None, _stream_handle(torch, stream)))
-        return (waic,) + tuple(x for x in (pointwise, draws) if x is not None) + (adapt,)
-    _lib.check(lib.mdfit_map_waic(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
-                                  ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S,
-                                  int(seed), int(index_base), ctypes.c_void_p(waic.data_ptr()),
-                                  ctypes.c_void_p(pointwise.data_ptr()) if pointwise is not None else None,
-                                  ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
-                                  _stream_handle(torch, stream)))
-    got = (waic,) + tuple(x for x in (pointwise, draws) if x is not None)
-    return waic if len(got) == 1 else got
+    T, S, dev = int(ty.shape[0]), int(num_draws), ty.device
+    waic = _buffer(torch, "waic", waic, (T, _lib.NWAICROW, _lib.NMAPWAIC), torch.float64, dev, required=True)
+    pointwise = _buffer(torch, "pointwise", pointwise, (T, _lib.NSUBFIT, _lib.NPOS, 2), torch.float64, dev)
+    draws = _buffer(torch, "draws", draws, (T, _lib.NSUBFIT, S, 6), torch.float64, dev)
+    return _map_is(torch, "waic", (ty, tN, res, T, S), (int(seed), int(index_base)), (waic,), (pointwise, draws),
+                   adapt_rounds, adapt, stream)
 
 
 def map_evidence_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, evid=None,
@@ -361,39 +341,11 @@ def map_evidence_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int =
     mdfit_map_psis_adapt's rounds; the adapt block is then the last element of
     the returned tuple."""
     torch = _torch()
-    lib = _lib.load()
-    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
-    if draws is False:
-        draws = None
-    use_adapt = R != 0 or adapt is not None
-    if use_adapt and (adapt is None or adapt is True):
-        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
-    if evid is None:
-        evid = torch.empty((T, _lib.NEVIDROW, _lib.NMAPEVID), dtype=torch.float64, device=ty.device)
-    if draws is True:
-        draws = torch.empty((T, _lib.NSUBFIT, S, 6), dtype=torch.float64, device=ty.device)
-    for name, t, n in (("evid", evid, T * _lib.NEVIDROW * _lib.NMAPEVID), ("draws", draws, T * _lib.NSUBFIT * S * 6),
-                       ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
-    for name, a in (("y", ty), ("N", tN)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    if use_adapt:
-        _lib.check(lib.mdfit_map_evidence_adapt(
-            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(seed), int(index_base),
-            ctypes.c_void_p(evid.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
-            ctypes.c_void_p(draws.data_ptr()) if draws is not None else None, _stream_handle(torch, stream)))
-        return (evid,) + ((draws,) if draws is not None else ()) + (adapt,)
-    _lib.check(lib.mdfit_map_evidence(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
-                                      ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T,
-                                      S, int(seed), int(index_base), ctypes.c_void_p(evid.data_ptr()),
-                                      ctypes.c_void_p(draws.data_ptr()) if draws is not None else None,
-                                      _stream_handle(torch, stream)))
-    return evid if draws is None else (evid, draws)
+    T, S, dev = int(ty.shape[0]), int(num_draws), ty.device
+    evid = _buffer(torch, "evid", evid, (T, _lib.NEVIDROW, _lib.NMAPEVID), torch.float64, dev, required=True)
+    draws = _buffer(torch, "draws", None if draws is False else draws, (T, _lib.NSUBFIT, S, 6), torch.float64, dev)
+    return _map_is(torch, "evidence", (ty, tN, res, T, S), (int(seed), int(index_base)), (evid,), (draws,),
+                   adapt_rounds, adapt, stream)
 
 
 def map_joint_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0, index_base: int = 0, waic=None,
@@ -411,45 +363,14 @@ def map_joint_device(ty, tN, res: FitBatch, num_draws: int = 256, seed: int = 0,
     NMAPADAPT]): mdfit_map_joint_adapt; the adapt block is then the last element
     of the returned tuple."""
     torch = _torch()
-    lib = _lib.load()
-    T, S, R = int(ty.shape[0]), int(num_draws), int(adapt_rounds)
-    use_adapt = R != 0 or adapt is not None
-    if use_adapt and (adapt is None or adapt is True):
-        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
-    if waic is None:
-        waic = torch.empty((T, _lib.NWAICROW, _lib.NMAPWAIC), dtype=torch.float64, device=ty.device)
-    if evid is None:
-        evid = torch.empty((T, _lib.NEVIDROW, _lib.NMAPEVID), dtype=torch.float64, device=ty.device)
-    if psis is None:
-        psis = torch.empty((T, 3, _lib.NMAPPSIS), dtype=torch.float64, device=ty.device)
-    if pointwise is True:
-        pointwise = torch.empty((T, _lib.NSUBFIT, _lib.NPOS, 2), dtype=torch.float64, device=ty.device)
-    if draws is True:
-        draws = torch.empty((T, _lib.NSUBFIT, S, 6), dtype=torch.float64, device=ty.device)
-    for name, t, n in (("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC),
-                       ("evid", evid, T * _lib.NEVIDROW * _lib.NMAPEVID), ("psis", psis, T * 3 * _lib.NMAPPSIS),
-                       ("pointwise", pointwise, T * _lib.NSUBFIT * _lib.NPOS * 2),
-                       ("draws", draws, T * _lib.NSUBFIT * S * 6), ("adapt", adapt, T * 3 * _lib.NMAPADAPT)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
-    for name, a in (("y", ty), ("N", tN)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    head = [ptr(ty), ptr(tN), ptr(res.out), ptr(res.status), T, S]
-    got = (waic, evid, psis) + tuple(x for x in (pointwise, draws) if x is not None)
-    if use_adapt:
-        _lib.check(lib.mdfit_map_joint_adapt(*head, R, int(seed), int(index_base), ptr(waic), ptr(evid), ptr(psis),
-                                             ptr(adapt), ptr(pointwise), ptr(draws), _stream_handle(torch, stream)))
-        return got + (adapt,)
-    _lib.check(lib.mdfit_map_joint(*head, int(seed), int(index_base), ptr(waic), ptr(evid), ptr(psis), ptr(pointwise),
-                                   ptr(draws), _stream_handle(torch, stream)))
-    return got
+    T, S, dev = int(ty.shape[0]), int(num_draws), ty.device
+    waic = _buffer(torch, "waic", waic, (T, _lib.NWAICROW, _lib.NMAPWAIC), torch.float64, dev, required=True)
+    evid = _buffer(torch, "evid", evid, (T, _lib.NEVIDROW, _lib.NMAPEVID), torch.float64, dev, required=True)
+    psis = _buffer(torch, "psis", psis, (T, 3, _lib.NMAPPSIS), torch.float64, dev, required=True)
+    pointwise = _buffer(torch, "pointwise", pointwise, (T, _lib.NSUBFIT, _lib.NPOS, 2), torch.float64, dev)
+    draws = _buffer(torch, "draws", draws, (T, _lib.NSUBFIT, S, 6), torch.float64, dev)
+    return _map_is(torch, "joint", (ty, tN, res, T, S), (int(seed), int(index_base)), (waic, evid, psis),
+                   (pointwise, draws), adapt_rounds, adapt, stream)
 
 
 def fit_batch_indexed_device(ty, tN, tm, taxon_index, opts: _lib.MdfitOpts, res: FitBatch | None = None,
@@ -462,11 +383,7 @@ def fit_batch_indexed_device(ty, tN, tm, taxon_index, opts: _lib.MdfitOpts, res:
     torch = _torch()
     lib = _lib.load()
     T = int(ty.shape[0])
-    for name, t in (("y", ty), ("N", tN)):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == (T, _lib.LD)):
-            raise ValueError(f"{name} must be a contiguous cuda int32/uint32 view of shape [T, {_lib.LD}]")
-    if tm is not None and not (tm.is_cuda and tm.is_contiguous() and tm.numel() == T * _lib.NPOS * _lib.NMM):
-        raise ValueError("mm must be a contiguous cuda tensor of T*30*12 uint32")
+    _check_fit_inputs(torch, ty, tN, tm, T)
     if taxon_index is not None:
         if not (taxon_index.is_cuda and taxon_index.is_contiguous() and taxon_index.dtype == torch.int64
                 and taxon_index.numel() == T):
@@ -478,12 +395,8 @@ def fit_batch_indexed_device(ty, tN, tm, taxon_index, opts: _lib.MdfitOpts, res:
     if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) >= T
             and (res.pred is None or res.pred.is_contiguous())):
         raise ValueError("res must hold contiguous records of at least T taxa")
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    _lib.check(lib.mdfit_fit_batch_indexed(ptr(ty), ptr(tN), ptr(tm), T, ptr(taxon_index), ctypes.byref(opts),
-                                           ptr(res.out), ptr(res.pred), ptr(res.status), ptr(res.workspace),
+    _lib.check(lib.mdfit_fit_batch_indexed(_ptr(ty), _ptr(tN), _ptr(tm), T, _ptr(taxon_index), ctypes.byref(opts),
+                                           _ptr(res.out), _ptr(res.pred), _ptr(res.status), _ptr(res.workspace),
                                            _stream_handle(torch, stream)))
     return res
 
@@ -495,20 +408,24 @@ def auto_route_device(res: FitBatch, psis, waic, route=None, stream=None):
     and composes res.out's row of every taxon with route 0 in place.  Returns
     route."""
     torch = _torch()
-    lib = _lib.load()
     T = int(res.out.shape[0])
-    if route is None:
-        route = torch.empty((T,), dtype=torch.int32, device=res.out.device)
-    for name, t, n in (("psis", psis, T * 3 * _lib.NMAPPSIS), ("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC)):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda float64 tensor of {n} elements")
-    if not (route.is_cuda and route.is_contiguous() and route.dtype == torch.int32 and route.numel() == T):
-        raise ValueError("route must be a contiguous cuda int32 tensor of T entries")
+    route = _route_inputs(torch, res, T, route, (("psis", psis, (T, 3, _lib.NMAPPSIS), torch.float64),
+                                                 ("waic", waic, (T, _lib.NWAICROW, _lib.NMAPWAIC), torch.float64)))
+    _lib.check(_lib.load().mdfit_auto_route(_ptr(res.status), _ptr(psis), _ptr(waic), T, _ptr(res.out), _ptr(route),
+                                            _stream_handle(torch, stream)))
+    return route
+
+
+def _route_inputs(torch, res, T: int, route, records):
+    """The checks the two routing entries share: the given records (name, tensor, shape, dtype), the route tensor
+    (None: allocated; returned) and res."""
+    for name, t, shape, dtype in records:
+        if t is None:
+            raise ValueError(f"{name} is required")
+        _buffer(torch, name, t, shape, dtype, res.out.device)
+    route = _buffer(torch, "route", route, (T,), torch.int32, res.out.device, required=True)
     if not (res.out.is_contiguous() and res.status.is_contiguous() and res.status.numel() == T):
         raise ValueError("res must hold the contiguous records of these T taxa")
-    _lib.check(lib.mdfit_auto_route(ctypes.c_void_p(res.status.data_ptr()), ctypes.c_void_p(psis.data_ptr()),
-                                    ctypes.c_void_p(waic.data_ptr()), T, ctypes.c_void_p(res.out.data_ptr()),
-                                    ctypes.c_void_p(route.data_ptr()), _stream_handle(torch, stream)))
     return route
 
 
@@ -519,28 +436,17 @@ def auto_route_pred_device(res: FitBatch, psis, waic, prec, ppred, route=None, s
     route 0 also gets its five predictive columns from prec and, where res.pred
     is not None, its 90 prediction floats from ppred.  Returns route."""
     torch = _torch()
-    lib = _lib.load()
     T = int(res.out.shape[0])
-    if route is None:
-        route = torch.empty((T,), dtype=torch.int32, device=res.out.device)
-    for name, t, n, dt in (("psis", psis, T * 3 * _lib.NMAPPSIS, torch.float64),
-                           ("waic", waic, T * _lib.NWAICROW * _lib.NMAPWAIC, torch.float64),
-                           ("prec", prec, T * _lib.NMAPPRED, torch.float64),
-                           ("ppred", ppred, T * _lib.NPRED * _lib.NPOS, torch.float32)):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of {n} elements")
-    if not (route.is_cuda and route.is_contiguous() and route.dtype == torch.int32 and route.numel() == T):
-        raise ValueError("route must be a contiguous cuda int32 tensor of T entries")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and res.status.numel() == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
+    route = _route_inputs(torch, res, T, route, (("psis", psis, (T, 3, _lib.NMAPPSIS), torch.float64),
+                                                 ("waic", waic, (T, _lib.NWAICROW, _lib.NMAPWAIC), torch.float64),
+                                                 ("prec", prec, (T, _lib.NMAPPRED), torch.float64),
+                                                 ("ppred", ppred, (T, _lib.NPRED, _lib.NPOS), torch.float32)))
     if res.pred is not None and not (res.pred.is_contiguous() and res.pred.dtype == torch.float32
                                      and res.pred.numel() == T * _lib.NPRED * _lib.NPOS):
         raise ValueError("res.pred must be a contiguous float32 tensor [T, 3, 30]")
-    _lib.check(lib.mdfit_auto_route_pred(
-        ctypes.c_void_p(res.status.data_ptr()), ctypes.c_void_p(psis.data_ptr()), ctypes.c_void_p(waic.data_ptr()),
-        ctypes.c_void_p(prec.data_ptr()), ctypes.c_void_p(ppred.data_ptr()), T, ctypes.c_void_p(res.out.data_ptr()),
-        ctypes.c_void_p(res.pred.data_ptr()) if res.pred is not None else None, ctypes.c_void_p(route.data_ptr()),
-        _stream_handle(torch, stream)))
+    _lib.check(_lib.load().mdfit_auto_route_pred(_ptr(res.status), _ptr(psis), _ptr(waic), _ptr(prec), _ptr(ppred), T,
+                                                 _ptr(res.out), _ptr(res.pred), _ptr(route),
+                                                 _stream_handle(torch, stream)))
     return route
 
 
@@ -724,6 +630,8 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
     T = int(y.shape[0])
     dev = torch.device(device)
     o_map, _ = auto_opts(opts)
+    parts = blocks.describe(None, {"psis_adapt": psis_adapt, "auto_pred": auto_pred}, psis_draws=psis_draws,
+                            pred_draws=pred_draws, with_auto=True).parts  # (auto, then the tails asked for)
     budget = budget_bytes if budget_bytes is not None else default_budget(dev)
     # (the MAP pass's buffers, its psis and waic records beside them: two sets' worth is an upper bound)
     chunks = plan_chunks(T, o_map, budget, with_mm=mm is not None, dest_on_device=dest is not None, with_waic=True)
@@ -731,9 +639,7 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
         h_out = np.empty((T, H_OUT_COLS), np.float64)
         h_pred = np.empty((T, _lib.NPRED, _lib.NPOS), np.float32)
         h_status = np.empty((T,), np.int32)
-        h_auto = np.empty((T, _lib.NAUTO), np.float32)
-        h_adapt = np.empty((T, _lib.NADAPTOUT), np.float32)
-        h_auto_pred = np.empty((T, _lib.NAUTOPRED), np.float32)
+        h_parts = {p.attr: np.empty((T, *p.shape), np.float32) for p in parts}
     for lo, hi in chunks:
         ty, tN, tm = to_device_counts(y[lo:hi], N[lo:hi], mm[lo:hi] if mm is not None else None, device=dev)
         o = _lib.MdfitOpts.from_buffer_copy(o_map)
@@ -743,29 +649,19 @@ def fit_auto_chunks(y, N, mm, opts: _lib.MdfitOpts | None = None, psis_draws: in
             res = FitBatch(dest.out[lo:hi], dest.pred[lo:hi] if dest.pred is not None else None, dest.status[lo:hi])
         res, _route, auto = fit_auto_device(ty, tN, tm, o, psis_draws, res=res, budget_bytes=budget_bytes,
                                             psis_adapt=psis_adapt, auto_pred=auto_pred, pred_draws=pred_draws)
-        if dest is not None:
-            dest.auto[lo:hi].copy_(auto)
-            if auto_pred:
-                dest.auto_pred[lo:hi].copy_(res.auto_pred)
-            if int(psis_adapt) > 0:
-                dest.adapt[lo:hi].copy_(res.adapt)
-        else:
-            if int(psis_adapt) > 0:
-                h_adapt[lo:hi] = res.adapt.cpu().numpy()
-            if auto_pred:
-                h_auto_pred[lo:hi] = res.auto_pred.cpu().numpy()
+        res.auto = auto  # (beside res.auto_pred and res.adapt, which fit_auto_device has set)
+        for p in parts:
+            if dest is not None:
+                getattr(dest, p.attr)[lo:hi].copy_(getattr(res, p.attr))
+            else:
+                h_parts[p.attr][lo:hi] = getattr(res, p.attr).cpu().numpy()
+        if dest is None:
             h_out[lo:hi] = res.out[:, :H_OUT_COLS].cpu().numpy()
             h_pred[lo:hi] = res.pred.cpu().numpy()
             h_status[lo:hi] = res.status.cpu().numpy()
-            h_auto[lo:hi] = auto.cpu().numpy()
     if dest is not None:
         return dest
-    got = (h_out, h_pred, h_status, h_auto)
-    if auto_pred:
-        got += (h_auto_pred,)
-    if int(psis_adapt) > 0:
-        got += (h_adapt,)
-    return got
+    return (h_out, h_pred, h_status, *h_parts.values())
 
 
 def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int = 1000, seed: int = 0,
@@ -786,47 +682,13 @@ def map_pred_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int =
     mdfit_map_psis_adapt's rounds and the predictive drawn from the best round;
     the adapt block is then the last element of the returned tuple."""
     torch = _torch()
-    lib = _lib.load()
-    T, S, R = int(ty.shape[0]), int(num_draws), int(num_pred)
-    use_adapt = int(adapt_rounds) != 0 or adapt is not None
-    if use_adapt and (adapt is None or adapt is True):
-        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
-    if ppred is None:
-        ppred = torch.empty((T, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=ty.device)
-    if rec is None:
-        rec = torch.empty((T, _lib.NMAPPRED), dtype=torch.float64, device=ty.device)
-    if index is True:
-        index = torch.empty((T, 3, R), dtype=torch.int32, device=ty.device)
-    if counts is True:
-        counts = torch.empty((T, _lib.NPREDJOB, R), dtype=torch.int32, device=ty.device)
-    for name, t, n, dt in (("ppred", ppred, T * _lib.NPRED * _lib.NPOS, torch.float32),
-                           ("rec", rec, T * _lib.NMAPPRED, torch.float64),
-                           ("index", index, T * 3 * R, torch.int32),
-                           ("counts", counts, T * _lib.NPREDJOB * R, torch.int32),
-                           ("adapt", adapt, T * 3 * _lib.NMAPADAPT, torch.float64)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of {n} elements")
-    for name, a in (("y", ty), ("N", tN)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    if use_adapt:
-        _lib.check(lib.mdfit_map_pred_adapt(
-            ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.status.data_ptr()), T, S, R, int(adapt_rounds), int(seed), int(index_base),
-            ctypes.c_void_p(ppred.data_ptr()), ctypes.c_void_p(rec.data_ptr()), ctypes.c_void_p(adapt.data_ptr()),
-            ctypes.c_void_p(index.data_ptr()) if index is not None else None,
-            ctypes.c_void_p(counts.data_ptr()) if counts is not None else None, _stream_handle(torch, stream)))
-        return (ppred, rec) + tuple(x for x in (index, counts) if x is not None) + (adapt,)
-    _lib.check(lib.mdfit_map_pred(ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()),
-                                  ctypes.c_void_p(res.out.data_ptr()), ctypes.c_void_p(res.status.data_ptr()), T, S, R,
-                                  int(seed), int(index_base), ctypes.c_void_p(ppred.data_ptr()),
-                                  ctypes.c_void_p(rec.data_ptr()),
-                                  ctypes.c_void_p(index.data_ptr()) if index is not None else None,
-                                  ctypes.c_void_p(counts.data_ptr()) if counts is not None else None,
-                                  _stream_handle(torch, stream)))
-    return (ppred, rec) + tuple(x for x in (index, counts) if x is not None)
+    T, S, R, dev = int(ty.shape[0]), int(num_draws), int(num_pred), ty.device
+    ppred = _buffer(torch, "ppred", ppred, (T, _lib.NPRED, _lib.NPOS), torch.float32, dev, required=True)
+    rec = _buffer(torch, "rec", rec, (T, _lib.NMAPPRED), torch.float64, dev, required=True)
+    index = _buffer(torch, "index", index, (T, 3, R), torch.int32, dev)
+    counts = _buffer(torch, "counts", counts, (T, _lib.NPREDJOB, R), torch.int32, dev)
+    return _map_is(torch, "pred", (ty, tN, res, T, S, R), (int(seed), int(index_base)), (ppred, rec), (index, counts),
+                   adapt_rounds, adapt, stream)
 
 
 def map_ppc_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int = 1000, seed: int = 0,
@@ -849,49 +711,14 @@ def map_ppc_device(ty, tN, res: FitBatch, num_draws: int = 256, num_pred: int = 
     the last element of the returned tuple.  adapt=False: the rounds without
     their record (the chunked dispatch, whose map_pred launch has written it)."""
     torch = _torch()
-    lib = _lib.load()
-    T, S, R = int(ty.shape[0]), int(num_draws), int(num_pred)
-    no_record = adapt is False
-    adapt = None if no_record else adapt
-    use_adapt = int(adapt_rounds) != 0 or adapt is not None
-    if use_adapt and not no_record and (adapt is None or adapt is True):
-        adapt = torch.empty((T, 3, _lib.NMAPADAPT), dtype=torch.float64, device=ty.device)
-    if ppos is None:
-        ppos = torch.empty((T, _lib.NPOS), dtype=torch.float32, device=ty.device)
-    if rec is None:
-        rec = torch.empty((T, _lib.NMAPPPC), dtype=torch.float64, device=ty.device)
-    if index is True:
-        index = torch.empty((T, R), dtype=torch.int32, device=ty.device)
-    if counts is True:
-        counts = torch.empty((T, _lib.NPOS, R), dtype=torch.int32, device=ty.device)
-    if disc is True:
-        disc = torch.empty((T, R, 4), dtype=torch.float64, device=ty.device)
-    for name, t, n, dt in (("ppos", ppos, T * _lib.NPOS, torch.float32),
-                           ("rec", rec, T * _lib.NMAPPPC, torch.float64),
-                           ("index", index, T * R, torch.int32),
-                           ("counts", counts, T * _lib.NPOS * R, torch.int32),
-                           ("disc", disc, T * R * 4, torch.float64),
-                           ("adapt", adapt, T * 3 * _lib.NMAPADAPT, torch.float64)):
-        if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of {n} elements")
-    for name, a in (("y", ty), ("N", tN)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and res.status.is_contiguous() and int(res.out.shape[0]) == T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    head = [ctypes.c_void_p(ty.data_ptr()), ctypes.c_void_p(tN.data_ptr()), ctypes.c_void_p(res.out.data_ptr()),
-            ctypes.c_void_p(res.status.data_ptr()), T, S, R]
-    taps = [ctypes.c_void_p(x.data_ptr()) if x is not None else None for x in (index, counts, disc)]
-    got = (ppos, rec) + tuple(x for x in (index, counts, disc) if x is not None)
-    if use_adapt:
-        _lib.check(lib.mdfit_map_ppc_adapt(*head, int(adapt_rounds), int(seed), int(index_base),
-                                           ctypes.c_void_p(ppos.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
-                                           ctypes.c_void_p(adapt.data_ptr()) if adapt is not None else None, *taps,
-                                           _stream_handle(torch, stream)))
-        return got + ((adapt,) if adapt is not None else ())
-    _lib.check(lib.mdfit_map_ppc(*head, int(seed), int(index_base), ctypes.c_void_p(ppos.data_ptr()),
-                                 ctypes.c_void_p(rec.data_ptr()), *taps, _stream_handle(torch, stream)))
-    return got
+    T, S, R, dev = int(ty.shape[0]), int(num_draws), int(num_pred), ty.device
+    ppos = _buffer(torch, "ppos", ppos, (T, _lib.NPOS), torch.float32, dev, required=True)
+    rec = _buffer(torch, "rec", rec, (T, _lib.NMAPPPC), torch.float64, dev, required=True)
+    index = _buffer(torch, "index", index, (T, R), torch.int32, dev)
+    counts = _buffer(torch, "counts", counts, (T, _lib.NPOS, R), torch.int32, dev)
+    disc = _buffer(torch, "disc", disc, (T, R, 4), torch.float64, dev)
+    return _map_is(torch, "ppc", (ty, tN, res, T, S, R), (int(seed), int(index_base)), (ppos, rec),
+                   (index, counts, disc), adapt_rounds, adapt, stream)
 
 
 def resample(w, num_pred: int, device="cuda"):
@@ -960,20 +787,11 @@ def nuts_diag_device(res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, diag=None
     the MCSE of D_max, float64 diag[T, 6, NNUTSDIAG] (_lib.NUTSDIAG_FIELDS).
     Reads res.workspace and res.out only.  Returns diag."""
     torch = _torch()
-    lib = _lib.load()
     T = int(n_taxa)
-    if diag is None:
-        diag = torch.empty((T, _lib.NSUBFIT, _lib.NNUTSDIAG), dtype=torch.float64, device=res.out.device)
-    if not (diag.is_cuda and diag.is_contiguous() and diag.dtype == torch.float64
-            and diag.numel() == T * _lib.NSUBFIT * _lib.NNUTSDIAG):
-        raise ValueError(f"diag must be a contiguous cuda float64 tensor of {T * _lib.NSUBFIT * _lib.NNUTSDIAG} elements")
-    if not (res.out.is_contiguous() and int(res.out.shape[0]) >= T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    if int(opts.mode) == _lib.MODE_NUTS and (res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts)):
-        raise ValueError("res.workspace does not hold the draws of T taxa under opts")
-    _lib.check(lib.mdfit_nuts_diag(ctypes.c_void_p(res.workspace.data_ptr()) if res.workspace is not None else None,
-                                   ctypes.c_void_p(res.out.data_ptr()), T, ctypes.byref(opts),
-                                   ctypes.c_void_p(diag.data_ptr()), _stream_handle(torch, stream)))
+    diag = _buffer(torch, "diag", diag, (T, _lib.NSUBFIT, _lib.NNUTSDIAG), torch.float64, res.out.device, required=True)
+    _check_nuts(res, T, opts)
+    _lib.check(_lib.load().mdfit_nuts_diag(_ptr(res.workspace), _ptr(res.out), T, ctypes.byref(opts), _ptr(diag),
+                                           _stream_handle(torch, stream)))
     return diag
 
 
@@ -986,20 +804,11 @@ def nuts_summary_device(res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, summ=N
     (_lib.NUTSSUMM_FIELDS).  Reads res.workspace and res.out only; independent
     of nuts_diag_device (either order on one workspace).  Returns summ."""
     torch = _torch()
-    lib = _lib.load()
     T = int(n_taxa)
-    if summ is None:
-        summ = torch.empty((T, _lib.NSUBFIT, _lib.NNUTSSUMM), dtype=torch.float64, device=res.out.device)
-    if not (summ.is_cuda and summ.is_contiguous() and summ.dtype == torch.float64
-            and summ.numel() == T * _lib.NSUBFIT * _lib.NNUTSSUMM):
-        raise ValueError(f"summ must be a contiguous cuda float64 tensor of {T * _lib.NSUBFIT * _lib.NNUTSSUMM} elements")
-    if not (res.out.is_contiguous() and int(res.out.shape[0]) >= T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    if int(opts.mode) == _lib.MODE_NUTS and (res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts)):
-        raise ValueError("res.workspace does not hold the draws of T taxa under opts")
-    _lib.check(lib.mdfit_nuts_summary(ctypes.c_void_p(res.workspace.data_ptr()) if res.workspace is not None else None,
-                                      ctypes.c_void_p(res.out.data_ptr()), T, ctypes.byref(opts),
-                                      ctypes.c_void_p(summ.data_ptr()), _stream_handle(torch, stream)))
+    summ = _buffer(torch, "summ", summ, (T, _lib.NSUBFIT, _lib.NNUTSSUMM), torch.float64, res.out.device, required=True)
+    _check_nuts(res, T, opts)
+    _lib.check(_lib.load().mdfit_nuts_summary(_ptr(res.workspace), _ptr(res.out), T, ctypes.byref(opts), _ptr(summ),
+                                              _stream_handle(torch, stream)))
     return summ
 
 
@@ -1015,32 +824,13 @@ def nuts_loo_device(y, N, res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, loo=
     independent of nuts_diag_device and nuts_summary_device (any order on one
     workspace).  Returns loo, or (loo, pointwise) when pointwise is asked for."""
     torch = _torch()
-    lib = _lib.load()
-    T = int(n_taxa)
-    if loo is None:
-        loo = torch.empty((T, _lib.NLOOROW, _lib.NNUTSLOO), dtype=torch.float64, device=res.out.device)
-    if not (loo.is_cuda and loo.is_contiguous() and loo.dtype == torch.float64
-            and loo.numel() == T * _lib.NLOOROW * _lib.NNUTSLOO):
-        raise ValueError(f"loo must be a contiguous cuda float64 tensor of {T * _lib.NLOOROW * _lib.NNUTSLOO} elements")
-    if pointwise is True:
-        pointwise = torch.empty((T, _lib.NSUBFIT, _lib.NPOS, 2), dtype=torch.float64, device=res.out.device)
-    if pointwise is not None and not (pointwise.is_cuda and pointwise.is_contiguous()
-                                      and pointwise.dtype == torch.float64
-                                      and pointwise.numel() == T * _lib.NSUBFIT * _lib.NPOS * 2):
-        raise ValueError(f"pointwise must be a contiguous cuda float64 tensor of {T * _lib.NSUBFIT * _lib.NPOS * 2} elements")
-    for name, a in (("y", y), ("N", N)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
-    if not (res.out.is_contiguous() and int(res.out.shape[0]) >= T):
-        raise ValueError("res must hold the contiguous records of these T taxa")
-    if int(opts.mode) == _lib.MODE_NUTS and (res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts)):
-        raise ValueError("res.workspace does not hold the draws of T taxa under opts")
-    _lib.check(lib.mdfit_nuts_loo(ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(N.data_ptr()),
-                                  ctypes.c_void_p(res.workspace.data_ptr()) if res.workspace is not None else None,
-                                  ctypes.c_void_p(res.out.data_ptr()), T, ctypes.byref(opts),
-                                  ctypes.c_void_p(loo.data_ptr()),
-                                  ctypes.c_void_p(pointwise.data_ptr()) if pointwise is not None else None,
-                                  _stream_handle(torch, stream)))
+    T, dev = int(n_taxa), res.out.device
+    loo = _buffer(torch, "loo", loo, (T, _lib.NLOOROW, _lib.NNUTSLOO), torch.float64, dev, required=True)
+    pointwise = _buffer(torch, "pointwise", pointwise, (T, _lib.NSUBFIT, _lib.NPOS, 2), torch.float64, dev)
+    _check_counts(y, N, T)
+    _check_nuts(res, T, opts)
+    _lib.check(_lib.load().mdfit_nuts_loo(_ptr(y), _ptr(N), _ptr(res.workspace), _ptr(res.out), T, ctypes.byref(opts),
+                                          _ptr(loo), _ptr(pointwise), _stream_handle(torch, stream)))
     return loo if pointwise is None else (loo, pointwise)
 
 
@@ -1069,25 +859,18 @@ def nuts_post_device(y, N, res: FitBatch, n_taxa: int, opts: _lib.MdfitOpts, mm=
                              ("count_flags", count_flags, T * _lib.LD, 1)):
         if t is not None and not (t.is_cuda and t.is_contiguous() and t.element_size() == size and t.numel() == n):
             raise ValueError(f"{name} must be a contiguous cuda tensor of {n} elements of {size} bytes")
-    for name, a in (("y", y), ("N", N)):
-        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and a.numel() >= T * _lib.LD):
-            raise ValueError(f"{name} must be the call's contiguous cuda 32-bit counts [T, {_lib.LD}]")
+    _check_counts(y, N, T)
     if mm is not None and not (mm.is_cuda and mm.is_contiguous() and mm.element_size() == 4
                                and mm.numel() == T * _lib.NPOS * _lib.NMM):
         raise ValueError("mm must be a contiguous cuda tensor of T*30*12 uint32")
-    if not (res.out.is_contiguous() and int(res.out.shape[0]) >= T and res.status.numel() >= T):
+    if res.status.numel() < T:
         raise ValueError("res must hold the contiguous records of these T taxa")
     if res.pred is not None and not (res.pred.is_contiguous() and res.pred.numel() >= T * _lib.NPRED * _lib.NPOS):
         raise ValueError("res.pred must be contiguous float32 [T, 3, 30]")
-    if int(opts.mode) == _lib.MODE_NUTS and (res.workspace is None or res.workspace.numel() < workspace_bytes(T, opts)):
-        raise ValueError("res.workspace does not hold the draws of T taxa under opts")
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    _lib.check(lib.mdfit_nuts_post(ptr(y), ptr(N), ptr(mm), T, ctypes.byref(opts), ptr(res.workspace), ptr(res.out),
-                                   ptr(res.pred), ptr(res.status), ptr(waic), ptr(counts), ptr(count_flags),
-                                   _stream_handle(torch, stream)))
+    _check_nuts(res, T, opts)
+    _lib.check(lib.mdfit_nuts_post(_ptr(y), _ptr(N), _ptr(mm), T, ctypes.byref(opts), _ptr(res.workspace),
+                                   _ptr(res.out), _ptr(res.pred), _ptr(res.status), _ptr(waic), _ptr(counts),
+                                   _ptr(count_flags), _stream_handle(torch, stream)))
     return waic, counts, count_flags
 
 
@@ -1126,87 +909,58 @@ N_SETS = 2  # device buffer sets in flight: chunk k+1's H2D (and fit) beside chu
 _BUDGET_FRAC = 0.6  # default device budget of a staging: this fraction of the free device memory
 
 
-_BLOCK = {b.name: b for b in blocks.BLOCKS}
-# one taxon's block as it leaves the device (f32), bytes
-LAP_BYTES, DIAG_BYTES, SUMM_BYTES, LOO_BYTES, PSIS_BYTES, WAIC_BYTES, PPRED_BYTES = (
-    _BLOCK[name].out_bytes for name in ("laplace", "diag", "summary", "loo", "psis", "waic", "ppred"))
+_PART = {p.name: p for p in (*blocks.BLOCKS, *blocks.TAILS)}
+# one taxon's block or tail as it leaves the device (f32), bytes
+(LAP_BYTES, DIAG_BYTES, SUMM_BYTES, LOO_BYTES, PSIS_BYTES, WAIC_BYTES, PPRED_BYTES, PPC_BYTES, QUANT_BYTES,
+ JOINT_BYTES) = (_PART[name].out_bytes for name in ("laplace", "diag", "summary", "loo", "psis", "waic", "ppred",
+                                                    "ppc", "quant", "joint"))
 PPRED_WORDS = PPRED_BYTES // 4
 PSIS_DRAWS = 256  # the default number of importance draws per sub-fit
 PRED_DRAWS = 1000  # predictive draws per job of mdfit_map_pred where the caller gives none (the reference's)
 
 
+def _pieces(block, part) -> tuple:
+    """Views of one f32 block [T, *part.shape] (torch or numpy), one per piece of part.device, shaped as computed:
+    the pieces lie in consecutive word ranges of a taxon's row."""
+    T = block.shape[0]
+    flat, views, lo = block.reshape(T, prod(part.shape)), [], 0
+    for shape, _dtype in part.device:
+        views.append(flat[:, lo:lo + prod(shape)].reshape(T, *shape))
+        lo += prod(shape)
+    return tuple(views)
+
+
 def split_ppred(block):
     """(ppred[T, 3, 30], rec[T, NMAPPRED]) views of a posterior predictive block [T, PPRED_WORDS]."""
-    n = _lib.NPRED * _lib.NPOS
-    return block[:, :n].reshape(-1, _lib.NPRED, _lib.NPOS), block[:, n:]
-
-
-PPC_BYTES = _lib.NPPCOUT * 4  # one taxon's posterior predictive check as it leaves the device (f32 ppos | rec)
-_PPC_DEVICE_BYTES = _lib.NPOS * 4 + _lib.NMAPPPC * 8  # ... and as the launch computes it (f32 ppos, f64 rec)
+    return _pieces(block, _PART["ppred"])
 
 
 def split_ppc(block):
     """(ppos[T, 30], rec[T, NMAPPPC]) views of a posterior predictive check block [T, NPPCOUT]."""
-    return block[:, :_lib.NPOS], block[:, _lib.NPOS:]
-
-
-def _check_ppc(ppc: bool, block) -> bool:
-    """ppc (the posterior predictive check, a tail of the ppred block) goes with with_ppred."""
-    if ppc and (block is None or block.name != "ppred"):
-        raise ValueError("ppc needs with_ppred: the check is of the predictive that mdfit_map_pred forms")
-    return bool(ppc)
-
-
-QUANT_BYTES = _lib.NQUANTOUT * 4  # one taxon's weighted order statistics as they leave the device (f32) ...
-_QUANT_DEVICE_BYTES = _lib.NQUANTOUT * 8  # ... and as the launch computes them (f64)
-
-
-def _check_quant(quantiles: bool, block, dmax_threshold: float = 0.01) -> bool:
-    """quantiles (the weighted order statistics, a tail of the psis block) goes with with_psis; dmax_threshold, the
-    exceedance threshold, is finite and in [0, 1]."""
-    if quantiles and (block is None or block.name != "psis"):
-        raise ValueError("quantiles needs with_psis: the order statistics are of the posterior mdfit_map_psis forms")
-    if quantiles and not 0.0 <= float(dmax_threshold) <= 1.0:
-        raise ValueError("dmax_threshold must be in [0, 1]")
-    return bool(quantiles)
-
-
-JOINT_BYTES = _lib.NJOINTOUT * 4  # one taxon's evidence and psis records as they leave the device (f32 evid | psis)
-_JOINT_DEVICE_BYTES = _lib.NJOINTOUT * 8  # ... and as the fused launch computes them (f64)
-_JOINT_EVID = _lib.NEVIDROW * _lib.NMAPEVID  # the words of the evidence record in the block
+    return _pieces(block, _PART["ppc"])
 
 
 def split_joint(block):
     """(evid[T, 7, NMAPEVID], psis[T, 3, NMAPPSIS]) views of a joint block [T, NJOINTOUT]."""
-    return (block[:, :_JOINT_EVID].reshape(-1, _lib.NEVIDROW, _lib.NMAPEVID),
-            block[:, _JOINT_EVID:].reshape(-1, 3, _lib.NMAPPSIS))
-
-
-def _check_joint(joint: bool, block) -> bool:
-    """joint (the evidence and psis records of the fused launch, a tail of the waic block) goes with with_waic."""
-    if joint and (block is None or block.name != "waic"):
-        raise ValueError("joint needs with_waic: mdfit_map_joint writes the evidence and the posterior beside the waic "
-                         "record")
-    return bool(joint)
-
-
-def _chunked_block(opts, switches):
-    """blocks.resolve for the chunked dispatch: the run's one block, or None."""
-    block = blocks.resolve(opts, **switches)
-    if block is not None and not block.chunked:
-        raise ValueError(f"{block.switch} is not the chunked dispatch's: fit_auto_chunks runs it")
-    return block
+    return _pieces(block, _PART["joint"])
 
 
 def _check_psis_adapt(psis_adapt: int, importance_sampled: bool) -> int:
     """psis_adapt (MDFIT-ADAPT v1's round cap) is 0 .. ADAPT_MAX_ROUNDS and, when
     not 0, goes with an importance-sampled block (blocks.Block.sampled)."""
-    R = int(psis_adapt)
-    if not 0 <= R <= _lib.ADAPT_MAX_ROUNDS:
-        raise ValueError(f"psis_adapt must be in [0, {_lib.ADAPT_MAX_ROUNDS}]")
-    if R > 0 and not importance_sampled:
-        raise ValueError("psis_adapt needs with_psis, with_waic, with_ppred or the auto inference")
-    return R
+    return blocks.check_rounds(psis_adapt, importance_sampled)
+
+
+def _set_bytes(C: int, opts, run: blocks.Run, with_mm: bool, with_pred: bool, dest_on_device: bool) -> int:
+    """device_bytes for a run already described.  The adapt tail (96 B computed + 8 B out per taxon) is not counted:
+    a known gap that device_bytes and plan_chunks, which take no psis_adapt, have always had."""
+    b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
+    if not dest_on_device:
+        b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
+    for part in run.parts:
+        if part is not blocks.ADAPT:
+            b += C * (part.device_bytes + (0 if dest_on_device else part.out_bytes))
+    return b + workspace_bytes(C, opts)
 
 
 def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = True, with_pred: bool = True,
@@ -1217,29 +971,13 @@ def device_bytes(C: int, opts: _lib.MdfitOpts | None = None, with_mm: bool = Tru
     B -- unless the chunk writes into the caller's device buffers) and the
     call's workspace (mdfit_workspace_bytes: MAP ~48 B below 60k taxa and
     ~4.9 KB from 60k, NUTS 6 x num_samples x 32 B, the draws).  switches (one
-    with_* of blocks.BLOCKS, checked by blocks.resolve): the run's block as the
-    launch computes it and -- unless it goes to the caller's device buffer --
-    as it leaves, rounded to f32.  ppc (with with_ppred): the check's block in
-    the same two forms; quantiles (with with_psis): the weighted order
-    statistics' block in the same two forms; joint (with with_waic): the
-    evidence and psis records of the fused launch in the same two forms."""
-    C = int(C)
-    block = _chunked_block(opts, switches)
-    ppc = _check_ppc(ppc, block)
-    quantiles = _check_quant(quantiles, block, dmax_threshold)
-    joint = _check_joint(joint, block)
-    b = C * (2 * _lib.LD * 4 + (_lib.NPOS * _lib.NMM * 4 if with_mm else 0))
-    if not dest_on_device:
-        b += C * (_lib.NOUT * 8 + (_lib.NPRED * _lib.NPOS * 4 if with_pred else 0) + 4)
-    if block is not None:
-        b += C * (block.device_bytes + (0 if dest_on_device else block.out_bytes))
-    if ppc:
-        b += C * (_PPC_DEVICE_BYTES + (0 if dest_on_device else PPC_BYTES))
-    if quantiles:
-        b += C * (_QUANT_DEVICE_BYTES + (0 if dest_on_device else QUANT_BYTES))
-    if joint:
-        b += C * (_JOINT_DEVICE_BYTES + (0 if dest_on_device else JOINT_BYTES))
-    return b + workspace_bytes(C, opts)
+    with_* of blocks.BLOCKS) and ppc, quantiles, joint (the tails of blocks.TAILS
+    that ride it; blocks.describe checks them): each as its launch computes it
+    and -- unless it goes to the caller's device buffer -- as it leaves, rounded
+    to f32.  (No psis_adapt: the adapt record is not counted)"""
+    run = blocks.describe(opts, {"ppc": ppc, "quantiles": quantiles, "joint": joint}, chunked=True,
+                          dmax_threshold=dmax_threshold, **switches)
+    return _set_bytes(int(C), opts, run, with_mm, with_pred, dest_on_device)
 
 
 def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | None = None, *,
@@ -1247,17 +985,20 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
                 dest_on_device: bool = False, ppc: bool = False, quantiles: bool = False,
                 dmax_threshold: float = 0.01, joint: bool = False, **switches) -> list[tuple[int, int]]:
     """Split T taxa into near-equal contiguous chunks [lo, hi) such that n_sets
-    buffer sets of the largest chunk (device_bytes, with the run's block of
-    switches, ppc, quantiles and joint) fit in budget_bytes (None: no memory bound), no chunk exceeds the
+    buffer sets of the largest chunk (device_bytes, with the run's block and
+    tails) fit in budget_bytes (None: no memory bound), no chunk exceeds the
     per-call limit (2^25 taxa) or chunk_taxa (> 0; env MDFIT_CHUNK_TAXA when 0).
     Taxa are independent and the sampler's streams are keyed by the global taxon
     index (opts.index_base + lo), so any split gives the records of one call bit
     for bit."""
-    T = int(T)
-    block = _chunked_block(opts, switches)
-    _check_ppc(ppc, block)
-    _check_quant(quantiles, block, dmax_threshold)
-    _check_joint(joint, block)
+    run = blocks.describe(opts, {"ppc": ppc, "quantiles": quantiles, "joint": joint}, chunked=True,
+                          dmax_threshold=dmax_threshold, **switches)
+    return _chunks(int(T), opts, run, budget_bytes, chunk_taxa, n_sets, with_mm, with_pred, dest_on_device)
+
+
+def _chunks(T: int, opts, run: blocks.Run, budget_bytes, chunk_taxa: int, n_sets: int, with_mm: bool,
+            with_pred: bool, dest_on_device: bool) -> list[tuple[int, int]]:
+    """plan_chunks for a run already described."""
     if T <= 0:
         return []
     cap = min(T, MAX_CALL_TAXA)
@@ -1267,9 +1008,7 @@ def plan_chunks(T: int, opts: _lib.MdfitOpts | None = None, budget_bytes: int | 
         cap = min(cap, int(chunk_taxa))
     if budget_bytes is not None:
         def per(c):
-            return n_sets * device_bytes(c, opts, with_mm, with_pred, dest_on_device, ppc, quantiles, joint=joint,
-                                         **switches)
-
+            return n_sets * _set_bytes(c, opts, run, with_mm, with_pred, dest_on_device)
 
         if per(1) > budget_bytes:
             raise _lib.MdfitError(f"device budget {budget_bytes} B below one taxon's {per(1)} B")
@@ -1301,9 +1040,7 @@ class _Set:
     """One chunk's device buffers (the workspace is the fitter's: the calls
     run one after another on the compute stream)."""
 
-    def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool,
-                 block: blocks.Block | None = None, with_adapt: bool = False, ppc: bool = False,
-                 quantiles: bool = False, joint: bool = False):
+    def __init__(self, torch, C: int, device, with_pred: bool, with_mm: bool, dest_on_device: bool, parts=()):
         self.d_y = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_N = torch.empty((C, _lib.LD), dtype=torch.int32, device=device)
         self.d_mm = torch.empty((C, _lib.NPOS, _lib.NMM), dtype=torch.int32, device=device) if with_mm else None
@@ -1313,88 +1050,103 @@ class _Set:
             self.pred = (torch.empty((C, _lib.NPRED, _lib.NPOS), dtype=torch.float32, device=device)
                          if with_pred else None)
             self.status = torch.empty((C,), dtype=torch.int32, device=device)
-        # the run's block as its launch writes it, and as one f32 block for the way out
-        self.computed = [torch.empty((C, *shape), dtype=getattr(torch, dtype), device=device)
-                         for shape, dtype in (block.device if block is not None else ())]
-        self.block = None
-        if block is not None and not dest_on_device:
-            self.block = torch.empty((C, *block.shape), dtype=torch.float32, device=device)
-        self.adapt64 = self.adapt = None
-        if with_adapt:  # as the adapt entries write it, and reduced to f32 [C, 2] for the way out
-            self.adapt64 = torch.empty((C, 3, _lib.NMAPADAPT), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.adapt = torch.empty((C, _lib.NADAPTOUT), dtype=torch.float32, device=device)
-        self.ppc_computed = self.ppc = None
-        if ppc:  # as mdfit_map_ppc writes it (f32 ppos, f64 rec), and as one f32 block for the way out
-            self.ppc_computed = (torch.empty((C, _lib.NPOS), dtype=torch.float32, device=device),
-                                 torch.empty((C, _lib.NMAPPPC), dtype=torch.float64, device=device))
-            if not dest_on_device:
-                self.ppc = torch.empty((C, _lib.NPPCOUT), dtype=torch.float32, device=device)
-        self.quant_computed = self.quant = None
-        if quantiles:  # as mdfit_map_quant writes it (f64), and as one f32 block for the way out
-            self.quant_computed = torch.empty((C, 3, _lib.NMAPQUANT), dtype=torch.float64, device=device)
-            if not dest_on_device:
-                self.quant = torch.empty((C, _lib.NQUANTOUT), dtype=torch.float32, device=device)
-        self.joint_computed = self.joint = None
-        if joint:  # as mdfit_map_joint writes them (f64 evid, psis), and as one f32 block for the way out
-            self.joint_computed = (torch.empty((C, _lib.NEVIDROW, _lib.NMAPEVID), dtype=torch.float64, device=device),
-                                   torch.empty((C, 3, _lib.NMAPPSIS), dtype=torch.float64, device=device))
-            if not dest_on_device:
-                self.joint = torch.empty((C, _lib.NJOINTOUT), dtype=torch.float32, device=device)
+        # by attr, the run's block and each tail: as its launch writes it, and as one f32 block for the way out
+        self.computed = {p.attr: [torch.empty((C, *shape), dtype=getattr(torch, dtype), device=device)
+                                  for shape, dtype in p.device] for p in parts}
+        self.f32 = {} if dest_on_device else {
+            p.attr: torch.empty((C, *p.shape), dtype=torch.float32, device=device) for p in parts}
 
 
 H_OUT_COLS = _lib.NRESULT  # record columns the host gets back: the 25 result columns
 
 
-# One launch function per chunked block: the block's *_device call on the first n taxa of buffer set st, whose
-# records res holds, into st.computed on the compute stream comp.  f: the fitter (the draw counts); o: the chunk's
-# options (its index_base is the chunk's global taxon index, which keys the Philox streams beside o.seed); ad_kw:
-# adapt_rounds and adapt of the sampled blocks when psis_adapt > 0 (the launch is then the *_adapt entry).  The MAP
-# blocks read the final records; the NUTS blocks read this chunk's draws in the one workspace, which the stream
-# keeps until the next chunk's fit.
-def _launch_laplace(f, st, n, res, o, comp, ad_kw):
-    map_laplace_device(st.d_y[:n], st.d_N[:n], res, lap=st.computed[0][:n], stream=comp)
+# One launch function per chunked block, and per tail that has a launch of its own: its *_device call on the first n
+# taxa of buffer set st, whose records res holds, into c = st.computed (by attr) on the compute stream comp.  f: the
+# fitter (f.plan: the draw counts, the threshold, the tails); o: the chunk's options (its index_base is the chunk's
+# global taxon index, which keys the Philox streams beside o.seed); ad_kw: adapt_rounds and adapt of the sampled
+# blocks when psis_adapt > 0 (the launch is then the *_adapt entry).  The MAP blocks read the final records; the
+# NUTS blocks read this chunk's draws in the one workspace, which the stream keeps until the next chunk's fit.
+def _launch_laplace(f, st, n, res, o, comp, c, ad_kw):
+    map_laplace_device(st.d_y[:n], st.d_N[:n], res, lap=c["lap"][0][:n], stream=comp)
 
 
-def _launch_diag(f, st, n, res, o, comp, ad_kw):
-    nuts_diag_device(res, n, o, diag=st.computed[0][:n], stream=comp)
+def _launch_diag(f, st, n, res, o, comp, c, ad_kw):
+    nuts_diag_device(res, n, o, diag=c["diag"][0][:n], stream=comp)
 
 
-def _launch_summary(f, st, n, res, o, comp, ad_kw):
-    nuts_summary_device(res, n, o, summ=st.computed[0][:n], stream=comp)
+def _launch_summary(f, st, n, res, o, comp, c, ad_kw):
+    nuts_summary_device(res, n, o, summ=c["summ"][0][:n], stream=comp)
 
 
-def _launch_loo(f, st, n, res, o, comp, ad_kw):
-    nuts_loo_device(st.d_y[:n], st.d_N[:n], res, n, o, loo=st.computed[0][:n], stream=comp)
+def _launch_loo(f, st, n, res, o, comp, c, ad_kw):
+    nuts_loo_device(st.d_y[:n], st.d_N[:n], res, n, o, loo=c["loo"][0][:n], stream=comp)
 
 
-def _launch_psis(f, st, n, res, o, comp, ad_kw):
-    map_psis_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
-                    psis=st.computed[0][:n], stream=comp, **ad_kw)
+def _launch_psis(f, st, n, res, o, comp, c, ad_kw):
+    map_psis_device(st.d_y[:n], st.d_N[:n], res, f.plan.psis_draws, int(o.seed), int(o.index_base),
+                    psis=c["psis"][0][:n], stream=comp, **ad_kw)
 
 
-def _launch_waic(f, st, n, res, o, comp, ad_kw):
-    if f.joint:  # the fused launch: the same waic record, and the evidence and psis records beside it
-        map_joint_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
-                         waic=st.computed[0][:n], evid=st.joint_computed[0][:n], psis=st.joint_computed[1][:n],
-                         stream=comp, **ad_kw)
+def _launch_waic(f, st, n, res, o, comp, c, ad_kw):
+    if "joint" in c:  # the fused launch: the same waic record, and the joint tail's evidence and psis records beside it
+        map_joint_device(st.d_y[:n], st.d_N[:n], res, f.plan.psis_draws, int(o.seed), int(o.index_base),
+                         waic=c["waic"][0][:n], evid=c["joint"][0][:n], psis=c["joint"][1][:n], stream=comp, **ad_kw)
         return
-    map_waic_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
-                    waic=st.computed[0][:n], stream=comp, **ad_kw)
+    map_waic_device(st.d_y[:n], st.d_N[:n], res, f.plan.psis_draws, int(o.seed), int(o.index_base),
+                    waic=c["waic"][0][:n], stream=comp, **ad_kw)
 
 
-def _launch_evidence(f, st, n, res, o, comp, ad_kw):
-    map_evidence_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, int(o.seed), int(o.index_base),
-                        evid=st.computed[0][:n], stream=comp, **ad_kw)
+def _launch_evidence(f, st, n, res, o, comp, c, ad_kw):
+    map_evidence_device(st.d_y[:n], st.d_N[:n], res, f.plan.psis_draws, int(o.seed), int(o.index_base),
+                        evid=c["evid"][0][:n], stream=comp, **ad_kw)
 
 
-def _launch_ppred(f, st, n, res, o, comp, ad_kw):
-    map_pred_device(st.d_y[:n], st.d_N[:n], res, f.psis_draws, f.pred_draws, int(o.seed), int(o.index_base),
-                    ppred=st.computed[0][:n], rec=st.computed[1][:n], stream=comp, **ad_kw)
+def _launch_ppred(f, st, n, res, o, comp, c, ad_kw):
+    map_pred_device(st.d_y[:n], st.d_N[:n], res, f.plan.psis_draws, f.plan.pred_draws, int(o.seed), int(o.index_base),
+                    ppred=c["ppred"][0][:n], rec=c["ppred"][1][:n], stream=comp, **ad_kw)
+
+
+# The two tails with a launch of their own follow their block's on the same stream with the same draws and rounds;
+# the block's launch has written the rounds' record, so theirs runs without it (adapt=False).  The joint tail has no
+# launch (_launch_waic writes it) and neither has adapt (the block's launch writes it).
+def _launch_ppc(f, st, n, res, o, comp, c, ad_kw):
+    map_ppc_device(st.d_y[:n], st.d_N[:n], res, f.plan.psis_draws, f.plan.pred_draws, int(o.seed), int(o.index_base),
+                   ppos=c["ppc"][0][:n], rec=c["ppc"][1][:n], stream=comp,
+                   **(dict(ad_kw, adapt=False) if ad_kw else {}))
+
+
+def _launch_quant(f, st, n, res, o, comp, c, ad_kw):
+    map_quant_device(st.d_y[:n], st.d_N[:n], res, f.plan.psis_draws, int(o.seed), int(o.index_base),
+                     f.plan.dmax_threshold, quant=c["quant"][0][:n], stream=comp,
+                     **(dict(ad_kw, adapt=False) if ad_kw else {}))
 
 
 _LAUNCH = {"laplace": _launch_laplace, "diag": _launch_diag, "summary": _launch_summary, "loo": _launch_loo,
-           "psis": _launch_psis, "waic": _launch_waic, "evidence": _launch_evidence, "ppred": _launch_ppred}
+           "psis": _launch_psis, "waic": _launch_waic, "evidence": _launch_evidence, "ppred": _launch_ppred,
+           "ppc": _launch_ppc, "quant": _launch_quant}
+
+
+# How a part's computed pieces become its f32 block on the way out (on the compute stream): one rounding copy per
+# piece into the piece's word range, but for two.
+def _leave(torch, part, computed, block32, res):
+    for view, piece in zip(_pieces(block32, part), computed):
+        view.copy_(piece)
+
+
+def _leave_diag(torch, part, computed, block32, res):
+    """... and the flags also carry the chain's divergence count (the record's slot 7, not among the columns that
+    leave the device): valid + 2 * divergences."""
+    _leave(torch, part, computed, block32, res)
+    div = torch.nan_to_num(res.out[:, _lib.F_DIAG + 7::_lib.DIAG_STRIDE], nan=0.0)
+    block32[:, :, _lib.NNUTSDIAG - 1] += (2.0 * div).to(torch.float32)
+
+
+def _leave_adapt(torch, part, computed, block32, res):
+    """The adapt record leaves reduced to its two columns."""
+    adapt_summary(computed[0], out=block32)
+
+
+_LEAVE = {"diag": _leave_diag, "adapt": _leave_adapt}
 
 
 class ChunkedFitter:
@@ -1428,57 +1180,36 @@ class ChunkedFitter:
     attribute of the block).  The sampled blocks take psis_draws draws per
     sub-fit (ppred also pred_draws predictive draws per job).
 
-    psis_adapt = R > 0 (a sampled block): the chunk's launch runs at most R
-    moment-matched proposal rounds per PMD row (MDFIT-ADAPT v1), and one more
-    f32 block [T, 2] = (largest round-0 khat over the PMD rows, largest best
-    round), reduced on the device (adapt_summary), leaves behind the block
-    (run's fifth array; dest.adapt).
-
-    ppc (with with_ppred): mdfit_map_ppc (mdfit_map_ppc_adapt with the same
-    rounds when psis_adapt > 0) follows the chunk's map_pred launch on the
-    compute stream -- no further stream --, and one more f32 block [T, NPPCOUT]
-    = ppos | rec (split_ppc), rounded on the device, leaves behind the block and
-    before adapt (run; dest.ppc).
-
-    quantiles (with with_psis): mdfit_map_quant (mdfit_map_quant_adapt with the
-    same rounds when psis_adapt > 0) follows the chunk's map_psis launch on the
-    compute stream with the same draws, seed and index_base and the exceedance
-    threshold dmax_threshold, and one more f32 block [T, NQUANTOUT] = the three
-    rows of _lib.MAPQUANT_FIELDS, rounded on the device, leaves behind the block
-    and before adapt (run; dest.quant).
-
-    joint (with with_waic): the chunk's map_waic launch is replaced by the one
-    launch of mdfit_map_joint (mdfit_map_joint_adapt when psis_adapt > 0), which
-    writes the same waic record and, from the same weights, the records of
-    mdfit_map_evidence and mdfit_map_psis; those leave as one more f32 block [T,
-    NJOINTOUT] = evid | psis (split_joint), rounded on the device, behind the
-    waic block and before adapt (run; dest.joint)."""
+    psis_adapt, ppc, quantiles (with dmax_threshold) and joint ask for the tails
+    of blocks.TAILS, which says what each rides, computes and sends out: a tail
+    with a launch of its own (_LAUNCH) follows the block's on the compute stream
+    with the same draws, seed, index_base and rounds -- no further stream --,
+    and every tail leaves behind the block as one more f32 block, rounded on
+    the device, in TAILS' order (run's further arrays; dest's attribute of the
+    tail's name).  psis_adapt = R > 0: the sampled block's launch runs at most R
+    moment-matched proposal rounds per PMD row (MDFIT-ADAPT v1) and the adapt
+    tail is their record reduced on the device (adapt_summary)."""
 
     def __init__(self, chunk_cap: int, device="cuda", opts: _lib.MdfitOpts | None = None, with_pred: bool = True,
                  with_mm: bool = True, dest_on_device: bool = False, psis_draws: int = PSIS_DRAWS,
                  pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False,
                  dmax_threshold: float = 0.01, joint: bool = False, **switches):
-        self.block = _chunked_block(opts, switches)
-        self.ppc = _check_ppc(ppc, self.block)
-        self.quantiles = _check_quant(quantiles, self.block, dmax_threshold)
-        self.dmax_threshold = float(dmax_threshold)
-        self.joint = _check_joint(joint, self.block)
+        tails = {"psis_adapt": psis_adapt, "ppc": ppc, "quantiles": quantiles, "joint": joint}
+        self.plan = plan = blocks.describe(opts, tails, chunked=True, psis_draws=psis_draws, pred_draws=pred_draws,
+                                           dmax_threshold=dmax_threshold, **switches)
         torch = _torch()
-        self.psis_adapt = _check_psis_adapt(psis_adapt, self.block is not None and self.block.sampled)
-        self.pred_draws = int(pred_draws)
-        self.psis_draws = int(psis_draws)
+        self.block, self.parts, self.psis_adapt = plan.block, plan.parts, plan.rounds
         self.chunk_cap = int(chunk_cap)
         self.device = torch.device(device)
         self.with_pred, self.with_mm, self.dest_on_device = with_pred, with_mm, dest_on_device
-        self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.block,
-                          self.psis_adapt > 0, self.ppc, self.quantiles, self.joint)
+        self.sets = [_Set(torch, self.chunk_cap, self.device, with_pred, with_mm, dest_on_device, self.parts)
                      for _ in range(N_SETS)]
         self.ws = alloc_workspace(self.chunk_cap, self.device, opts)
         self.copy = torch.cuda.Stream(device=self.device)
         self.full_cap = False  # (staging: the chunk capacity is the device budget's, not the batch's)
         self.capacity = 0  # pinned host buffers (input staging for pageable sources, outputs)
         self.h_y = self.h_N = self.h_mm = self.h_out = self.h_pred = self.h_status = None
-        self.h_block = self.h_adapt = self.h_ppc = self.h_quant = self.h_joint = None
+        self.h_parts = {}  # by attr: the block's and each tail's f32 array on the way out
         self._end = None  # the previous run's last event (its transfers use the pinned buffers)
 
     def _host(self, T: int):
@@ -1494,16 +1225,8 @@ class ChunkedFitter:
             self.h_pred = (torch.empty((cap, _lib.NPRED, _lib.NPOS), dtype=torch.float32).pin_memory()
                            if self.with_pred else None)
             self.h_status = torch.empty((cap,), dtype=torch.int32).pin_memory()
-            if self.block is not None:
-                self.h_block = torch.empty((cap, *self.block.shape), dtype=torch.float32).pin_memory()
-            if self.psis_adapt > 0:
-                self.h_adapt = torch.empty((cap, _lib.NADAPTOUT), dtype=torch.float32).pin_memory()
-            if self.ppc:
-                self.h_ppc = torch.empty((cap, _lib.NPPCOUT), dtype=torch.float32).pin_memory()
-            if self.quantiles:
-                self.h_quant = torch.empty((cap, _lib.NQUANTOUT), dtype=torch.float32).pin_memory()
-            if self.joint:
-                self.h_joint = torch.empty((cap, _lib.NJOINTOUT), dtype=torch.float32).pin_memory()
+            self.h_parts = {p.attr: torch.empty((cap, *p.shape), dtype=torch.float32).pin_memory()
+                            for p in self.parts}
         self.capacity = cap
 
     def _sources(self, y, N, mm, pinned):
@@ -1529,20 +1252,12 @@ class ChunkedFitter:
         torch = _torch()
         lib = _lib.load()
         o0 = opts if opts is not None else _lib.default_opts()
-        block = self.block
-        if block is not None:
-            blocks.resolve(o0, **{block.switch: True})  # (this run's options, not only the constructor's)
-            if dest is not None and getattr(dest, block.attr) is None:
-                shape = ", ".join(map(str, block.shape))
-                raise ValueError(f"{block.switch}: dest.{block.attr} (float32 [T, {shape}]) required")
-        if self.psis_adapt > 0 and dest is not None and dest.adapt is None:
-            raise ValueError("psis_adapt: dest.adapt (float32 [T, NADAPTOUT]) required")
-        if self.ppc and dest is not None and getattr(dest, "ppc", None) is None:
-            raise ValueError("ppc: dest.ppc (float32 [T, NPPCOUT]) required")
-        if self.quantiles and dest is not None and getattr(dest, "quant", None) is None:
-            raise ValueError("quantiles: dest.quant (float32 [T, NQUANTOUT]) required")
-        if self.joint and dest is not None and getattr(dest, "joint", None) is None:
-            raise ValueError("joint: dest.joint (float32 [T, NJOINTOUT]) required")
+        if self.block is not None:
+            blocks.resolve(o0, **{self.block.switch: True})  # (this run's options, not only the constructor's)
+        for p in self.parts if dest is not None else ():
+            if getattr(dest, p.attr, None) is None:
+                asked = p.switch if p is self.block else p.option
+                raise ValueError(f"{asked}: dest.{p.attr} (float32 [T, {', '.join(map(str, p.shape))}]) required")
         src_y, src_N, src_mm = src
         comp = torch.cuda.current_stream(self.device)
         cp = self.copy
@@ -1582,48 +1297,18 @@ class ChunkedFitter:
             self.ws = res.workspace
             if ev_mm is not None:
                 comp.wait_event(ev_mm)
-                _lib.check(lib.mdfit_noise(ctypes.c_void_p(st.d_y.data_ptr()), ctypes.c_void_p(st.d_N.data_ptr()),
-                                           ctypes.c_void_p(st.d_mm.data_ptr()), n, ctypes.c_void_p(res.out.data_ptr()),
-                                           h_s))
-            block32 = adapt32 = ppc32 = quant32 = joint32 = None
-            if block is not None:  # the records are final: the block's launch, then one f32 block for the way out
-                ad_kw = {"adapt_rounds": self.psis_adapt, "adapt": st.adapt64[:n]} if self.psis_adapt > 0 else {}
-                _LAUNCH[block.name](self, st, n, res, o, comp, ad_kw)
-                block32 = getattr(dest, block.attr)[lo:hi] if dest is not None else st.block[:n]
+                _lib.check(lib.mdfit_noise(_ptr(st.d_y), _ptr(st.d_N), _ptr(st.d_mm), n, _ptr(res.out), h_s))
+            # the records are final: the block, then each tail in the record's order -- its launch where it has one
+            # (the others' pieces are written by now), then its one f32 block for the way out
+            ad_kw = ({"adapt_rounds": self.psis_adapt, "adapt": st.computed["adapt"][0][:n]}
+                     if self.psis_adapt > 0 else {})
+            leaving = {}
+            for p in self.parts:
+                if p.name in _LAUNCH:
+                    _LAUNCH[p.name](self, st, n, res, o, comp, st.computed, ad_kw)
+                block32 = leaving[p.attr] = getattr(dest, p.attr)[lo:hi] if dest is not None else st.f32[p.attr][:n]
                 with torch.cuda.stream(comp):
-                    # (ppred: its two computed pieces into the two views of the block; the others: one rounding copy)
-                    views = split_ppred(block32) if block.name == "ppred" else (block32,)
-                    for view, computed in zip(views, st.computed):
-                        view.copy_(computed[:n])
-                    if block.name == "diag":
-                        # on the way out the flags also carry the chain's divergence count (the record's
-                        # slot 7, not among the columns that leave the device): valid + 2 * divergences
-                        div = torch.nan_to_num(res.out[:, _lib.F_DIAG + 7::_lib.DIAG_STRIDE], nan=0.0)
-                        block32[:, :, _lib.NNUTSDIAG - 1] += (2.0 * div).to(torch.float32)
-            if self.ppc:  # the check of the predictive just formed: the same draws, rounds and stream
-                map_ppc_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, self.pred_draws, int(o.seed),
-                               int(o.index_base), ppos=st.ppc_computed[0][:n], rec=st.ppc_computed[1][:n], stream=comp,
-                               **({"adapt_rounds": self.psis_adapt, "adapt": False} if self.psis_adapt > 0 else {}))
-                ppc32 = dest.ppc[lo:hi] if dest is not None else st.ppc[:n]
-                with torch.cuda.stream(comp):
-                    for view, computed in zip(split_ppc(ppc32), st.ppc_computed):
-                        view.copy_(computed[:n])
-            if self.quantiles:  # the order statistics of the posterior just formed: the same draws, rounds and stream
-                map_quant_device(st.d_y[:n], st.d_N[:n], res, self.psis_draws, int(o.seed), int(o.index_base),
-                                 self.dmax_threshold, quant=st.quant_computed[:n], stream=comp,
-                                 **({"adapt_rounds": self.psis_adapt, "adapt": False} if self.psis_adapt > 0 else {}))
-                quant32 = dest.quant[lo:hi] if dest is not None else st.quant[:n]
-                with torch.cuda.stream(comp):
-                    quant32.copy_(st.quant_computed[:n].reshape(n, _lib.NQUANTOUT))
-            if self.joint:  # the fused launch (_launch_waic) has written them: one f32 block for the way out
-                joint32 = dest.joint[lo:hi] if dest is not None else st.joint[:n]
-                with torch.cuda.stream(comp):
-                    for view, computed in zip(split_joint(joint32), st.joint_computed):
-                        view.copy_(computed[:n])
-            if self.psis_adapt > 0:  # the adapt record, reduced to its two columns in place
-                adapt32 = dest.adapt[lo:hi] if dest is not None else st.adapt[:n]
-                with torch.cuda.stream(comp):
-                    adapt_summary(st.adapt64[:n], out=adapt32)
+                    _LEAVE.get(p.name, _leave)(torch, p, [c[:n] for c in st.computed[p.attr]], block32, res)
             ev_done = torch.cuda.Event()
             ev_done.record(comp)
             done.append(ev_done)
@@ -1634,16 +1319,8 @@ class ChunkedFitter:
                     if res.pred is not None:
                         self.h_pred[lo:hi].copy_(res.pred, non_blocking=True)
                     self.h_status[lo:hi].copy_(res.status, non_blocking=True)
-                    if block32 is not None:
-                        self.h_block[lo:hi].copy_(block32, non_blocking=True)
-                    if ppc32 is not None:
-                        self.h_ppc[lo:hi].copy_(ppc32, non_blocking=True)
-                    if quant32 is not None:
-                        self.h_quant[lo:hi].copy_(quant32, non_blocking=True)
-                    if joint32 is not None:
-                        self.h_joint[lo:hi].copy_(joint32, non_blocking=True)
-                    if adapt32 is not None:
-                        self.h_adapt[lo:hi].copy_(adapt32, non_blocking=True)
+                    for attr, block32 in leaving.items():
+                        self.h_parts[attr][lo:hi].copy_(block32, non_blocking=True)
                 last_d2h = cp
         end = torch.cuda.Event()
         end.record(cp if last_d2h is not None else comp)
@@ -1652,12 +1329,11 @@ class ChunkedFitter:
 
     def run(self, y, N, mm=None, opts: _lib.MdfitOpts | None = None, sync: bool = True,
             pinned: PinnedPack | None = None, chunks=None):
-        """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status[, the
-        run's block f32 [T, *shape]][, ppc f32 [T, NPPCOUT]][, quant f32 [T, NQUANTOUT]][, joint f32 [T, NJOINTOUT]][, adapt f32 [T, 2]]) of the
-        pinned buffers
-        (valid until the next run).  pinned: y, N, mm are that PinnedPack's
-        views.  chunks: the split (default plan_chunks at this staging's
-        chunk_cap)."""
+        """Fit len(y) taxa; returns numpy views (out[:, :25], pred, status, then
+        the run's block and tails, f32 [T, *shape] each, in blocks.Run.parts'
+        order) of the pinned buffers (valid until the next run).  pinned: y, N,
+        mm are that PinnedPack's views.  chunks: the split (default plan_chunks
+        at this staging's chunk_cap)."""
         T = int(y.shape[0])
         if chunks is None:
             chunks = plan_chunks(T, opts, chunk_taxa=self.chunk_cap)
@@ -1667,25 +1343,14 @@ class ChunkedFitter:
         end = self._launch(chunks, self._sources(y, N, mm, pinned), opts)
         if sync:
             end.synchronize()
-        got = (self.h_out[:T].numpy(), self.h_pred[:T].numpy() if self.h_pred is not None else None,
-               self.h_status[:T].numpy())
-        if self.block is not None:
-            got += (self.h_block[:T].numpy(),)
-        if self.ppc:
-            got += (self.h_ppc[:T].numpy(),)
-        if self.quantiles:
-            got += (self.h_quant[:T].numpy(),)
-        if self.joint:
-            got += (self.h_joint[:T].numpy(),)
-        if self.psis_adapt > 0:
-            got += (self.h_adapt[:T].numpy(),)
-        return got
+        return (self.h_out[:T].numpy(), self.h_pred[:T].numpy() if self.h_pred is not None else None,
+                self.h_status[:T].numpy(), *(self.h_parts[p.attr][:T].numpy() for p in self.parts))
 
     def run_into_device(self, y, N, mm, opts, dest: FitBatch, chunks=None):
         """Fit len(y) taxa chunk by chunk into the caller's device tensors dest
-        (out[T, NOUT], pred, status -- and the run's block under its attribute,
-        ppc with ppc, quant with quantiles, joint with joint, adapt when psis_adapt > 0: rows written in place), ordered on the
-        caller's current stream."""
+        (out[T, NOUT], pred, status -- and the run's block and tails under their
+        attributes: rows written in place), ordered on the caller's current
+        stream."""
         T = int(y.shape[0])
         if chunks is None:
             chunks = plan_chunks(T, opts, chunk_taxa=self.chunk_cap)
@@ -1755,9 +1420,9 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
             pred_draws: int = PRED_DRAWS, psis_adapt: int = 0, ppc: bool = False, quantiles: bool = False,
             dmax_threshold: float = 0.01, joint: bool = False, **switches) -> ChunkedFitter:
     """The ChunkedFitter for batches of n_taxa on this device, reused across calls
-    of this process (per device, buffer kind, sampler length and the run's block
-    of switches with the draw counts it uses, psis_adapt, ppc, quantiles
-    with its threshold and joint): the
+    of this process (per device, buffer kind, sampler length and the run's
+    blocks.Run.key: its block of switches with the draw counts it uses, its
+    rounds, its tails and their threshold): the
     multi-file pipeline fits one file after another, and pinned + device
     buffers allocated per file cost more host time than the fit.  Its chunk
     capacity is the largest chunk N_SETS buffer sets of which fit the device
@@ -1771,14 +1436,10 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
         dev = torch.device(dev.type, torch.cuda.current_device())
     o = opts if opts is not None else _lib.default_opts()
     env_chunk = int(os.environ.get("MDFIT_CHUNK_TAXA", "0") or 0)
-    block = _chunked_block(o, switches)
-    key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk,
-           block.name if block is not None else None,
-           int(psis_draws) if block is not None and block.sampled else 0,
-           int(pred_draws) if block is not None and block.name == "ppred" else 0, int(psis_adapt),
-           _check_ppc(ppc, block),
-           float(dmax_threshold) if _check_quant(quantiles, block, dmax_threshold) else None,
-           _check_joint(joint, block))
+    tails = {"psis_adapt": psis_adapt, "ppc": ppc, "quantiles": quantiles, "joint": joint}
+    plan = blocks.describe(o, tails, chunked=True, psis_draws=psis_draws, pred_draws=pred_draws,
+                           dmax_threshold=dmax_threshold, **switches)
+    key = (str(dev), bool(with_mm), bool(dest_on_device), int(o.mode), int(o.num_samples), env_chunk, plan.key)
     st = _STAGING.get(key)
     T = max(1, int(n_taxa))
     if st is not None and (st.chunk_cap >= T or st.full_cap):
@@ -1794,12 +1455,10 @@ def staging(n_taxa: int, device="cuda", opts: _lib.MdfitOpts | None = None, with
     # per taxon that batches below 60k never touch)
     if T < _lib.STREAM_MAX_TAXA:
         want = min(want, _lib.STREAM_MAX_TAXA - 1)
-    cap = plan_chunks(want, o, budget, chunk_taxa=env_chunk, with_mm=with_mm, dest_on_device=dest_on_device,
-                      ppc=ppc, quantiles=quantiles, dmax_threshold=dmax_threshold, joint=joint, **switches)[0]
+    cap = _chunks(want, o, plan, budget, env_chunk, N_SETS, with_mm, True, dest_on_device)[0]
     cap = cap[1] - cap[0]
-    st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device,
-                       psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
-                       quantiles=quantiles, dmax_threshold=dmax_threshold, joint=joint, **switches)
+    st = ChunkedFitter(cap, device=dev, opts=o, with_mm=with_mm, dest_on_device=dest_on_device, **plan.options,
+                       **switches)
     # (chunk capacity below the batch: memory-bound, no regrow for larger batches)
     st.full_cap = cap < want
     _STAGING[key] = st
@@ -1812,14 +1471,10 @@ def fit_batch_host(y, N, mm=None, opts: _lib.MdfitOpts | None = None, noise=None
                    joint: bool = False, **named):
     """The product's host-to-host fit: (out[T, 25], pred, status) -- and, with
     named (one chunked block of blocks.BLOCKS by its name, e.g. laplace=True), a
-    fourth array, the block's f32 [T, *shape] --, chunked through the device
-    budget (ChunkedFitter, which documents psis_draws, pred_draws and
-    psis_adapt; psis_adapt > 0 returns a fifth array adapt[T, 2] f32,
-    _lib.ADAPTOUT_FIELDS; ppc, with ppred=True, the check's f32 [T, NPPCOUT]
-    behind the block and before adapt; quantiles, with psis=True, the weighted
-    order statistics' f32 [T, NQUANTOUT] in the same place, P(D_max >
-    dmax_threshold) among them; joint, with waic=True, the fused launch's f32
-    [T, NJOINTOUT] = evid | psis in the same place).  mm goes to the device (the assembly computes the
+    fourth array, the block's f32 [T, *shape], and behind it the f32 array of
+    each tail asked for (blocks.TAILS, in its order; ChunkedFitter documents
+    the options) --, chunked through the device budget.  mm goes to the device
+    (the assembly computes the
     noise columns); without it, `noise` (float64[T][3], ingest.noise) fills them
     when given.  pinned: y, N, mm are views of that PinnedPack (copied to the
     device from there)."""

@@ -410,31 +410,20 @@ def fit_packed(p: Packed, opts=None, shard: bool = True, psis_draws: int = 256, 
     # statistics (ingest.noise) take ~1.5 ms of CPU per 10k taxa on the 16-thread
     # share of a multi-file pipeline that is host-bound
     # (the block's mode is checked against opts where the fit is planned: engine.staging)
-    block = blocks.select(**{"with_" + name: on for name, on in named.items()})
-    auto = block is not None and not block.chunked
-    psis_adapt = engine._check_psis_adapt(psis_adapt, block is not None and block.sampled)
-    if auto_pred and not auto:
-        raise ValueError("auto_pred goes with the auto inference")
-    ppc = engine._check_ppc(ppc, block)
-    quantiles = engine._check_quant(quantiles, block, dmax_threshold)
-    joint = engine._check_joint(joint, block)
+    tails = {"psis_adapt": psis_adapt, "auto_pred": auto_pred, "ppc": ppc, "quantiles": quantiles, "joint": joint}
+    run = blocks.describe(None, tails, check_mode=False, psis_draws=psis_draws, pred_draws=pred_draws,
+                          dmax_threshold=dmax_threshold, **{"with_" + name: on for name, on in named.items()})
     try:
         if grouped:
-            return _fit_sharded(p, opts, dev, rank, world, block, psis_draws, pred_draws, psis_adapt, auto_pred, ppc,
-                                quantiles, dmax_threshold, joint)
-        if auto:
-            return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, psis_draws, device=dev, psis_adapt=psis_adapt,
-                                          auto_pred=auto_pred, pred_draws=pred_draws)
-        return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, psis_draws=psis_draws,
-                                     pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc, quantiles=quantiles,
-                                     dmax_threshold=dmax_threshold, joint=joint, **named)
+            return _fit_sharded(p, opts, dev, rank, world, run)
+        if run.block is not None and not run.block.chunked:
+            return engine.fit_auto_chunks(p.y, p.N, p.mm, opts, device=dev, **run.options)
+        return engine.fit_batch_host(p.y, p.N, p.mm, opts, pinned=p.pinned, **run.options, **named)
     finally:
         p.release_pinned()  # (the call synchronised, or raised: the pinned set goes back either way)
 
 
-def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Block | None = None,
-                 psis_draws: int = 256, pred_draws: int = 1000, psis_adapt: int = 0, auto_pred: bool = False,
-                 ppc: bool = False, quantiles: bool = False, dmax_threshold: float = 0.01, joint: bool = False):
+def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, run: blocks.Run):
     import torch
 
     from . import engine
@@ -445,30 +434,20 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
         opts = _lib.MdfitOpts.from_buffer_copy(opts)
         opts.index_base = opts.index_base + lo
     cap = shard_capacity(p.n_taxa, world)
-    switch = {block.switch: True} if block is not None else {}
-    ppred = block is not None and block.name == "ppred"  # (its adapt tail has a switch of its own)
-    layout = dict(switch, with_adapt=psis_adapt > 0 and not ppred, with_ppred_adapt=psis_adapt > 0 and ppred,
-                  with_auto_pred=auto_pred, with_ppc=ppc, with_quant=quantiles, with_joint=joint)
-    rec = alloc_records(cap, dev, **layout)
+    block = run.block
+    rec = alloc_records(cap, dev, **run.layout)
     # the rows are written in place into the gather buffers
     dest = engine.FitBatch(rec.out[: hi - lo], rec.pred[: hi - lo], rec.status[: hi - lo],
-                           adapt=rec.adapt[: hi - lo] if psis_adapt > 0 else None,
-                           auto_pred=rec.auto_pred[: hi - lo] if auto_pred else None,
-                           ppc=rec.ppc[: hi - lo] if ppc else None,
-                           quant=rec.quant[: hi - lo] if quantiles else None,
-                           joint=rec.joint[: hi - lo] if joint else None,
-                           **({block.attr: getattr(rec, block.attr)[: hi - lo]} if block is not None else {}))
+                           **{part.attr: getattr(rec, part.attr)[: hi - lo] for part in run.parts})
+    mm = p.mm[lo:hi] if p.mm is not None else None
     if hi > lo and block is not None and not block.chunked:  # each rank runs auto on its shard
-        engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, psis_draws,
-                               device=dev, dest=dest, psis_adapt=psis_adapt, auto_pred=auto_pred,
-                               pred_draws=pred_draws)
+        engine.fit_auto_chunks(p.y[lo:hi], p.N[lo:hi], mm, opts, device=dev, dest=dest, **run.options)
         torch.cuda.synchronize(dev)
     elif hi > lo:  # the shard through the bounded-memory chunked dispatch
         with engine._STAGING_LOCK:
-            st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=p.mm is not None, dest_on_device=True,
-                                psis_draws=psis_draws, pred_draws=pred_draws, psis_adapt=psis_adapt, ppc=ppc,
-                                quantiles=quantiles, dmax_threshold=dmax_threshold, joint=joint, **switch)
-            st.run_into_device(p.y[lo:hi], p.N[lo:hi], p.mm[lo:hi] if p.mm is not None else None, opts, dest)
+            st = engine.staging(hi - lo, device=dev, opts=opts, with_mm=mm is not None, dest_on_device=True,
+                                **run.options, **({block.switch: True} if block is not None else {}))
+            st.run_into_device(p.y[lo:hi], p.N[lo:hi], mm, opts, dest)
             torch.cuda.synchronize(dev)  # (the chunks' pinned input staging is reused by the next call)
     p.release_pinned()
     buf = rec.stage()
@@ -476,7 +455,7 @@ def _fit_sharded(p: Packed, opts, dev, rank: int, world: int, block: blocks.Bloc
     parts = gather_records(buf, cap, rank, world)
     if rank != 0:
         return None
-    return unpack_gathered(parts, p.n_taxa, world, **layout)
+    return unpack_gathered(parts, p.n_taxa, world, **run.layout)
 
 
 # --------------------------------------------------------------------------
@@ -904,26 +883,17 @@ def _fit_for_frames(p: Packed, cfg, opts, shard: bool):
     about), kw the optional arrays under make_df_fit_results' keywords."""
     inference = getattr(cfg, "inference", "nuts")
     block = next((b for b in blocks.BLOCKS if b.inference == inference), None)
-    res = fit_packed(p, opts, shard=shard, psis_draws=psis_draws_of(cfg), pred_draws=pred_draws_of(cfg),
-                     psis_adapt=psis_adapt_of(cfg), auto_pred=auto_pred_of(cfg), ppc=ppc_of(cfg),
-                     quantiles=quantiles_of(cfg), dmax_threshold=dmax_threshold_of(cfg), joint=joint_of(cfg),
-                     **({block.name: True} if block is not None else {}))
+    # every tail's option has its reader above, <option>_of(cfg)
+    tails = {t.option: globals()[t.option + "_of"](cfg) for t in blocks.TAILS}
+    draws = dict(psis_draws=psis_draws_of(cfg), pred_draws=pred_draws_of(cfg), dmax_threshold=dmax_threshold_of(cfg))
+    res = fit_packed(p, opts, shard=shard, **draws, **tails, **({block.name: True} if block is not None else {}))
     if res is None:
         return None
     out, pred, status, *rest = res
-    ppc = rest.pop(1) if ppc_of(cfg) else None  # (directly behind the ppred block)
-    quant = rest.pop(1) if quantiles_of(cfg) else None  # (directly behind the psis block)
-    joint = rest.pop(1) if joint_of(cfg) else None  # (directly behind the waic block)
-    extra, auto_pred, adapt = _split_rest(cfg, rest)
-    kw = {"adapt": adapt, "auto_pred": auto_pred}
-    if ppc is not None:
-        kw["ppc"] = ppc
-    if quant is not None:
-        kw["quant"] = quant
-    if joint is not None:
-        kw["joint"] = joint
-    if block is not None:
-        kw[block.attr] = extra
+    # the arrays behind (out, pred, status) are the run's block and tails in the record's order
+    run = blocks.describe(None, tails, check_mode=False, **draws,
+                          **({block.switch: True} if block is not None else {}))
+    kw = {part.attr: a for part, a in zip(run.parts, rest, strict=True)}
     keep = status == _lib.OK
     for t in np.where(~keep)[0]:
         logger.warning(f"Fit: tax_id {p.tax_id[t]} failed (status {int(status[t])}). Skipping.")

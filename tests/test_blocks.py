@@ -5,6 +5,7 @@ plan's bytes, the gather record's layout, the one-block and mode rules."""
 from __future__ import annotations
 
 import itertools
+import re
 
 import numpy as np
 import pytest
@@ -30,6 +31,34 @@ SAMPLED = {"psis", "waic", "evidence", "ppred", "auto"}
 SWITCHES = [row[0] for row in ROWS.values()]
 CHUNKED = [name for name, row in ROWS.items() if row[5] is not None]
 BASE = 496  # the gather record without a block
+# the tails, in the gather record's order.  name: (option, switch, the blocks it rides, f32 shape out per taxon, bytes
+# out, device bytes as computed; None: not chunked)
+TAIL_ROWS = {
+    "ppc": ("ppc", "with_ppc", ("ppred",), (42,), 168, 30 * 4 + 12 * 8),
+    "quant": ("quantiles", "with_quant", ("psis",), (48,), 192, 384),
+    "joint": ("joint", "with_joint", ("waic",), (104,), 416, 832),
+    "auto_pred": ("auto_pred", "with_auto_pred", ("auto",), (2,), 8, None),
+    "adapt": ("psis_adapt", "with_adapt", ("psis", "waic", "evidence", "ppred", "auto"), (2,), 8, 96),
+}
+PPRED_ADAPT = "with_ppred_adapt"  # the ppred block's adapt tail keeps a switch of its own
+PLANNED = ("ppc", "quant", "joint")  # the tails device_bytes and plan_chunks take (no psis_adapt: adapt is not counted)
+# the refusals of a tail without a block it rides: by its option (engine), by its switch (distributed)
+REFUSAL = {
+    "ppc": ("ppc needs with_ppred: the check is of the predictive that mdfit_map_pred forms",
+            "with_ppc goes with with_ppred"),
+    "quant": ("quantiles needs with_psis: the order statistics are of the posterior mdfit_map_psis forms",
+              "with_quant goes with with_psis"),
+    "joint": ("joint needs with_waic: mdfit_map_joint writes the evidence and the posterior beside the waic record",
+              "with_joint goes with with_waic"),
+    "auto_pred": ("auto_pred goes with the auto inference", "with_auto_pred goes with with_auto"),
+    "adapt": ("psis_adapt needs with_psis, with_waic, with_ppred or the auto inference",
+              "with_adapt goes with with_psis, with_waic or with_auto"),
+}
+RIDES = [(tail, block) for tail, row in TAIL_ROWS.items() for block in row[2]]
+
+
+def _tail_switch(tail, block):
+    return PPRED_ADAPT if (tail, block) == ("adapt", "ppred") else TAIL_ROWS[tail][1]
 
 
 def _opts(mode):
@@ -215,3 +244,108 @@ def test_tail_blocks_follow_the_block():
     for a, view in zip(got[3:], (rec.auto, rec.auto_pred, rec.adapt)):
         want = np.concatenate([view.numpy(), view.numpy()[:6]])
         assert np.array_equal(a.view(np.int32), want.view(np.int32))
+
+
+@pytest.mark.parametrize("name", list(TAIL_ROWS))
+def test_tail_table_pins(name):
+    import inspect
+
+    from metadamage_amd import blocks, distributed as d, engine, fits
+
+    assert [t.name for t in blocks.TAILS] == list(TAIL_ROWS)  # the gather record's order
+    option, switch, rides, shape, nbytes, dev = TAIL_ROWS[name]
+    (t,) = [t for t in blocks.TAILS if t.name == name]
+    assert (t.option, t.switch, tuple(t.rides), tuple(t.shape), t.out_bytes) == (option, switch, rides, shape, nbytes)
+    assert (t.refusal, t.switch_refusal) == REFUSAL[name]
+    assert int(np.prod(shape)) * 4 == nbytes == getattr(d, "REC_" + name.upper())
+    assert t.device_bytes == (dev or 0) and (dev is None) == (t.device == ())
+    assert dict(t.block_switches) == ({"ppred": PPRED_ADAPT} if name == "adapt" else {})
+    assert name in engine.FitBatch.__dataclass_fields__
+    assert name in inspect.signature(fits.make_df_fit_results).parameters
+    assert option in inspect.signature(fits.fit_packed).parameters
+    for f in (engine.device_bytes, engine.plan_chunks):  # (which take no psis_adapt: the adapt record is not counted)
+        assert (option in inspect.signature(f).parameters) == (name in PLANNED)
+    with pytest.raises(Exception):  # frozen
+        t.name = "x"
+
+
+@pytest.mark.parametrize("tail, block", [(t, b) for t, b in RIDES if t in PLANNED])
+def test_tail_bytes_in_the_chunk_plan(tail, block):
+    from metadamage_amd import engine
+
+    option, _, _, _, nbytes, dev = TAIL_ROWS[tail]
+    switch, mode = ROWS[block][:2]
+    o = _opts(mode)
+    kw = {switch: True}
+    assert (engine.device_bytes(1000, o, **kw, **{option: True}) - engine.device_bytes(1000, o, **kw)
+            == 1000 * (dev + nbytes))
+    assert (engine.device_bytes(1000, o, dest_on_device=True, **kw, **{option: True})
+            - engine.device_bytes(1000, o, dest_on_device=True, **kw)) == 1000 * dev
+    assert engine.device_bytes(1000, o, **kw, **{option: False}) == engine.device_bytes(1000, o, **kw)
+
+
+@pytest.mark.filterwarnings("ignore:invalid value encountered in cast")  # (random bytes hold signalling NaNs)
+@pytest.mark.parametrize("block, tails", [("auto", ("auto_pred", "adapt")), ("ppred", ("ppc", "adapt")),
+                                          ("psis", ("quant", "adapt")), ("waic", ("joint", "adapt"))]
+                         + [(b, (t,)) for t, b in RIDES])
+def test_tails_lie_and_come_back_in_the_records_order(block, tails):
+    from metadamage_amd import distributed as d
+
+    n = 7
+    switch, _, attr, shape, nbytes, _ = ROWS[block]
+    kw = dict({switch: True}, **{_tail_switch(t, block): True for t in tails})
+    rec = d.alloc_records(n, "cpu", **kw)
+    offset = BASE + nbytes
+    assert getattr(rec, attr).data_ptr() == rec.buf.data_ptr() + n * BASE
+    where = [(BASE, shape)]  # (byte offset per taxon, shape) of the block and of each tail, in the record's order
+    for t in TAIL_ROWS:
+        view = getattr(rec, t)
+        assert (view is None) == (t not in tails), t
+        if view is not None:
+            assert tuple(view.shape) == (n, *TAIL_ROWS[t][3]) and view.is_contiguous()
+            assert view.data_ptr() == rec.buf.data_ptr() + n * offset, t
+            where.append((offset, TAIL_ROWS[t][3]))
+            offset += TAIL_ROWS[t][4]
+    assert rec.buf.numel() == n * offset
+    # 13 taxa over two parts of capacity 7, random bytes: the arrays come back in that order, bit for bit
+    parts = [_random_bytes(n * offset, seed=r) for r in (1, 2)]
+    got = d.unpack_gathered(parts, 13, 2, **kw)
+    assert len(got) == 3 + len(where)
+    for a, (lo, shp) in zip(got[3:], where):
+        words = int(np.prod(shp))
+        pieces = [p.numpy()[n * lo: n * lo + 4 * n * words].view(np.int32).reshape(n, *shp) for p in parts]
+        want = np.concatenate([pieces[0], pieces[1][:6]])
+        assert a.dtype == np.float32 and a.shape == want.shape and np.array_equal(a.view(np.int32), want), (lo, shp)
+
+
+@pytest.mark.parametrize("tail", list(TAIL_ROWS))
+def test_a_tail_without_a_block_it_rides_is_refused_everywhere(tail):
+    from metadamage_amd import distributed as d, engine
+
+    option, switch, rides, _, _, _ = TAIL_ROWS[tail]
+    by_option, by_switch = REFUSAL[tail]
+    buf = _random_bytes(4 * 2000)
+    for block in (None, *ROWS):
+        if block in rides:
+            continue
+        kw = {ROWS[block][0]: True} if block is not None else {}
+        if tail in PLANNED and block != "auto":  # (auto: the chunk plan refuses the block itself)
+            o = _opts(ROWS[block][1]) if block is not None else None
+            for f in (engine.device_bytes, engine.plan_chunks):
+                with pytest.raises(ValueError, match=re.escape(by_option)):
+                    f(10, o, **kw, **{option: True})
+        for call in (lambda: d.alloc_records(4, "cpu", **kw, **{switch: True}),
+                     lambda: d.unpack_gathered([buf], 4, 1, **kw, **{switch: True})):
+            with pytest.raises(ValueError, match=re.escape(by_switch)):
+                call()
+    # the ppred block asks for its adapt tail by a switch of its own, which goes with no other block
+    if tail == "adapt":
+        for call in (lambda: d.alloc_records(4, "cpu", with_ppred=True, with_adapt=True),
+                     lambda: d.unpack_gathered([buf], 4, 1, with_ppred=True, with_adapt=True)):
+            with pytest.raises(ValueError, match=re.escape(by_switch)):
+                call()
+        for block in (None, *ROWS):
+            if block != "ppred":
+                kw = {ROWS[block][0]: True} if block is not None else {}
+                with pytest.raises(ValueError, match="with_ppred_adapt goes with with_ppred"):
+                    d.unpack_gathered([buf], 4, 1, with_ppred_adapt=True, **kw)

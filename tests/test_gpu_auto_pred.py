@@ -207,8 +207,9 @@ def test_two_chunks_equal_one_and_the_gather_carries_the_block(torch_dev, batch3
     monkeypatch.delenv("MDFIT_CHUNK_TAXA", raising=False)
     assert not (dist.is_available() and dist.is_initialized())
     dev = torch_dev.device("cuda", torch_dev.cuda.current_device())
-    got = fits._fit_sharded(_packed(h), _opts3(), dev, 0, 1, blocks.select(with_auto=True), psis_draws=S3,
-                            pred_draws=RPRED3, psis_adapt=ADAPT3, auto_pred=True)
+    run = blocks.describe(_opts3(), {"psis_adapt": ADAPT3, "auto_pred": True}, with_auto=True, psis_draws=S3,
+                          pred_draws=RPRED3)
+    got = fits._fit_sharded(_packed(h), _opts3(), dev, 0, 1, run)
     assert len(got) == 6
     assert np.array_equal(got[0], d.round_like_gather(out), equal_nan=True)
     for a, b in zip(got[1:], one[1:]):

@@ -208,8 +208,9 @@ def test_fit_packed_puts_the_columns_in_the_frame(torch_dev, batch, tmp_path):
     from metadamage_amd import blocks
 
     dev = torch_dev.device("cuda", torch_dev.cuda.current_device())
-    waic_block = next(bl for bl in blocks.BLOCKS if bl.name == "waic")
-    sh = fits._fit_sharded(packed(), opts, dev, 0, 1, waic_block, S, 1000, 0, False, False, False, 0.01, True)
+    run = blocks.describe(opts, {"psis_adapt": 0, "joint": True}, with_waic=True, psis_draws=S, pred_draws=1000,
+                          dmax_threshold=0.01)
+    sh = fits._fit_sharded(packed(), opts, dev, 0, 1, run)
     assert len(sh) == 5 and np.array_equal(_bits(sh[4]), _bits(joint)) and np.array_equal(_bits(sh[3]), _bits(waic))
 
 

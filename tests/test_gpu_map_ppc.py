@@ -356,8 +356,8 @@ def test_record_does_not_depend_on_the_call(torch_dev, monkeypatch, batch_a):
     # the sharded branch as rank 0 of a world of one: the gather record carries the check before the adapt tail
     from metadamage_amd import blocks
 
-    ppred_block = next(bl for bl in blocks.BLOCKS if bl.name == "ppred")
-    sh = fits._fit_sharded(packed(), opts, dev, 0, 1, ppred_block, S, R, ROUNDS, False, True)
+    run = blocks.describe(opts, {"psis_adapt": ROUNDS, "ppc": True}, with_ppred=True, psis_draws=S, pred_draws=R)
+    sh = fits._fit_sharded(packed(), opts, dev, 0, 1, run)
     assert len(sh) == 6 and np.array_equal(sh[4].view(np.int32), want_pca.view(np.int32))
     assert np.array_equal(sh[5].view(np.int32), want_ad.view(np.int32)) and np.array_equal(sh[3], got[3], equal_nan=True)
 
