@@ -1095,6 +1095,22 @@ int mdfit_objective(const int32_t* model, const int32_t* subset, const uint32_t*
                     double* H, double* ell, void* hip_stream);
 
 /*
+ * The same kernel layout and outputs with the point evaluation's other forms
+ * (the ones the fit kernel takes by wave: tests/test_gpu_map_objective.py).
+ * `form` is a sum of the bits below; each applies to the items whose layout has
+ * it and leaves the others in the plain form.  g and H are the plain form's in
+ * every form; so are F and ell without MDFIT_FORM_ACCF.  Unknown bits: an
+ * argument error, nothing launched.
+ */
+#define MDFIT_FORM_ACCF 1       /* the polish phase's value term: F and ell are the full log-pmf
+                                 * (ln C(N,y) included) in the cancellation-free form */
+#define MDFIT_FORM_NULL_ROW 2   /* model_null items: lg3(a), lg3(b) from the row's pad lane */
+#define MDFIT_FORM_WHOLE_PAIR 4 /* all-position items: lg3(a), lg3(b) shared by the lanes 16 apart */
+int mdfit_objective_form(const int32_t* model, const int32_t* subset, const uint32_t* y,
+                         const uint32_t* N, const double* u, int64_t n, int32_t form, double* F,
+                         double* g, double* H, double* ell, void* hip_stream);
+
+/*
  * Register-only throughput probe of the per-point evaluation the fit kernel
  * runs (value + gradient + Hessian of one beta-binomial point): launches
  * `n_waves` waves that each do `iters` evaluations; `sink` is a device

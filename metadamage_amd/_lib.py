@@ -206,6 +206,7 @@ EXPORTED_SYMBOLS = [
     "mdfit_nuts_peak_probe",
     "mdfit_poison_lds",
     "mdfit_objective",
+    "mdfit_objective_form",
     "mdfit_nuts_potential",
     "mdfit_profile_enable",
     "mdfit_profile_read",
@@ -354,6 +355,8 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.mdfit_nuts_peak_probe.restype = ctypes.c_int
     lib.mdfit_objective.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     lib.mdfit_objective.restype = ctypes.c_int
+    lib.mdfit_objective_form.argtypes = [vp, vp, vp, vp, vp, i64, ctypes.c_int32, vp, vp, vp, vp, vp]
+    lib.mdfit_objective_form.restype = ctypes.c_int
     lib.mdfit_last_error.argtypes = []
     lib.mdfit_last_error.restype = ctypes.c_char_p
     lib.mdfit_abi_version.argtypes = []

@@ -1523,9 +1523,14 @@ __global__ __launch_bounds__(kWave) void peak_probe_kernel(int iters, double* __
 // the fit kernel's own layout and code (all-position: lanes 0..31, halves
 // summed; forward / reverse: lanes 0..15) -- the parity test of the objective
 // itself.  One wave per item; every lane runs (the row-collective pieces).
+// form (mdfit_objective_form): the point evaluation's other forms, each where
+// this layout has it -- MDFIT_FORM_ACCF the polish phase's value term,
+// MDFIT_FORM_NULL_ROW (model_null items) lg3(a), lg3(b) from the row's pad,
+// MDFIT_FORM_WHOLE_PAIR (all-position items) lg3(a), lg3(b) shared by the
+// lanes 16 apart.
 template <int KIND>
 __device__ void objective_group(const uint32_t* gy, const uint32_t* gN, int64_t i, bool pmd,
-                                bool rev, const double u[4], double* F, double* g, double* H,
+                                bool rev, const double u[4], int form, double* F, double* g, double* H,
                                 double* ell_out) {
   const int lane = threadIdx.x;
   const int r = lane & 31, h = r >> 4, k = r & 15;
@@ -1540,7 +1545,9 @@ __device__ void objective_group(const uint32_t* gy, const uint32_t* gN, int64_t 
   double acc[kNAcc];
 #pragma unroll
   for (int j = 0; j < kNAcc; ++j) acc[j] = 0.0;
-  const double ell = point_accum<true>(pd, th, acc);
+  const bool null_row = (form & MDFIT_FORM_NULL_ROW) != 0 && !pmd;
+  const bool whole_pair = (form & MDFIT_FORM_WHOLE_PAIR) != 0 && KIND == kAll;
+  const double ell = point_accum<true>(pd, th, acc, form & MDFIT_FORM_ACCF, null_row, whole_pair);
 #pragma unroll
   for (int j = 0; j < kNAcc; ++j) {
     const double s16 = gsum<16>(acc[j]);
@@ -1573,8 +1580,26 @@ __global__ __launch_bounds__(kWave) void objective_kernel(
 #pragma unroll
   for (int j = 0; j < 4; ++j) u[j] = gu[i * 4 + j];
   const bool pmd = model[i] == 0;
-  if (subset[i] == 0) objective_group<kAll>(gy, gN, i, pmd, false, u, F, g, H, ell_out);
-  else objective_group<kFR>(gy, gN, i, pmd, subset[i] == 2, u, F, g, H, ell_out);
+  if (subset[i] == 0) objective_group<kAll>(gy, gN, i, pmd, false, u, 0, F, g, H, ell_out);
+  else objective_group<kFR>(gy, gN, i, pmd, subset[i] == 2, u, 0, F, g, H, ell_out);
+}
+
+// the same with the point evaluation's form chosen by the caller (mdfit_objective_form)
+__global__ __launch_bounds__(kWave) void objective_form_kernel(
+    const int32_t* __restrict__ model, const int32_t* __restrict__ subset,
+    const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN, const double* __restrict__ gu,
+    int64_t n, int form, double* __restrict__ F, double* __restrict__ g, double* __restrict__ H,
+    double* __restrict__ ell_out) {
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  if (threadIdx.x < kNPos) ell_out[i * kNPos + threadIdx.x] = 0.0;
+  __syncthreads();
+  double u[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) u[j] = gu[i * 4 + j];
+  const bool pmd = model[i] == 0;
+  if (subset[i] == 0) objective_group<kAll>(gy, gN, i, pmd, false, u, form, F, g, H, ell_out);
+  else objective_group<kFR>(gy, gN, i, pmd, subset[i] == 2, u, form, F, g, H, ell_out);
 }
 
 // MDFIT-AUTO v1 (mdfit_auto_route): one thread per taxon, the rule and the
@@ -2235,6 +2260,19 @@ int mdfit_objective(const int32_t* model, const int32_t* subset, const uint32_t*
   hipLaunchKernelGGL(mdfit::objective_kernel, dim3((unsigned)n), dim3(mdfit::kWave), 0,
                      (hipStream_t)hip_stream, model, subset, y, N, u, n, F, g, H, ell);
   return check_launch("objective_kernel");
+}
+
+int mdfit_objective_form(const int32_t* model, const int32_t* subset, const uint32_t* y,
+                         const uint32_t* N, const double* u, int64_t n, int32_t form, double* F,
+                         double* g, double* H, double* ell, void* hip_stream) {
+  if (n < 0 || (n > 0 && (!model || !subset || !y || !N || !u || !F || !g || !H || !ell)))
+    return set_err(MDFIT_E_ARG, "bad arguments");
+  if ((form & ~(MDFIT_FORM_ACCF | MDFIT_FORM_NULL_ROW | MDFIT_FORM_WHOLE_PAIR)) != 0)
+    return set_err(MDFIT_E_ARG, "form: unknown bits");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(mdfit::objective_form_kernel, dim3((unsigned)n), dim3(mdfit::kWave), 0,
+                     (hipStream_t)hip_stream, model, subset, y, N, u, n, (int)form, F, g, H, ell);
+  return check_launch("objective_form_kernel");
 }
 
 int mdfit_map_laplace(const uint32_t* y, const uint32_t* N, const double* out, const int32_t* status,

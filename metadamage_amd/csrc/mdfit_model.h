@@ -206,12 +206,17 @@ __device__ __forceinline__ PointArgs point_args(const PointData& pd, const Theta
     r.Dq = pd.k >= 1 ? -th.A * kk * wq : 0.0;
     r.DqA = pd.k >= 1 ? -kk * wq : 0.0;
     r.Dqq = pd.k >= 2 ? th.A * kk * (kk - 1.0) * (wq * th.iomq) : 0.0;
+    r.omD = 1.0 - r.D;
   } else {
     r.D = th.q;
     r.Dq = 1.0;
     r.DA = r.Dc = r.Dqq = r.DqA = 0.0;
+    // 1 - D from the complementary sigmoid where that side holds it to relative
+    // precision (u0 > 0): 1.0 - q carries 2^-53 / (1 - q) into b = omD phi, and
+    // the J phi psi(b) ~ -1 terms of g and H then no longer cancel (DESIGN.md
+    // §3.4.2).  For q <= 1/2 the subtraction is accurate and its bits stay.
+    r.omD = th.q > 0.5 ? th.omq : 1.0 - th.q;
   }
-  r.omD = 1.0 - r.D;
   r.a = r.D * th.phi;
   r.b = r.omD * th.phi;
   return r;

@@ -1601,9 +1601,11 @@ def profile_read():
     return a.value, b.value, n.value
 
 
-def objective(model, subset, y, N, u, device="cuda"):
+def objective(model, subset, y, N, u, device="cuda", form=None):
     """Per-item sub-fit objective (F, g[4], H[4,4], ell[30]) evaluated by the
-    fit kernel's code path (mdfit_objective)."""
+    fit kernel's code path (mdfit_objective).  form: a sum of the
+    MDFIT_FORM_* bits of include/mdfit.h (1 accf, 2 null_row, 4 whole_pair), the
+    point evaluation's other forms (mdfit_objective_form); None: the plain entry."""
     torch = _torch()
     lib = _lib.load()
     n = len(model)
@@ -1617,7 +1619,11 @@ def objective(model, subset, y, N, u, device="cuda"):
     H = torch.empty((n, 4, 4), dtype=torch.float64, device=device)
     ell = torch.empty((n, 30), dtype=torch.float64, device=device)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(lib.mdfit_objective(ptr(tm), ptr(ts), ptr(ty), ptr(tN), ptr(tu), n, ptr(F), ptr(g), ptr(H),
-                                   ptr(ell), _stream_handle(torch)))
+    if form is None:
+        _lib.check(lib.mdfit_objective(ptr(tm), ptr(ts), ptr(ty), ptr(tN), ptr(tu), n, ptr(F), ptr(g), ptr(H),
+                                       ptr(ell), _stream_handle(torch)))
+    else:
+        _lib.check(lib.mdfit_objective_form(ptr(tm), ptr(ts), ptr(ty), ptr(tN), ptr(tu), n, int(form), ptr(F),
+                                            ptr(g), ptr(H), ptr(ell), _stream_handle(torch)))
     torch.cuda.current_stream().synchronize()
     return F.cpu().numpy(), g.cpu().numpy(), H.cpu().numpy(), ell.cpu().numpy()

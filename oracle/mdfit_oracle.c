@@ -208,7 +208,11 @@ static void evaluate(int model, const uint32_t* y, const uint32_t* N, int lo,
       D = q;
       Dq = 1.0;
     }
-    double omD = 1.0 - D;
+    /* model_null: 1 - D from the complementary sigmoid where that side holds
+     * it to relative precision; 1.0 - q carries 2^-53 / (1 - q) into b, and the
+     * J phi psi(b) ~ -1 terms of g and H then no longer cancel.
+     * For q <= 1/2 the subtraction is accurate and its bits stay. */
+    double omD = (model == M_NULL && u[P_Q] > 0) ? omq : 1.0 - D;
     double a = D * phi, b = omD * phi;
     double t1 = o_lgamma(yy + a), t2 = o_lgamma(NN - yy + b), t3 = o_lgamma(NN + phi);
     double t4 = o_lgamma(a), t5 = o_lgamma(b), t6 = o_lgamma(phi);
@@ -240,8 +244,7 @@ static void evaluate(int model, const uint32_t* y, const uint32_t* N, int lo,
       Hh[j][3] += lDF * dD[j];
     }
     Hh[P_Q][P_Q] += lD * Dqq;
-    Hh[P_Q][P_A] += lD * DqA;
-    Hh[P_A][P_Q] += lD * DqA;
+    Hh[P_A][P_Q] += lD * DqA; /* (the lower triangle is the one read below) */
     G[3] += lF;
     Hh[3][3] += lFF;
   }
@@ -275,10 +278,13 @@ static void evaluate(int model, const uint32_t* y, const uint32_t* N, int lo,
   r->mag = mag;
   for (int j = 0; j < 4; j++) {
     r->g[j] = -(J[j] * G[j] + gp[j]);
-    for (int m = 0; m < 4; m++) {
+    /* the lower triangle (the one direction()'s Cholesky reads), mirrored:
+     * (J_j Hh) J_m and (J_m Hh) J_j round differently, and H is symmetric bit
+     * for bit */
+    for (int m = 0; m <= j; m++) {
       double h = J[j] * Hh[j][m] * J[m];
       if (j == m) h += J2[j] * G[j] + hp[j];
-      r->H[j][m] = -h;
+      r->H[j][m] = r->H[m][j] = -h;
     }
   }
   if (model == M_NULL) { /* A, c are not parameters of model_null */

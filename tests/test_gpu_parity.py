@@ -88,7 +88,9 @@ def test_full_logpmf_vs_long_double_oracle(engine, oracle_lib):
 def test_objective_vs_oracle(engine, oracle_lib):
     """mdfit_objective (the fit kernel's own lane layout and point code) vs the
     oracle's objective: F, gradient, Hessian and pointwise ell of all 6
-    sub-fit kinds at seeded points around the data-driven start."""
+    sub-fit kinds at seeded points around the data-driven start.  Both sides
+    against mpmath, at the edges of the box and at derived bars:
+    tests/test_map_objective.py (oracle), tests/test_gpu_map_objective.py (kernel)."""
     from metadamage_amd.synthetic import generate
 
     b = generate(40, seed=21)
