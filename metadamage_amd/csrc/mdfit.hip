@@ -416,6 +416,17 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
   unsigned long long st_claim1 = 0, st_claim2 = 0;
   const unsigned long long k0 = stamp();
 #endif
+#if defined(MDFIT_STAMP3) && !defined(MDFIT_STAMP2)
+#error "MDFIT_STAMP3 splits what MDFIT_STAMP2 leaves: build with -DMDFIT_STAMP -DMDFIT_STAMP2 -DMDFIT_STAMP3"
+#endif
+#ifdef MDFIT_STAMP3
+  // (-DMDFIT_STAMP -DMDFIT_STAMP2 -DMDFIT_STAMP3: the rest of the Newton logic,
+  // in the record's slots 0..3 and 6 in place of eval / reduce / logic / fetch
+  // and finish_eval + pgnorm -- acceptance and backtracking, the ut update, the
+  // done / diag-write path, priority and ballot, the publication; slot 7 stays
+  // newton_dir)
+  unsigned long long st_acc = 0, st_ut = 0, st_done = 0, st_prio = 0, st_pub = 0;
+#endif
 
   while (true) {
 #ifdef MDFIT_STAMP
@@ -631,6 +642,9 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
       // logic -- finish_eval + pgnorm, and newton_dir)
       st_claim1 += stamp() - e2;
 #endif
+#ifdef MDFIT_STAMP3
+      const unsigned long long c0 = stamp(), ndb = st_claim2;
+#endif
       bool accept = false, done = false;
       // the saddle escape's re-evaluation at u (same F, g, H as the current
       // point) goes through the acceptance below; its H gives the direction
@@ -784,9 +798,16 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
         done = true;
         status = MDFIT_MAXITER;
       }
+#ifdef MDFIT_STAMP3
+      const unsigned long long c1 = stamp();
+      st_acc += (c1 - c0) - (st_claim2 - ndb);
+#endif
       if (!done) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) ut[j] = clampd(fma(t, d[j], u[j]), kULo[j], kUHi[j]);
+#ifdef MDFIT_STAMP3
+        st_ut += stamp() - c1;
+#endif
       } else {
         // lanes 0..7 of the half write the diag slots (for an all-position fit
         // the forward half only)
@@ -801,8 +822,14 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
         }
         allok = status == MDFIT_OK;  // (read after an all-position fit: the pair's warm start)
         running = false;
+#ifdef MDFIT_STAMP3
+        st_done += stamp() - c1;
+#endif
       }
     }
+#ifdef MDFIT_STAMP3
+    const unsigned long long p0 = stamp();
+#endif
     // waves holding a long fit (the critical path of small batches) win issue
     // arbitration: +5 % at C2, no change at 100k taxa (A/B of thresholds
     // 12/15/20/30 and of chain- vs fit-length counting: 15 by fit length best)
@@ -814,6 +841,10 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
     // a slot is free when neither half is running: an all-position fit then
     // continues with its pair, a pair with the next task
     const unsigned long long busy = __ballot(running);
+#ifdef MDFIT_STAMP3
+    const unsigned long long p1 = stamp();
+    st_prio += p1 - p0;
+#endif
     if ((busy & slot_mask) == 0ull) {
       if (mode == kAllFit) {
         if (sub == 0) {
@@ -857,6 +888,9 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
         mode = kIdle;
       }
     }
+#ifdef MDFIT_STAMP3
+    st_pub += stamp() - p1;
+#endif
 #ifdef MDFIT_STAMP
     const unsigned long long l1 = stamp();
     st_fetch += e0 - f0;
@@ -877,6 +911,13 @@ void fit_kernel(const uint32_t* __restrict__ gy, const uint32_t* __restrict__ gN
     rr[5] = stamp() - k0;
     rr[6] = st_claim1;
     rr[7] = st_claim2;
+#ifdef MDFIT_STAMP3
+    rr[0] = st_acc;
+    rr[1] = st_ut;
+    rr[2] = st_done;
+    rr[3] = st_prio;
+    rr[6] = st_pub;
+#endif
   }
 #endif
 }
@@ -2458,6 +2499,19 @@ int mdfit_psis_weights(const double* lw, int64_t n_series, int32_t S, double* w,
 int mdfit_set_stamp(unsigned long long* buf) {
   hipMemcpyToSymbol(HIP_SYMBOL(mdfit::g_stamp), &buf, sizeof(buf));
   return 0;
+}
+// what the record's slots hold: 1 the four parts and the two claims, 2
+// (-DMDFIT_STAMP2) slots 6 / 7 finish_eval + pgnorm and newton_dir, 3
+// (-DMDFIT_STAMP3) slots 0..3 and 6 the rest of the Newton logic.
+// tools/stamp_profile.py refuses a build whose mode is not the one it prints.
+int mdfit_stamp_mode(void) {
+#if defined(MDFIT_STAMP3)
+  return 3;
+#elif defined(MDFIT_STAMP2)
+  return 2;
+#else
+  return 1;
+#endif
 }
 #endif
 

@@ -98,6 +98,18 @@ __device__ __forceinline__ double xrow(double v) {
   return __hiloint2double((int)(odd ? rh[0] : rh[1]), (int)(odd ? rl[0] : rl[1]));
 }
 
+// Both directions of that exchange from one swap per dword, without a select:
+// given v, `even` is on every lane the value held by the even row of its pair
+// of rows (rows 0 and 2: the lane's own there, its partner's on the odd rows),
+// `odd` the one held by the odd row.
+__device__ __forceinline__ void xrow_pair(double v, double& even, double& odd) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  even = __hiloint2double((int)rh[0], (int)rl[0]);
+  odd = __hiloint2double((int)rh[1], (int)rl[1]);
+}
+
 // Broadcast lane N of every 16-lane DPP row to the whole row (row_newbcast).
 template <int N>
 __device__ __forceinline__ double rowb(double v) {
@@ -302,27 +314,41 @@ __device__ __forceinline__ LG3 rowb3(const LG3& t) {
 // all-position fit, rows z > 0 and z < 0 at the same |z| lane by lane, so a
 // lane and its partner 16 away have the same a and b: the even row computes
 // lg3(a), the odd row lg3(b), and they exchange (xrow): 4 lg3 instead of 5.
+//
+// The pad's neutral argument (kRowPhi only).  A lane that holds no point (y = N
+// = 0) evaluates lg3 at a = D(1) phi and b = (1 - D(1)) phi, which are below 10
+// far more often than any real y + a or N - y + b -- and lg3's small-argument
+// shift (the product with two derivatives, one more reciprocal and log) is run
+// by the whole wave when one lane needs it.  Those triples are read only under
+// null_row (the broadcast above); a pad's own terms are never accumulated, and
+// its partner in the whole_pair exchange is the other row's pad.  So without
+// null_row such a lane evaluates them at kPadArg instead: no result changes,
+// and the wave takes the shift only where a real point needs it.  Its
+// lg3(N + phi) stays: that is the row's phi triple.
+constexpr double kPadArg = 16.0;
 template <bool kRowPhi = false>
 __device__ __forceinline__ double point_accum(const PointData& pd, const Theta& th, double acc[kNAcc],
                                               int accf = 0, bool null_row = false, bool whole_pair = false) {
   const PointArgs pa = point_args(pd, th);
   const LG3 t3 = lg3<true>(pd.N + th.phi);
   const LG3 t6 = kRowPhi ? rowb3<15>(t3) : lg3<true>(th.phi);
-  const LG3 t1 = lg3<true>(pd.y + pa.a);
-  const LG3 t2 = lg3<true>(pd.N - pd.y + pa.b);
+  const bool neutral = kRowPhi && !pd.valid && !null_row;
+  const LG3 t1 = lg3<true>(neutral ? kPadArg : pd.y + pa.a);
+  const LG3 t2 = lg3<true>(neutral ? kPadArg : pd.N - pd.y + pa.b);
   LG3 t4, t5;
   if (kRowPhi && null_row) {
     t4 = rowb3<15>(t1);
     t5 = rowb3<15>(t2);
   } else if (kRowPhi && whole_pair) {
     const bool odd = (threadIdx.x & 16) != 0;
-    const LG3 mine = lg3<true>(odd ? pa.b : pa.a);
-    const LG3 other = {xrow(mine.l), xrow(mine.p), xrow(mine.q)};
-    t4 = odd ? other : mine;
-    t5 = odd ? mine : other;
+    const LG3 mine = lg3<true>(neutral ? kPadArg : (odd ? pa.b : pa.a));
+    // (the even rows hold lg3(a), the odd rows lg3(b): the swap's two results)
+    xrow_pair(mine.l, t4.l, t5.l);
+    xrow_pair(mine.p, t4.p, t5.p);
+    xrow_pair(mine.q, t4.q, t5.q);
   } else {
-    t4 = lg3<true>(pa.a);
-    t5 = lg3<true>(pa.b);
+    t4 = lg3<true>(neutral ? kPadArg : pa.a);
+    t5 = lg3<true>(neutral ? kPadArg : pa.b);
   }
   return point_finish(pd, th, pa, t1, t2, t3, t4, t5, t6, acc, accf);
 }
@@ -549,7 +575,14 @@ __device__ __forceinline__ bool newton_dir(bool pmd, const double u[4], const do
     for (int j = 0; j < 4; ++j)
       if (fr[j]) sc = fmax(sc, fabs(H[hidx(j, j)]));
     if (sc == 0.0) sc = 1.0;
-    const int kl = (int)(threadIdx.x & (G - 1));
+    // (kl opaque: the G - 1 compares i <= kl below are invariant lane masks,
+    // which the optimiser otherwise hoists out of the caller's fit loop into
+    // SGPR pairs -- 30 scalar registers at G = 16, spilled to VGPR lanes and
+    // read back around every use -- for a block that few trips enter.  G = 16
+    // only, the one-point-per-lane layout: at G = 8 it was measured to change
+    // nothing, and that kernel's code stays what it was)
+    int kl = (int)(threadIdx.x & (G - 1));
+    if (G == 16) asm volatile("" : "+v"(kl));
     const int gbase = (int)(threadIdx.x & ~(G - 1));
     double mu = 1e-10 * sc;
 #pragma unroll
